@@ -6,9 +6,11 @@ AdamW — all in libvadhip kernels — on B=8 synthetic Avenue/UCSD-shaped clips
 Data parallel for --gpus N > 1 (launched by torch.distributed.run): 8 clips per rank, gradients summed over
 RCCL; value = all clips processed / max-over-ranks wall time (weak scaling).
 
-Prints ONE JSON line (rank 0).  `roofline` covers the dominant kernel family of the step, timed live with HIP
-events inside the timed region; `cpu_baseline` times the CPU oracle (oracle/cad_oracle.py, a port of the
-reference step) on this host's cores on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps, writes the last timed step's
+outputs (--dump-outputs DIR) and prints the headline.  --full adds the legs beside it: `roofline` covers the dominant
+kernel family of the step, timed live with HIP events in instrumented steps after the timed region; `cpu_baseline`
+times the CPU oracle (oracle/cad_oracle.py, a port of the reference step) on this host's cores on a bounded sample;
+`parity` compares a probe forward with that oracle; `h2d_inclusive` / `dropin_loop` feed the step from host memory.
 """
 from __future__ import annotations
 
@@ -182,6 +184,33 @@ def host_cpu_info(threads):
     return {"cores": threads, "os_cpu_count": os.cpu_count(), "affinity_cpus": aff, "cpu_quota": cpu_quota()}
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: total size of the .npy files
+
+
+def dump_outputs(args, rank, named):
+    """--dump-outputs DIR (rank 0): what the last timed step returned to its caller, one DIR/<name>.npy per array in
+    float32 (float64 arrays stay float64).  An output set above DUMP_MAX_BYTES is cut to a fixed sample: every array
+    keeps the same share of its elements, drawn without replacement by default_rng(0) (sorted flat indices)."""
+    if not args.dump_outputs or rank != 0:
+        return
+    import numpy as np
+    import torch
+    arrs = {}
+    for name, v in named.items():
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        arrs[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        keep = 0.95 * DUMP_MAX_BYTES / total
+        rng = np.random.default_rng(0)
+        for name, a in arrs.items():
+            idx = np.sort(rng.choice(a.size, size=max(1, int(a.size * keep)), replace=False))
+            arrs[name] = a.reshape(-1)[idx]
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
+
 def run_gpu(args, rank, world, local_rank):
     import torch
     import torch.distributed as dist
@@ -215,26 +244,29 @@ def run_gpu(args, rank, world, local_rank):
 
     # one instrumented step: per-label kernel times -> the dominant kernel family (largest summed time over the conv
     # families, the weight gradients included although they run on their own stream beside the input gradients)
+    # (--full only: a plain run goes from the warm-up straight to the timed region)
     eng = trainer.eng
-    eng.profile(True, "")
-    trainer.step(pool[0], labels, inputs_ready=True)
-    torch.cuda.synchronize()
-    breakdown = eng.profile_read()
-    fam_time = {}
-    for lab, (ms, n) in breakdown.items():
-        if lab.split("/L")[0] in CONV_FAMILIES:
-            fam = lab.split("/L")[0]
-            fam_time[fam] = fam_time.get(fam, 0.0) + ms
-    dominant = max(fam_time, key=fam_time.get)
-    # (the largest family on the critical stream: conv_wgrad is overlapped, DESIGN.md §3 Streams)
-    critical = max((f for f in fam_time if f != "conv_wgrad"), key=fam_time.get)
+    if args.full:
+        eng.profile(True, "")
+        trainer.step(pool[0], labels, inputs_ready=True)
+        torch.cuda.synchronize()
+        breakdown = eng.profile_read()
+        fam_time = {}
+        for lab, (ms, n) in breakdown.items():
+            if lab.split("/L")[0] in CONV_FAMILIES:
+                fam = lab.split("/L")[0]
+                fam_time[fam] = fam_time.get(fam, 0.0) + ms
+        dominant = max(fam_time, key=fam_time.get)
+        # (the largest family on the critical stream: conv_wgrad is overlapped, DESIGN.md §3 Streams)
+        critical = max((f for f in fam_time if f != "conv_wgrad"), key=fam_time.get)
 
     # timed region: K uninstrumented steps (the headline).  The per-family kernel times for the roofline come from a
     # separate instrumented phase right after it (every conv family's kernels dispatched with HIP start/stop events,
     # hipExtLaunchKernel, on the stream each runs on), so the headline carries no profiling overhead; that phase's own
     # step time is reported beside it (prof_ms_per_step)
-    eng.profile(True, "conv_")  # clears the breakdown records
-    eng.profile(False)
+    if args.full:
+        eng.profile(True, "conv_")  # clears the breakdown records
+        eng.profile(False)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -247,6 +279,21 @@ def run_gpu(args, rank, world, local_rank):
         dist.barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    dump_outputs(args, rank, {"losses": losses})  # (now: the steps of the --full legs below reuse the loss buffer)
+    # whole-step algorithmic FLOP rate (all 3x3 convs fwd/dgrad/wgrad + conv1 fwd), for context
+    conv_flops = sum(2.0 * NF * oh * ow * co * ci * 9 for NF, ci, co, oh, ow in conv_shapes(B, T, H, W))
+    dgrad_flops = conv_flops - 2.0 * B * T * conv_shapes(B, T, H, W)[0][3] * conv_shapes(B, T, H, W)[0][4] * 32 * 32 * 9
+    c1 = algorithmic_work("conv1", B, T, H, W)[1]
+    step_flops = 2 * conv_flops + dgrad_flops + c1
+    if not args.full:
+        if world > 1:
+            t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+        step_ms = 1e3 * elapsed / args.steps
+        return dict(elapsed=elapsed, step_ms=step_ms, host_enqueue_ms=1e3 * (t_enq - t_loop0) / args.steps,
+                    final_loss=float(losses[4].item()), step_tflops=step_flops / (step_ms * 1e-3) / 1e12,
+                    allreduce_bytes=4 * trainer.allreduce_floats if trainer.dist else 0)
     n_prof = max(3, args.steps // max(1, args.prof_every))
     eng.profile(True, "conv_", reset=False)
     tp0 = time.perf_counter()
@@ -367,11 +414,6 @@ def run_gpu(args, rank, world, local_rank):
                   "path": "vad_amd.train.train_epoch (train_model's inner loop): pinned u8 loader -> prefetch / "
                           "ClipStager (batch k+1 staged during step k) -> CadTrainer.step(inputs_ready=event, "
                           "host_losses=True) -> losses.tolist() every step (cad:692's loss.item())"}
-    # whole-step algorithmic FLOP rate (all 3x3 convs fwd/dgrad/wgrad + conv1 fwd), for context
-    conv_flops = sum(2.0 * NF * oh * ow * co * ci * 9 for NF, ci, co, oh, ow in conv_shapes(B, T, H, W))
-    dgrad_flops = conv_flops - 2.0 * B * T * conv_shapes(B, T, H, W)[0][3] * conv_shapes(B, T, H, W)[0][4] * 32 * 32 * 9
-    c1 = algorithmic_work("conv1", B, T, H, W)[1]
-    step_flops = 2 * conv_flops + dgrad_flops + c1
     roof["instrumented_steps"] = n_prof
     roof["instrumented_ms_per_step"] = round(prof_ms_per_step, 4)
     return dict(elapsed=elapsed, step_ms=step_ms, host_enqueue_ms=1e3 * (t_enq - t_loop0) / args.steps, roof=roof,
@@ -520,9 +562,13 @@ def run_bbox(args, rank, world, local_rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     frames = int(sum(x.shape[0] * x.shape[2] for x in groups.values()))
-    probe = {T: (x[:2].cpu(), o[0].reshape(-1)[:2].cpu()) for (T, x), o in zip(groups.items(), out)}
-    return dict(elapsed=elapsed, step_ms=1e3 * elapsed / args.steps, frames=frames, Ts=Ts.tolist(),
-                state={k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, probe=probe)
+    dump_outputs(args, rank, {f"{name}_T{T}": v for T, o in zip(groups, out)
+                              for name, v in zip(("scores", "adjacency", "features"), o)})
+    r = dict(elapsed=elapsed, step_ms=1e3 * elapsed / args.steps, frames=frames, Ts=Ts.tolist())
+    if args.full:  # (the CPU leg's inputs)
+        r["probe"] = {T: (x[:2].cpu(), o[0].reshape(-1)[:2].cpu()) for (T, x), o in zip(groups.items(), out)}
+        r["state"] = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    return r
 
 
 def bbox_cpu(args, r):
@@ -623,12 +669,15 @@ def run_mc(args, rank, world, local_rank):
         loss, acc = tr.train_epoch()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    model.eval()
-    with torch.no_grad():
-        probe = model(batches[0][0]).reshape(-1).cpu()
-    state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-    return dict(elapsed=elapsed, step_ms=1e3 * elapsed / args.steps, loss=loss, probe=probe, state=state,
-                x0=batches[0][0].cpu())
+    dump_outputs(args, rank, {"loss": loss, "accuracy": acc})
+    r = dict(elapsed=elapsed, step_ms=1e3 * elapsed / args.steps, loss=loss)
+    if args.full:  # (the CPU leg's inputs)
+        model.eval()
+        with torch.no_grad():
+            r["probe"] = model(batches[0][0]).reshape(-1).cpu()
+        r["state"] = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+        r["x0"] = batches[0][0].cpu()
+    return r
 
 
 def mc_cpu(args, r):
@@ -707,10 +756,13 @@ def run_ae(args, rank, world, local_rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     lv = losses.cpu().tolist()
-    ev = tr.eval_batch(x[:4])
-    probe = {"x": x[:4].cpu(), "recon_error": ev["recon_error"].cpu(), "score": ev["anomaly_score"].cpu(),
-             "state": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}}
-    return dict(elapsed=elapsed, step_ms=1e3 * elapsed / args.steps, loss=lv[0], status=lv[3], probe=probe)
+    dump_outputs(args, rank, {"losses": losses})
+    r = dict(elapsed=elapsed, step_ms=1e3 * elapsed / args.steps, loss=lv[0], status=lv[3])
+    if args.full:  # (the CPU leg's inputs)
+        ev = tr.eval_batch(x[:4])
+        r["probe"] = {"x": x[:4].cpu(), "recon_error": ev["recon_error"].cpu(), "score": ev["anomaly_score"].cpu(),
+                      "state": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}}
+    return r
 
 
 def ae_cpu(args, r):
@@ -793,11 +845,14 @@ def run_a2(args, rank, world, local_rank):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    xp = x[:4]
-    preds, graphs, _ = vad.evaluate_improved([(xp, y[:4])])
-    probe = {"x": xp.cpu(), "preds": preds, "graphs": graphs,
-             "state": {k: v.detach().cpu().clone() for k, v in vad.model.state_dict().items()}}
-    return dict(elapsed=elapsed, step_ms=1e3 * elapsed / args.steps, loss=loss, stepped=stepped, probe=probe)
+    dump_outputs(args, rank, {"loss": loss, "loss_components": list(comps.values()), "stepped": stepped})
+    r = dict(elapsed=elapsed, step_ms=1e3 * elapsed / args.steps, loss=loss, stepped=stepped)
+    if args.full:  # (the CPU leg's inputs)
+        xp = x[:4]
+        preds, graphs, _ = vad.evaluate_improved([(xp, y[:4])])
+        r["probe"] = {"x": xp.cpu(), "preds": preds, "graphs": graphs,
+                      "state": {k: v.detach().cpu().clone() for k, v in vad.model.state_dict().items()}}
+    return r
 
 
 def a2_cpu(args, r):
@@ -875,6 +930,12 @@ def main():
     ap.add_argument("--W", type=int, default=None)
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default=None,
                     help="fp32: fp32 numerics; bf16: backbone 3x3 convs on bf16 operands (fp32 accumulate)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: instrumented steps for the "
+                         "roofline and the per-kernel breakdown, the CPU baseline and parity probe (unless "
+                         "--no-cpu-baseline), the input-inclusive and drop-in loop legs (--h2d-steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned to its caller as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--prof-every", type=int, default=4,
                     help="after the timed region, steps // k instrumented steps (at least 3) give the roofline events")
@@ -890,6 +951,8 @@ def main():
     ap.add_argument("--tune", action="append", default=[], metavar="KNOB=V",
                     help="measurement only: set a libvadhip tuning knob (vad_set_tuning) before the run")
     args = ap.parse_args()
+    if args.breakdown_out and not args.full:
+        ap.error("--breakdown-out needs --full (the breakdown comes from an instrumented step)")
     # --gpus N: one process per GPU.  Launched without torch.distributed.run (no WORLD_SIZE), bench.py starts the N
     # ranks itself as a child torch.distributed.run before anything touches the GPU and exits with its status;
     # launched by torch.distributed.run, the world size must be N.
@@ -934,7 +997,7 @@ def main():
     if args.config == 1:
         r = run_mc(args, rank, world, local_rank)
         if rank == 0:
-            cpu, parity = (None, None) if args.no_cpu_baseline else mc_cpu(args, r)
+            cpu, parity = mc_cpu(args, r) if args.full and not args.no_cpu_baseline else (None, None)
             clips = world * args.batch * args.steps
             tflops = MC_TRAIN_FLOP_PER_CLIP * clips / r["elapsed"] / 1e12
             print(json.dumps({
@@ -956,7 +1019,7 @@ def main():
     if args.config == "cad1":
         r = run_ae(args, rank, world, local_rank)
         if rank == 0:
-            cpu, parity = (None, None) if args.no_cpu_baseline else ae_cpu(args, r)
+            cpu, parity = ae_cpu(args, r) if args.full and not args.no_cpu_baseline else (None, None)
             clips = world * args.batch * args.steps
             tflops = ae_flops_per_clip(args.T) * args.batch / (r["step_ms"] * 1e-3) / 1e12
             print(json.dumps({
@@ -980,7 +1043,7 @@ def main():
     if args.config == "a2":
         r = run_a2(args, rank, world, local_rank)
         if rank == 0:
-            cpu, parity = (None, None) if args.no_cpu_baseline else a2_cpu(args, r)
+            cpu, parity = a2_cpu(args, r) if args.full and not args.no_cpu_baseline else (None, None)
             clips = world * args.batch * args.steps
             fpc = a2_flops_per_clip(args.T, args.H, args.W)
             tflops = fpc * args.batch / (r["step_ms"] * 1e-3) / 1e12
@@ -1007,7 +1070,7 @@ def main():
     if args.config == 5:
         r = run_bbox(args, rank, world, local_rank)
         if rank == 0:
-            cpu, parity = (None, None) if args.no_cpu_baseline else bbox_cpu(args, r)
+            cpu, parity = bbox_cpu(args, r) if args.full and not args.no_cpu_baseline else (None, None)
             clips = world * args.batch * args.steps
             print(json.dumps({
                 "metric": BASELINE_METRIC, "value": round(clips / r["elapsed"], 3), "unit": "clips/s",
@@ -1024,7 +1087,7 @@ def main():
         return
     r = run_gpu(args, rank, world, local_rank)
     if rank == 0:
-        cpu = None if args.no_cpu_baseline else cpu_baseline(args)
+        cpu = cpu_baseline(args) if args.full and not args.no_cpu_baseline else None
         parity = None if (args.no_cpu_baseline or r.get("probe") is None) else parity_check(args, r["probe"])
         clips = world * args.batch * args.steps
         out = {
@@ -1044,7 +1107,7 @@ def main():
                                    + (("2" if world == 1 else "3") if args.config == 2 else "4"),
                        "clips_per_gpu": args.batch, "global_batch": world * args.batch, "clip_len": args.T,
                        "frame": f"1x{args.H}x{args.W}", "parallelism": f"dp{world}"},
-            "roofline": r["roof"],
+            "roofline": r.get("roof"),
             "cpu_baseline": cpu,
             "parity": parity,
             "h2d_inclusive": r.get("h2d"),

@@ -1,4 +1,5 @@
 """Helpers shared by the parity tests: golden fixture loading and reference-identical model construction."""
+import contextlib
 import glob
 import os
 
@@ -12,6 +13,25 @@ A2_CKPT = "a2_best_improved_model.npz"
 
 def load(name):
     return dict(np.load(os.path.join(GOLDEN_DIR, name), allow_pickle=False))
+
+
+@contextlib.contextmanager
+def recording_threads():
+    """The torch CPU thread count the golden vectors were recorded at (8, make_golden.py): torch splits CPU sums by
+    its thread count, so comparisons at rounding level hold only on that partition, whatever the host's CPU count or
+    OMP_NUM_THREADS."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(n)
+
+
+def init_checksums(t):
+    """(sum, sum of squares) of a tensor in float64, as make_golden.py recorded them (init_sum / init_sq)."""
+    with recording_threads():
+        return np.float64(t.double().sum()), np.float64((t.double() ** 2).sum())
 
 
 def cad_cases():

@@ -7,7 +7,7 @@ import torch
 
 from oracle import a2_oracle as ao
 from tests.golden.cases import A2_CASES
-from tests.golden_util import A2_CKPT, load
+from tests.golden_util import A2_CKPT, init_checksums, load
 
 
 def make_a2_model(case):
@@ -27,8 +27,9 @@ def test_a2_init_matches_reference(case):
     torch.manual_seed(case["seed"])
     m = CausalAnomalyDetector()
     for n, t in m.state_dict().items():
-        assert np.float64(t.double().sum()) == g[f"init_sum/{n}"], n
-        assert np.float64((t.double() ** 2).sum()) == g[f"init_sq/{n}"], n
+        s, sq = init_checksums(t)
+        assert s == g[f"init_sum/{n}"], n
+        assert sq == g[f"init_sq/{n}"], n
 
 
 def test_a2_checkpoint_fixture_loads_strict():

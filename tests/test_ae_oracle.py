@@ -6,7 +6,7 @@ import torch
 
 from oracle import ae_oracle as ae
 from tests.golden.cases import AE_CASES
-from tests.golden_util import ae_case_data, ae_memory_init, load
+from tests.golden_util import ae_case_data, ae_memory_init, init_checksums, load
 
 # conv / conv-transpose biases feeding a train-mode BatchNorm: exactly-zero true gradient (BN removes the mean)
 PRE_BN_BIASES = ("encoder.0.bias", "encoder.3.bias", "encoder.6.bias", "encoder.9.bias", "decoder.3.bias",
@@ -32,8 +32,9 @@ def test_ae_init_matches_reference(case):
     torch.manual_seed(case["seed"])
     m = VideoAutoEncoder(input_channels=1, latent_dim=64)
     for n, t in m.state_dict().items():
-        assert np.float64(t.double().sum()) == g[f"init_sum/{n}"], n
-        assert np.float64((t.double() ** 2).sum()) == g[f"init_sq/{n}"], n
+        s, sq = init_checksums(t)
+        assert s == g[f"init_sum/{n}"], n
+        assert sq == g[f"init_sq/{n}"], n
 
 
 def run_oracle(case):

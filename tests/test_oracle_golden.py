@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from oracle import cad_oracle as co
-from tests.golden_util import cad_cases, load, make_cad_model
+from tests.golden_util import cad_cases, init_checksums, load, make_cad_model
 
 CASES = cad_cases()
 
@@ -23,8 +23,9 @@ def test_init_matches_reference(case):
     from vad_amd.cad import CausalAnomalyDetector
     m = CausalAnomalyDetector()
     for n, t in m.state_dict().items():
-        assert np.float64(t.double().sum()) == pytest.approx(g[f"init_sum/{n}"], rel=0, abs=0), n
-        assert np.float64((t.double() ** 2).sum()) == pytest.approx(g[f"init_sq/{n}"], rel=0, abs=0), n
+        s, sq = init_checksums(t)
+        assert s == pytest.approx(g[f"init_sum/{n}"], rel=0, abs=0), n
+        assert sq == pytest.approx(g[f"init_sq/{n}"], rel=0, abs=0), n
 
 
 def _run_oracle(case):

@@ -1,4 +1,4 @@
-"""Summarise a bench.py --breakdown-out JSON: per-family totals and per-layer conv times with TFLOP/s."""
+"""Summarise a bench.py --full --breakdown-out JSON: per-family totals and per-layer conv times with TFLOP/s."""
 import json
 import sys
 
