@@ -67,6 +67,15 @@ _SIGS = {
     "vad_set_tuning": (_I, [ctypes.c_char_p, _I]),
     "vad_conv3x3_wgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I64, _P]),
     "vad_bn_bwd_apply": (_I, [_P, _P, _P, _I, _I, _P, _I, _P]),
+    # 3-D building blocks (kernel unit tests)
+    "vad_conv3d_scratch_floats": (_I64, [_I] * 11),
+    "vad_conv3d_forward": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I64, _P]),
+    "vad_conv3d_dgrad": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I64, _P]),
+    "vad_conv3d_wgrad": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I64, _P]),
+    "vad_maxpool3d_forward": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "vad_maxpool3d_backward": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "vad_adaptive_avgpool3d_forward": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "vad_adaptive_avgpool3d_backward": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     # minicausal (config 1)
     "vad_mc_create": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "vad_mc_destroy": (None, [_P]),

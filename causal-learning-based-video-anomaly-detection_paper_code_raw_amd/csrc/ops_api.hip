@@ -1,6 +1,8 @@
-// Stand-alone entry points for single building blocks (dense layer, 3x3 conv) used by the kernel unit tests.
+// Stand-alone entry points for single building blocks (dense layer, 3x3 conv, the 3-D clip blocks) used by the kernel
+// unit tests.
 #include "../../include/vad.h"
 #include "backbone.h"
+#include "conv3d.h"
 
 using namespace vad;
 
@@ -49,4 +51,175 @@ extern "C" int vad_bn_bwd_apply(const void* dA, const void* y, const float* stat
   int nb = 0;
   return bn_bwd_apply(reinterpret_cast<const float*>(dA), reinterpret_cast<const float*>(y), stats, M, C,
                       reinterpret_cast<float*>(dY), nullptr, &nb, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The 3-D building blocks of the clip-level CNNs, one kernel family per call (the plans pick a family by shape and
+// knobs; the unit tests pin each at the shapes the plans accept).  Thin wrappers: weight images, columns and split-K
+// slabs are carved from the caller's scratch in the order the plans keep them.
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int64_t kAlign = 64;  // floats: every carved region starts 256-byte aligned
+int64_t up(int64_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
+
+struct Conv3dCall {
+  Vol5 in;
+  Conv3dGeom g;
+  int Co, path;
+};
+
+// kind 0 forward / 1 input gradient / 2 weight gradient; sets the error text and returns non-zero when `path` does not
+// run this combination
+int conv3d_call(int kind, int path, int layout, int N, int Ci, int D, int H, int W, int Co, int sd, int sh, int sw,
+                bool gate, Conv3dCall* c) {
+  VAD_CHECK(kind >= 0 && kind <= 2 && N >= 1 && Ci >= 1 && Co >= 1 && D >= 1 && H >= 1 && W >= 1 && sd >= 1 &&
+                sh >= 1 && sw >= 1 && (layout == 0 || layout == 1),
+            "vad_conv3d: unsupported shape");
+  const bool s1 = sd == 1 && sh == 1 && sw == 1, s2 = sd == 2 && sh == 2 && sw == 2;
+  switch (path) {
+    case 0:
+      VAD_CHECK(!gate, "vad_conv3d: path 0 (im2col) has no fused gate");
+      break;
+    case 1:
+      VAD_CHECK(s1, "vad_conv3d: path 1 (direct) is stride 1");
+      VAD_CHECK(Ci <= 16 && (Co == 8 || Co == 16 || Co == 32), "vad_conv3d: path 1 (direct) needs Ci <= 16 and Co in {8, 16, 32}");
+      VAD_CHECK(kind != 1 || Ci == 8 || Ci == 16, "vad_conv3d: path 1 (direct) input gradient needs Ci in {8, 16}");
+      VAD_CHECK(!gate, "vad_conv3d: path 1 (direct) has no fused gate");
+      break;
+    case 2:
+      VAD_CHECK(s2, "vad_conv3d: path 2 (conv3s2) is stride 2 on all three axes");
+      VAD_CHECK(Ci % 4 == 0 && Co % 4 == 0, "vad_conv3d: path 2 (conv3s2) needs Ci % 4 == 0 and Co % 4 == 0");
+      VAD_CHECK(layout == 1, "vad_conv3d: path 2 (conv3s2) reads NDHWC");
+      break;
+    case 3:
+      VAD_CHECK(kind == 0, "vad_conv3d: path 3 (x3) is forward only");
+      VAD_CHECK(s1, "vad_conv3d: path 3 (x3) is stride 1");
+      VAD_CHECK(Ci % 16 == 0 && Co % 32 == 0, "vad_conv3d: path 3 (x3) needs Ci % 16 == 0 and Co % 32 == 0");
+      VAD_CHECK(layout == 1, "vad_conv3d: path 3 (x3) reads NDHWC");
+      break;
+    default:
+      VAD_CHECK(false, "vad_conv3d: unknown path");
+  }
+  c->in = Vol5{N, Ci, D, H, W};
+  c->g = conv3d_geom(c->in, Co, 3, sd, sh, sw, 1);
+  c->Co = Co;
+  c->path = path;
+  VAD_CHECK(c->g.rows() * c->g.K() < (1ll << 31) && c->in.numel() < (1ll << 31) && c->g.rows() * Co < (1ll << 31),
+            "vad_conv3d: volume too large for a unit call");
+  return 0;
+}
+
+int64_t conv3d_min_scratch(int kind, const Conv3dCall& c) {
+  const int64_t wimg = 27ll * c.in.C * c.Co, cols = c.g.rows() * c.g.K();
+  switch (c.path) {
+    case 0: return up(cols) + (kind == 2 ? (int64_t)c.Co * (c.g.K() + 1) : 0);
+    case 1: return kind == 2 ? conv3d_direct_wgrad_slab_floats(c.in, c.Co) : 2 * up(wimg);
+    case 2: return kind == 2 ? (int64_t)c.Co * (27 * c.in.C + 1) : 2 * up(wimg);
+    default: return up(wimg);
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t vad_conv3d_scratch_floats(int kind, int path, int N, int Ci, int D, int H, int W, int Co, int sd,
+                                             int sh, int sw) {
+  Conv3dCall c;
+  if (conv3d_call(kind, path, 1, N, Ci, D, H, W, Co, sd, sh, sw, false, &c) != 0) return -1;
+  return conv3d_min_scratch(kind, c);
+}
+
+extern "C" int vad_conv3d_forward(const float* x, int layout, int N, int Ci, int D, int H, int W, const float* w,
+                                  const float* bias, int Co, int sd, int sh, int sw, int path, float* y, float* scratch,
+                                  int64_t scratch_floats, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  Conv3dCall c;
+  VAD_TRY(conv3d_call(0, path, layout, N, Ci, D, H, W, Co, sd, sh, sw, false, &c));
+  VAD_CHECK(scratch && scratch_floats >= conv3d_min_scratch(0, c), "vad_conv3d_forward: scratch too small");
+  const Strides5 str = layout == 0 ? ncdhw_strides(c.in) : ndhwc_strides(c.in);
+  const int64_t wimg = up(27ll * Ci * Co);
+  if (path == 0) {
+    const int64_t cols = up(c.g.rows() * c.g.K());
+    VAD_TRY(im2col3d(x, str, c.g, nullptr, nullptr, 0, scratch, st));
+    return dense_fwd(scratch, (int)c.g.rows(), c.g.K(), w, bias, Co, y, DenseAct{}, scratch + cols,
+                     scratch_floats - cols, st);
+  }
+  if (path == 1) {
+    VAD_TRY(conv3d_direct_prep(w, Co, Ci, scratch, scratch + wimg, st));
+    return conv3d_direct_fwd(x, str, c.in, scratch, Co, bias, y, st);
+  }
+  if (path == 2) {
+    VAD_TRY(conv3s2_prep(w, Co, Ci, scratch, scratch + wimg, st));
+    return conv3s2_fwd(x, N, D, H, W, Ci, scratch, bias, Co, 0, y, st, scratch + 2 * wimg, scratch_floats - 2 * wimg);
+  }
+  VAD_TRY(conv3d_prep_w3(w, Co, Ci, scratch, st));
+  return conv3d_x3_fwd(N, D, H, W, Ci, Co, x, scratch, bias, y, st);
+}
+
+extern "C" int vad_conv3d_dgrad(const float* dy, int N, int Ci, int D, int H, int W, const float* w, int Co, int sd,
+                                int sh, int sw, int path, const float* gate, float* dx, float* scratch,
+                                int64_t scratch_floats, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  Conv3dCall c;
+  VAD_TRY(conv3d_call(1, path, 1, N, Ci, D, H, W, Co, sd, sh, sw, gate != nullptr, &c));
+  VAD_CHECK(scratch && scratch_floats >= conv3d_min_scratch(1, c), "vad_conv3d_dgrad: scratch too small");
+  const int64_t wimg = up(27ll * Ci * Co);
+  if (path == 0) {
+    VAD_TRY(dense_dgrad(dy, (int)c.g.rows(), Co, w, c.g.K(), scratch, nullptr, 1.f, nullptr, st));
+    return col2im3d(scratch, c.g, dx, st);
+  }
+  if (path == 1) {  // dX = conv(dY, flipped W^T) over the layer's input grid (stride 1: the output grid)
+    VAD_TRY(conv3d_direct_prep(w, Co, Ci, scratch, scratch + wimg, st));
+    const Vol5 vy{N, Co, D, H, W};
+    return conv3d_direct_fwd(dy, ndhwc_strides(vy), vy, scratch + wimg, Ci, nullptr, dx, st);
+  }
+  VAD_TRY(conv3s2_prep(w, Co, Ci, scratch, scratch + wimg, st));
+  return conv3s2_dgrad(dy, N, Co, scratch + wimg, Ci, dx, D, H, W, st, gate);
+}
+
+extern "C" int vad_conv3d_wgrad(const float* x, int layout, const float* dy, int N, int Ci, int D, int H, int W,
+                                int Co, int sd, int sh, int sw, int path, float* dW, float* db, float* scratch,
+                                int64_t scratch_floats, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  Conv3dCall c;
+  VAD_TRY(conv3d_call(2, path, layout, N, Ci, D, H, W, Co, sd, sh, sw, false, &c));
+  VAD_CHECK(scratch && scratch_floats >= conv3d_min_scratch(2, c), "vad_conv3d_wgrad: scratch too small");
+  const Strides5 str = layout == 0 ? ncdhw_strides(c.in) : ndhwc_strides(c.in);
+  if (path == 0) {
+    VAD_CHECK(db, "vad_conv3d_wgrad: path 0 (im2col) writes db");
+    const int64_t cols = up(c.g.rows() * c.g.K());
+    VAD_TRY(im2col3d(x, str, c.g, nullptr, nullptr, 0, scratch, st));
+    return dense_wgrad(dy, (int)c.g.rows(), Co, scratch, c.g.K(), dW, db, scratch + cols, scratch_floats - cols,
+                       nullptr, st, 1024);
+  }
+  if (path == 1) return conv3d_direct_wgrad(dy, Co, x, str, c.in, dW, db, scratch, scratch_floats, st);
+  return conv3s2_wgrad(dy, Co, x, Ci, N, D, H, W, dW, scratch, scratch_floats, 1024, st, db);
+}
+
+extern "C" int vad_maxpool3d_forward(const float* y, const float* stats, int relu, int N, int C, int D, int H, int W,
+                                     int kd, int kh, int kw, float* out, void* stream) {
+  VAD_CHECK(N >= 1 && C >= 1 && D >= 1 && H >= 1 && W >= 1 && kd >= 1 && kh >= 1 && kw >= 1,
+            "vad_maxpool3d_forward: unsupported shape");
+  return maxpool3d_fwd(y, stats, relu, Vol5{N, C, D, H, W}, kd, kh, kw, out, (hipStream_t)stream);
+}
+
+extern "C" int vad_maxpool3d_backward(const float* y, const float* stats, int relu, int N, int C, int D, int H, int W,
+                                      int kd, int kh, int kw, const float* dout, float* dA, void* stream) {
+  VAD_CHECK(N >= 1 && C >= 1 && D >= 1 && H >= 1 && W >= 1 && kd >= 1 && kh >= 1 && kw >= 1,
+            "vad_maxpool3d_backward: unsupported shape");
+  return maxpool3d_bwd(y, stats, relu, Vol5{N, C, D, H, W}, kd, kh, kw, dout, dA, (hipStream_t)stream);
+}
+
+extern "C" int vad_adaptive_avgpool3d_forward(const float* x, const float* stats, int relu, int N, int C, int D, int H,
+                                              int W, int OD, int OH, int OW, float* out, void* stream) {
+  VAD_CHECK(N >= 1 && C >= 1 && D >= 1 && H >= 1 && W >= 1 && OD >= 1 && OH >= 1 && OW >= 1,
+            "vad_adaptive_avgpool3d_forward: unsupported shape");
+  return adaptive_avgpool3d_fwd(x, stats, relu, Vol5{N, C, D, H, W}, OD, OH, OW, out, (hipStream_t)stream);
+}
+
+extern "C" int vad_adaptive_avgpool3d_backward(const float* dout, int N, int C, int D, int H, int W, int OD, int OH,
+                                               int OW, const float* gate, float* dx, void* stream) {
+  VAD_CHECK(N >= 1 && C >= 1 && D >= 1 && H >= 1 && W >= 1 && OD >= 1 && OH >= 1 && OW >= 1,
+            "vad_adaptive_avgpool3d_backward: unsupported shape");
+  return adaptive_avgpool3d_bwd(dout, Vol5{N, C, D, H, W}, OD, OH, OW, dx, (hipStream_t)stream, gate);
 }

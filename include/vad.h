@@ -150,6 +150,45 @@ int vad_conv3x3_wgrad(const float* x_nhwc, const float* dy_nhwc, int NF, int Ci,
  * are bf16 (config 4), else fp32 */
 int vad_bn_bwd_apply(const void* dA, const void* y, const float* stats, int M, int C, void* dY, int bf16,
                      void* stream);
+/* nn.Conv3d(Ci, Co, 3, stride (sd, sh, sw), padding=1) of the clip-level 3-D CNNs (mc:25-102, a2:27-35, bbox:58-65) on
+ * one named kernel family; w in torch layout [Co][Ci][3][3][3]; outputs, dy and dx are NDHWC.  path:
+ *   0  im2col3d + dense_fwd / dense_dgrad + col2im3d / dense_wgrad (any stride, any channel counts);
+ *   1  conv3d_direct_*: stride 1, Ci <= 16, Co in {8, 16, 32}; its input gradient (the forward over dy with the
+ *      flipped weights) additionally needs Ci in {8, 16};
+ *   2  conv3s2_*: stride 2 on all three axes, Ci % 4 == 0, Co % 4 == 0;
+ *   3  conv3d_prep_w3 + conv3d_x3_fwd: forward only, stride 1, Ci % 16 == 0, Co % 32 == 0.
+ * A combination the path does not support is an error (no fall-back to another path).  layout: 0 = x is NCDHW (torch),
+ * 1 = NDHWC; paths 2 and 3 read NDHWC only.  scratch (caller-owned) holds the path's weight images / columns and, in
+ * what is left, its split-K slabs: vad_conv3d_scratch_floats(kind 0 forward / 1 input gradient / 2 weight gradient)
+ * is the least it needs (< 0: unsupported combination); more lets the GEMMs split K as they do inside the plans. */
+int64_t vad_conv3d_scratch_floats(int kind, int path, int N, int Ci, int D, int H, int W, int Co, int sd, int sh,
+                                  int sw);
+int vad_conv3d_forward(const float* x, int layout, int N, int Ci, int D, int H, int W, const float* w,
+                       const float* bias, int Co, int sd, int sh, int sw, int path, float* y, float* scratch,
+                       int64_t scratch_floats, void* stream);
+/* gate (nullable, path 2 only, dx's layout): dx = 0 where !(gate > 0), the fused backward of the ReLU that made gate */
+int vad_conv3d_dgrad(const float* dy, int N, int Ci, int D, int H, int W, const float* w, int Co, int sd, int sh,
+                     int sw, int path, const float* gate, float* dx, float* scratch, int64_t scratch_floats,
+                     void* stream);
+/* dW [Co][Ci][27] and db [Co] (nullable on paths 1 and 2), written, not accumulated */
+int vad_conv3d_wgrad(const float* x, int layout, const float* dy, int N, int Ci, int D, int H, int W, int Co, int sd,
+                     int sh, int sw, int path, float* dW, float* db, float* scratch, int64_t scratch_floats,
+                     void* stream);
+/* nn.MaxPool3d((kd, kh, kw)) (stride = kernel, floor mode) of act(y), y NDHWC (N, D, H, W, C) -> out NDHWC;
+ * act = relu(stats[2C + c] * y + stats[3C + c]) when stats != NULL (a BatchNorm state [mean | invstd | scale | shift],
+ * 4 C floats), else relu(y) when relu, else y.  The backward writes dA (y's dims): dout at the first maximum of each
+ * window in torch's scan order, zero elsewhere; it obeys the "maxpool3d_bwd_win" knob. */
+int vad_maxpool3d_forward(const float* y, const float* stats, int relu, int N, int C, int D, int H, int W, int kd,
+                          int kh, int kw, float* out, void* stream);
+int vad_maxpool3d_backward(const float* y, const float* stats, int relu, int N, int C, int D, int H, int W, int kd,
+                           int kh, int kw, const float* dout, float* dA, void* stream);
+/* nn.AdaptiveAvgPool3d((OD, OH, OW)) of act(x) (act as above), x NDHWC -> out [N][C][OD][OH][OW] (torch's flatten
+ * order); the backward writes dx (NDHWC) from dout in that order, zero where !(gate > 0) when gate (nullable, dx's
+ * layout) is given */
+int vad_adaptive_avgpool3d_forward(const float* x, const float* stats, int relu, int N, int C, int D, int H, int W,
+                                   int OD, int OH, int OW, float* out, void* stream);
+int vad_adaptive_avgpool3d_backward(const float* dout, int N, int C, int D, int H, int W, int OD, int OH, int OW,
+                                    const float* gate, float* dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * minicausal_vad_complete3.py — SimpleVideoAnomalyDetector (mc:25-102) + StableTrainer step (mc:249-330)

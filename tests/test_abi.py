@@ -91,3 +91,29 @@ def test_rng_contract_properties():
     assert not (rng.u24(5, 2, 4, np.arange(4), np.arange(7)) == a).all()  # the step changes the draws
     px = rng.pixels_u8(0, 0, 0, 2, 4096)
     assert px.dtype == np.uint8 and px.min() == 0 and px.max() == 255
+
+
+def test_conv3d_paths_refuse_what_they_do_not_run():
+    """vad_conv3d_* name one kernel family; a combination that family does not run is an error with a text that says
+    why (never a fall-back to another family).  The checks precede any launch, so no device is needed."""
+    from vad_amd import _native
+    L = _native.lib()
+    fwd = lambda path, Ci, Co, s, layout=1: L.vad_conv3d_forward(
+        None, layout, 1, Ci, 4, 8, 8, None, None, Co, s, s, s, path, None, None, 0, None)
+    for args, text in [((1, 8, 16, 2), b"path 1 (direct) is stride 1"),
+                       ((1, 32, 16, 1), b"needs Ci <= 16"),
+                       ((1, 8, 24, 1), b"Co in {8, 16, 32}"),
+                       ((2, 16, 32, 1), b"path 2 (conv3s2) is stride 2"),
+                       ((2, 3, 16, 2), b"needs Ci % 4 == 0"),
+                       ((2, 16, 32, 2, 0), b"reads NDHWC"),
+                       ((3, 8, 64, 1), b"needs Ci % 16 == 0"),
+                       ((4, 8, 8, 1), b"unknown path"),
+                       ((0, 8, 8, 1), b"scratch too small")]:
+        assert fwd(*args) != 0
+        assert text in L.vad_last_error(), (args, L.vad_last_error())
+    assert L.vad_conv3d_dgrad(None, 1, 32, 4, 8, 8, None, 64, 1, 1, 1, 3, None, None, None, 0, None) != 0
+    assert b"forward only" in L.vad_last_error()
+    assert L.vad_conv3d_dgrad(None, 1, 3, 4, 8, 8, None, 8, 1, 1, 1, 1, None, None, None, 0, None) != 0
+    assert b"input gradient needs Ci in {8, 16}" in L.vad_last_error()
+    assert L.vad_conv3d_scratch_floats(1, 3, 1, 32, 4, 8, 8, 64, 1, 1, 1) < 0
+    assert L.vad_conv3d_scratch_floats(0, 0, 2, 3, 5, 37, 27, 16, 1, 2, 2) >= 2 * 5 * 19 * 14 * 81

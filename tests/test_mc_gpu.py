@@ -138,8 +138,8 @@ def test_mc_nonfinite_input_skips_step():
 def test_mc_maxpool_window_backward_is_bit_identical(case):
     """MaxPool3d backward with one thread per window (knob maxpool3d_bwd_win = 1, the default: the first max found once,
     the window's gradients written together) against one thread per input element (0): the same torch first-max rule,
-    so the post-step params are bit-identical.  (Extents the windows do not divide are cleared first on the window
-    path; the reference's shapes divide evenly.)"""
+    so the post-step params are bit-identical.  (These shapes divide evenly; extents the windows do not divide, which
+    the window path clears first, are in test_ragged3d_gpu.py and test_kernels3d_gpu.py.)"""
     from vad_amd import _native as nat
     out = []
     for v in (1, 0):
