@@ -2,6 +2,7 @@
 // shared dense-layer GEMMs.  All tensors are fp32, activations NHWC, frames folded into the batch axis.
 #pragma once
 #include "common.h"
+#include "weight_images.h"
 
 namespace vad {
 
@@ -20,6 +21,7 @@ extern int g_cad_dir_affine;  // knob "cad_dir_affine": the direct classifier's 
 extern int g_cad_stem_early;
 extern int g_cad_prep_stream, g_cad_wgrad_stream, g_cad_det_gate, g_cad_last_wgrad_main, g_cad_event_sysfence,
     g_cad_dy_per_layer, g_cad_l0_slab, g_cad_stream_prio;  // knobs "cad_prep_stream", "cad_wgrad_stream" (A/B)
+extern int g_cad_opt_images;  // knob "cad_opt_images" (A/B of the plan option opt_images)
 extern int g_stem_fused;  // knob "stem_fused" (default 1)
 bool stem_fused_ok(int OW);  // conv1 output width the fused stem handles
 int stem_fused(const float* x, int NF, int H, int W, const float* w, const float* b, const float* gamma, int OH,
@@ -81,6 +83,12 @@ int conv3_prep_weights(const float* w, const Conv3Layer& L, float* wf, float* wd
 // w3 (nullable, per layer nullable): also the pre-split bf16-plane Wd image of conv3_x3_dgrad_s2
 int conv3_prep_weights_all(int n, const float* const* w, const Conv3Layer* L, float* const* wf, float* const* wd,
                            hipStream_t st, __bf16* const* w3 = nullptr);
+// the two halves of it: the table of the images under the calling thread's precision / storage mode and the current
+// knobs (which images exist and in which layout), and the relayout launch.  The cad plan keeps the table: its fused
+// optimizer writes the same images through it (weight_images.h)
+int conv3_prep_table(int n, const float* const* w, const Conv3Layer* L, float* const* wf, float* const* wd,
+                     __bf16* const* w3, PrepTab* out);
+int conv3_prep_run(const PrepTab& t, hipStream_t st);
 int conv3_fwd(const Conv3Layer& L, const float* src, const float* src_stats /*nullable: BN+ReLU on load*/,
               const float* wf, const float* bias, float* y, float* partials, int* nparts, hipStream_t st,
               int* parts_cm = nullptr);  // parts_cm: in = accepted, out = 1 if written so

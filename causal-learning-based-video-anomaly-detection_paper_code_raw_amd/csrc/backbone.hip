@@ -24,6 +24,7 @@ int g_cad_wgrad_stream = 1;  // knob "cad_wgrad_stream": backbone weight gradien
 // stride-2 one (A/B at config 2: both 1.922 -> 1.893 ms, stride-1 only 1.927 -> 1.922, profiles/r03_bnfuse_ab.json)
 int g_bn_bwd_fuse = 3;
 int g_cad_stream_prio = 1;  // knob "cad_stream_prio" (cad_plan.hip streams(); A/B profiles/r03_prio_ab.json)
+int g_cad_opt_images = 1;  // knob "cad_opt_images": the fused optimizer writes the weight images it invalidates (0: the forward relayouts every time)
 int g_cad_l0_slab = 1;  // knob "cad_l0_slab": layer 0's weight gradient on a split-K slab of its own (no wait for layer 1's)
 
 // =====================================================================================================
@@ -1153,6 +1154,7 @@ int set_tuning(const char* key, int value) {
   else if (k == "mlp_tail_rb") g_mlp_tail_rb = value;
   else if (k == "cad_last_wgrad_main") g_cad_last_wgrad_main = value;
   else if (k == "cad_l0_slab") g_cad_l0_slab = value;
+  else if (k == "cad_opt_images") g_cad_opt_images = value;
   else if (k == "cad_stream_prio") g_cad_stream_prio = value;
   else if (k == "conv_split_pipe") g_x3_pipe = value;
   else if (k == "bn_bwd_fuse") g_bn_bwd_fuse = value;
@@ -1262,63 +1264,19 @@ __global__ void conv3_prep_kernel(const float* __restrict__ w, int Ci, int Co, i
   }
 }
 
-struct PrepTab {
-  const float* w[8];
-  float* wf[8];
-  float* wd[8];
-  __bf16* w3[8];  // nullable: pre-split bf16 planes of Wd, [ci][tap][co / 16][3][16]
-  int Ci[8], Co[8], classes[8];
-  int64_t end[8];  // inclusive prefix sums of Co*Ci*9
-  int n;
-  int bf16;  // also the bf16 copies of the plain images (conv3_bf16_image: behind the fp32 image)
-};
-
+// (PrepTab and conv3_image_store, the one routine that writes a layer's images: weight_images.h)
 __global__ void conv3_prep_all_kernel(const PrepTab t) {
   const int64_t total = t.end[t.n - 1];
   for (int64_t g = blockIdx.x * 256ll + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
     int l = 0;
     while (g >= t.end[l]) ++l;
     const int64_t i = g - (l ? t.end[l - 1] : 0);
-    const int Ci = t.Ci[l], Co = t.Co[l];
-    const int tap = (int)(i % 9);
-    const int ci = (int)((i / 9) % Ci);
-    const int co = (int)(i / (9 * Ci));
-    const float v = t.w[l][i];
-    t.wf[l][((int64_t)co * 9 + tap) * Ci + ci] = v;
-    if (t.bf16) {
-      const int64_t tot = (int64_t)Co * Ci * 9;
-      reinterpret_cast<__bf16*>(t.wf[l] + tot)[((int64_t)co * 9 + tap) * Ci + ci] = (__bf16)v;
-      reinterpret_cast<__bf16*>(t.wd[l] + tot)[((int64_t)ci * 9 + tap) * Co + co] = (__bf16)v;
-    }
-    if (t.w3[l]) {  // (the split of put_planes / split3: hi, mid, lo)
-      const __bf16 h = (__bf16)v;
-      const float r = v - (float)h;
-      const __bf16 m = (__bf16)r;
-      __bf16* d = t.w3[l] + ((((int64_t)ci * 9 + tap) * (Co / 16) + co / 16) * 3) * 16 + co % 16;
-      d[0] = h;
-      d[16] = m;
-      d[32] = (__bf16)(r - (float)m);
-    }
-    if (!t.classes[l]) {
-      t.wd[l][((int64_t)ci * 9 + tap) * Co + co] = v;
-    } else {
-      const int kh = tap / 3, kw = tap % 3;
-      const int ph = (kh + 1) & 1, pw = (kw + 1) & 1;
-      const int ri = (ph == 0) ? 0 : (kh == 0 ? 0 : 1);
-      const int cj = (pw == 0) ? 0 : (kw == 0 ? 0 : 1);
-      const int nrt = ph == 0 ? 1 : 2, nct = pw == 0 ? 1 : 2;
-      int64_t off = 0;
-      for (int c = 0; c < ph * 2 + pw; ++c) {
-        const int r = (c >> 1) == 0 ? 1 : 2, q = (c & 1) == 0 ? 1 : 2;
-        off += (int64_t)r * q * Ci * Co;
-      }
-      t.wd[l][off + ((int64_t)ci * (nrt * nct) + ri * nct + cj) * Co + co] = v;
-    }
+    conv3_image_store(t, l, i, t.w[l][i]);
   }
 }
 
-int conv3_prep_weights_all(int n, const float* const* w, const Conv3Layer* L, float* const* wf, float* const* wd,
-                           hipStream_t st, __bf16* const* w3) {
+int conv3_prep_table(int n, const float* const* w, const Conv3Layer* L, float* const* wf, float* const* wd,
+                     __bf16* const* w3, PrepTab* out) {
   VAD_CHECK(n >= 1 && n <= 8, "conv3_prep_weights_all: 1..8 layers");
   PrepTab t{};
   t.n = n;
@@ -1336,10 +1294,23 @@ int conv3_prep_weights_all(int n, const float* const* w, const Conv3Layer* L, fl
     acc += (int64_t)L[l].Co * L[l].Ci * 9;
     t.end[l] = acc;
   }
+  *out = t;
+  return 0;
+}
+
+int conv3_prep_run(const PrepTab& t, hipStream_t st) {
+  const int64_t acc = t.end[t.n - 1];
   hipLaunchKernelGGL(conv3_prep_all_kernel, dim3((unsigned)std::min<int64_t>(cdiv(acc, 256), 4096)), dim3(256), 0, st,
                      t);
   VAD_LAUNCH_CHECK();
   return 0;
+}
+
+int conv3_prep_weights_all(int n, const float* const* w, const Conv3Layer* L, float* const* wf, float* const* wd,
+                           hipStream_t st, __bf16* const* w3) {
+  PrepTab t;
+  VAD_TRY(conv3_prep_table(n, w, L, wf, wd, w3, &t));
+  return conv3_prep_run(t, st);
 }
 
 int conv3_prep_weights(const float* w, const Conv3Layer& L, float* wf, float* wd, hipStream_t st) {

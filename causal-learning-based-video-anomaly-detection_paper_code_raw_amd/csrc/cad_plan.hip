@@ -3,6 +3,7 @@
 // The plan owns no device memory: PyTorch allocates the workspace and the flat parameter/grad/state buffers.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vad.h"
@@ -211,13 +212,19 @@ __global__ void opt_prepare_kernel(const float* __restrict__ partials, int np, c
   }
 }
 
-// torch.optim.AdamW single-tensor update, one 256-element chunk per block iteration (slots are 256-aligned)
+// torch.optim.AdamW single-tensor update, one 256-element chunk per block iteration (slots are 256-aligned).
+// IMG: every new value of a conv weight / a detector layer-1..4 weight also goes into the plan's derived images of it
+// (weight_image_store: the routine the relayout kernels use), so the next forward needs no relayout.  A slot that is
+// inactive this step keeps its parameters, so its images stay valid.  IMG = false compiles to the plain update.
+struct NoImages {};
+template <bool IMG>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     const int16_t* __restrict__ chunk_slot, int64_t nchunks,
                                                     const float* __restrict__ slot_info,
                                                     const float* __restrict__ clip, float grad_scale, float lr,
-                                                    float beta1, float beta2, float eps, float wd) {
+                                                    float beta1, float beta2, float eps, float wd,
+                                                    const std::conditional_t<IMG, WeightImages, NoImages> img) {
   const float coef = clip[0] * grad_scale;
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const int s = chunk_slot[c];
@@ -225,15 +232,22 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     if (slot_info[s * 4] == 0.f) continue;
     const float bc1 = slot_info[s * 4 + 1], bc2s = slot_info[s * 4 + 2];
     const int64_t i = c * 256 + threadIdx.x;
-    const float gr = g[i] * coef;
-    float pv = p[i] * (1.f - lr * wd);
-    const float mv = m[i] + (gr - m[i]) * (1.f - beta1);
-    const float vv = v[i] * beta2 + gr * gr * (1.f - beta2);
-    const float denom = sqrtf(vv) / bc2s + eps;
-    pv = pv - (lr / bc1) * mv / denom;
+    // The roundings are spelled out (no compiler contraction in this block, fmaf where a product stays unrounded): the
+    // two instantiations must agree bit for bit, and with the parameters every earlier build of this kernel produced.
+    float pv, mv, vv;
+    {
+#pragma clang fp contract(off)
+      const float gr = g[i] * coef;
+      pv = p[i] * fmaf(-lr, wd, 1.f);
+      mv = fmaf(1.f - beta1, fmaf(g[i], coef, -m[i]), m[i]);
+      vv = v[i] * beta2 + (gr * gr) * (1.f - beta2);
+      const float denom = sqrtf(vv) / bc2s + eps;
+      pv = pv - ((lr / bc1) * mv) / denom;
+    }
     p[i] = pv;
     m[i] = mv;
     v[i] = vv;
+    if constexpr (IMG) weight_image_store(img, s, i, pv);
   }
 }
 
@@ -390,6 +404,25 @@ struct CadPlanImpl {
   // dYb[b] is done" (st3)
   hipStream_t st3 = nullptr;
   hipEvent_t ev_dy[2] = {nullptr, nullptr}, ev_wg[2] = {nullptr, nullptr}, ev_wgj = nullptr, ev_prep = nullptr;
+  hipEvent_t ev_prep_det = nullptr;  // the detector's transposed layers (only the detector's forward waits for it)
+  // Weight images (weight_images.h): the conv images wf / wd / w3 (+ bf16 copies) and the detector's wt.  images_fresh:
+  // they hold the current parameters -- set by a forward that ran the relayout and by an optimizer step that wrote them
+  // (option "opt_images", default on; knob "cad_opt_images"), cleared by vad_cad_bind, by an optimizer step that did
+  // not write them and by option "images_fresh" = 0 (the caller changed the parameters itself).  img_tab: the table
+  // of the last relayout; which images exist and their layout depend on options and knobs (conv_bf16, act_bf16,
+  // conv_dgrad_s2_w3, conv_patch, ...), so a forward compares its own table with it (images_match) and relayouts when
+  // they differ.  A forward over fresh images launches no relayout and neither records nor waits on ev_prep.
+  int opt_images = 1, images_fresh = 0;
+  WeightImages img_tab{};
+  bool images_match(const PrepTab& a) const {
+    const PrepTab& b = img_tab.conv;
+    if (a.n != b.n || a.bf16 != b.bf16) return false;
+    for (int l = 0; l < a.n; ++l)
+      if (a.w[l] != b.w[l] || a.wf[l] != b.wf[l] || a.wd[l] != b.wd[l] || a.w3[l] != b.w3[l] ||
+          a.classes[l] != b.classes[l])
+        return false;
+    return true;
+  }
   // ev_layer[l]: every grad of backbone layer l (conv weight + bias, BN gamma / beta) is final -- recorded after the
   // layer's split-K reduce on the queue that ran it (layer 0: also after the stem backward), for per-layer
   // data-parallel gradient buckets (vad_cad_wait_layer_grads)
@@ -424,6 +457,7 @@ struct CadPlanImpl {
       }
       VAD_HIP(hipEventCreateWithFlags(&ev_wgj, evf));
       VAD_HIP(hipEventCreateWithFlags(&ev_prep, evf));
+      VAD_HIP(hipEventCreateWithFlags(&ev_prep_det, evf));
       for (int l = 0; l < 8; ++l) VAD_HIP(hipEventCreateWithFlags(&ev_layer[l], evf));
       VAD_HIP(hipEventCreateWithFlags(&ev_input, evf));
       VAD_HIP(hipEventCreateWithFlags(&ev_stem, evf));
@@ -459,6 +493,7 @@ struct CadPlanImpl {
     }
     if (ev_wgj) (void)hipEventDestroy(ev_wgj);
     if (ev_prep) (void)hipEventDestroy(ev_prep);
+    if (ev_prep_det) (void)hipEventDestroy(ev_prep_det);
     for (int l = 0; l < 8; ++l)
       if (ev_layer[l]) (void)hipEventDestroy(ev_layer[l]);
     if (ev_input) (void)hipEventDestroy(ev_input);
@@ -630,6 +665,26 @@ struct CadPlanImpl {
     }
     return m;
   }
+  // the optimizer's view of the images: the relayout tables and the parameter slot -> image map
+  void set_image_table(const PrepTab& pt) {
+    const CadLayout& LY = layout();
+    img_tab = WeightImages{};
+    img_tab.conv = pt;
+    img_tab.det = mlp_transpose_args();
+    for (int i = 0; i < 160; ++i) img_tab.slot_img[i] = -1;
+    for (int l = 0; l < pt.n; ++l) {
+      const Slot& s = LY.slots[LY.conv_w[l]];
+      img_tab.slot_img[LY.conv_w[l]] = (int8_t)l;
+      img_tab.off[l] = s.offset;
+      img_tab.numel[l] = s.numel;
+    }
+    for (int j = 0; j < img_tab.det.n; ++j) {  // entry j: detector layer j + 1
+      const Slot& s = LY.slots[LY.det_w[j + 1]];
+      img_tab.slot_img[LY.det_w[j + 1]] = (int8_t)(8 + j);
+      img_tab.off[8 + j] = s.offset;
+      img_tab.numel[8 + j] = s.numel;
+    }
+  }
   MlpTransposeArgs mlp_transpose_args() const {
     const CadLayout& LY = layout();
     const int dd[6] = {6144, 512, 256, 128, 64, 20};
@@ -750,17 +805,29 @@ struct CadPlanImpl {
     for (int l = 0; l < 8; ++l) act_bf16 = act_bf16 && conv3_act_bf16_ok(L[l], l > 0);
     ActStorage abf(act_bf16);
     // weight relayouts (conv images -- with bf16 storage also their bf16 copies --, the detector's transposed layers)
-    // on the side stream, beside the stem
-    VAD_TRY(fork(st));
+    // on the side stream, beside the stem: only when the images do not hold the current parameters in the layout this
+    // forward reads (in steady-state training the optimizer wrote them; in repeated eval forwards the first one did)
+    VAD_TRY(streams());
+    bool relayout = false;
     {
       hipStream_t st = g_cad_prep_stream ? st2 : st0;
       const float* w8[8];
       for (int l = 0; l < 8; ++l) w8[l] = P(LY.conv_w[l]);
       for (int l = 0; l < 8; ++l)
         w3[l] = conv3_dgrad_w3_wanted(L[l]) ? reinterpret_cast<__bf16*>(wd[l] + (int64_t)L[l].Co * L[l].Ci * 9) : nullptr;
-      TIMED("prep", conv3_prep_weights_all(8, w8, L, wf, wd, st, w3));
-      TIMED("prep", mlp_transpose(mlp_transpose_args(), st));
-      VAD_HIP(hipEventRecord(ev_prep, st));
+      PrepTab pt;
+      VAD_TRY(conv3_prep_table(8, w8, L, wf, wd, w3, &pt));
+      relayout = !images_fresh || !images_match(pt);
+      if (relayout) {
+        VAD_TRY(fork(st0));
+        images_fresh = 0;
+        set_image_table(pt);
+        TIMED("prep", conv3_prep_run(img_tab.conv, st));
+        VAD_HIP(hipEventRecord(ev_prep, st));  // (layer1.0 waits for the conv images only)
+        TIMED("prep", mlp_transpose(img_tab.det, st));
+        VAD_HIP(hipEventRecord(ev_prep_det, st));
+        images_fresh = 1;
+      }
     }
     int np = 0;
     bwd_state = 0;
@@ -798,7 +865,7 @@ struct CadPlanImpl {
       TIMED("maxpool", maxpool3s2_bnrelu(y1, stats[0], NF, H1, W1, 32, pool, HP, WP, st));
       pool_stats = nullptr;
     }
-    VAD_HIP(hipStreamWaitEvent(st, ev_prep, 0));  // layer1.0 reads the prepared weight images
+    if (relayout) VAD_HIP(hipStreamWaitEvent(st, ev_prep, 0));  // layer1.0 reads the prepared weight images
     const float* src = pool;
     const float* sst = pool_stats;
     for (int l = 0; l < 8; ++l) {
@@ -872,6 +939,7 @@ struct CadPlanImpl {
       int ns = 0;
       TIMED("det_fwd", dense_fwd_splitk(feats, NF, 6144, P(LY.det_w[0]), 512, dense_scratch2, dense_scratch_floats,
                                         &ns, st));
+      if (relayout) VAD_HIP(hipStreamWaitEvent(st, ev_prep_det, 0));  // layers 1-4 read the transposed weights
       MlpTailArgs m = mlp_args(NF, f0, dd, LY.det_w, LY.det_b, dh, dlog, S_DET_DROP2, wt);
       const DenseAct a0 = act(true, S_DET_DROP1, 0.3, f0);
       m.L[0].relu = a0.relu;
@@ -1154,9 +1222,26 @@ struct CadPlanImpl {
                        steps, b1, b2, max_norm, slot_info, clip, tn, stem_active);
     VAD_LAUNCH_CHECK();
     const int64_t nchunks = LY.param_floats / 256;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)std::min<int64_t>(nchunks, 4096)), dim3(256), 0, st, params,
-                       grads, m, v, chunk_slot, nchunks, slot_info, clip, gscale, lr, b1, b2, eps, wd_);
+    // The image-writing update overwrites buffers the backward of this step reads: wd / w3 in every conv3_dgrad (the
+    // caller's stream; the training stem's layer-0 input gradient too) and the parameters themselves in the side
+    // stream's detector / head chain (mlp_tail_bwd, dense_dgrad; wt is read by the forward's mlp_tail_fwd only).  All
+    // of them are ordered before this launch, exactly as the parameter update itself needs: the input gradients are
+    // queued on the caller's stream ahead of it; the side stream is joined on the caller's stream by the whole
+    // backward (stage -1), by stage 0, by stage 1 after a stage 2 (bwd_state == 2) and, for a stage 2 without its
+    // stage 1, by join_open_stage2 above; skip_zero_detector changes what the side stream's kernels do on device, not
+    // these joins.  The weight-gradient stream (joined through ev_wgj / ev_wg[1]) and the early stem of the next
+    // forward read no image.  The images are written only in the layout of this plan's last relayout (img_tab); a
+    // forward that wants another one relayouts.
+    const bool write_images = opt_images && g_cad_opt_images && images_fresh && img_tab.conv.n > 0;
+    const dim3 grid((unsigned)std::min<int64_t>(nchunks, 4096));
+    if (write_images)
+      hipLaunchKernelGGL(adamw_kernel<true>, grid, dim3(256), 0, st, params, grads, m, v, chunk_slot, nchunks,
+                         slot_info, clip, gscale, lr, b1, b2, eps, wd_, img_tab);
+    else
+      hipLaunchKernelGGL(adamw_kernel<false>, grid, dim3(256), 0, st, params, grads, m, v, chunk_slot, nchunks,
+                         slot_info, clip, gscale, lr, b1, b2, eps, wd_, NoImages{});
     VAD_LAUNCH_CHECK();
+    images_fresh = write_images ? 1 : 0;
     if (pw) {
       VAD_HIP(hipEventRecord(pb, st));
       prof.recs.push_back({"optimizer", pa, pb});
@@ -1277,6 +1362,8 @@ int vad_cad_bind(vad_cad_plan* plan, void* workspace, float* params, float* grad
   ws.dry = false;
   c.carve(ws);
   c.bound = 1;
+  c.images_fresh = 0;
+  c.img_tab = WeightImages{};
   c.params = params; c.grads = grads; c.bufs = bufs; c.nbt = nbt;
   c.m = exp_avg; c.v = exp_avg_sq; c.steps = steps;
   VAD_HIP(hipMemcpy(c.chunk_slot, plan->chunk_host.data(), plan->chunk_host.size() * sizeof(int16_t),
@@ -1422,9 +1509,18 @@ int vad_cad_debug_buffer(vad_cad_plan* plan, const char* name, int idx, void** p
     *ptr = c.gh[idx];
     *nfloats = (int64_t)c.B * w[idx];
   }
+  // the weight images, whole buffers (wf: fp32 image | bf16 copy; wd: fp32 image | bf16 copy or the three bf16 planes)
+  else if (n == "wf" && idx >= 0 && idx < 8) { *ptr = c.wf[idx]; *nfloats = (int64_t)c.L[idx].Co * c.L[idx].Ci * 9 * 3 / 2; }
+  else if (n == "wd" && idx >= 0 && idx < 8) { *ptr = c.wd[idx]; *nfloats = (int64_t)c.L[idx].Co * c.L[idx].Ci * 9 * 5 / 2; }
+  else if (n == "wt" && idx >= 1 && idx < 5) {
+    const int dd[5] = {512, 256, 128, 64, 20};
+    *ptr = c.wt[idx];
+    *nfloats = (int64_t)dd[idx - 1] * dd[idx];
+  }
+  else if (n == "images_fresh") { *ptr = nullptr; *nfloats = c.images_fresh; }
   else if (n == "bn_sync") { *ptr = c.bnsync; *nfloats = 2 * 2 * 256; }  // double [2*256]: 1024 float words
   else { vad::set_error("vad_cad_debug_buffer: unknown buffer " + n); return 1; }
-  VAD_CHECK(*ptr != nullptr || n == "act_bf16", "vad_cad_debug_buffer: " + n + " is not carved under this plan's options");
+  VAD_CHECK(*ptr != nullptr || n == "act_bf16" || n == "images_fresh", "vad_cad_debug_buffer: " + n + " is not carved under this plan's options");
   return 0;
 }
 
@@ -1443,6 +1539,9 @@ int vad_cad_set_option(vad_cad_plan* plan, const char* key, int64_t value) {
   else if (std::string(key) == "dy_per_layer") plan->impl.dy_per_layer = value ? 1 : 0;
   else if (std::string(key) == "act_bf16") plan->impl.act_bf16_opt = value ? 1 : 0;
   else if (std::string(key) == "input_armed" && value == 0) plan->impl.input_armed = 0;  // (arming: vad_cad_input_ready)
+  else if (std::string(key) == "opt_images") plan->impl.opt_images = value ? 1 : 0;
+  // (0: the parameters were changed by someone other than this plan's optimizer; setting it is not offered)
+  else if (std::string(key) == "images_fresh" && value == 0) plan->impl.images_fresh = 0;
   else { vad::set_error("vad_cad_set_option: unknown key"); return 1; }
   return 0;
 }

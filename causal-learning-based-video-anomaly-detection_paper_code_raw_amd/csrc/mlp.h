@@ -1,6 +1,7 @@
 // Fused MLP chains (detector_net / direct_classifier) and the generic row-reduction weight gradient.
 #pragma once
 #include "common.h"
+#include "weight_images.h"
 
 namespace vad {
 
@@ -29,12 +30,7 @@ struct MlpTailArgs {
   int nsplit;
 };
 
-struct MlpTransposeArgs {
-  int n;
-  const float* W[8];
-  float* WT[8];
-  int K[8], N[8];
-};
+// (MlpTransposeArgs and the store both writers of WT use: weight_images.h)
 int mlp_transpose(const MlpTransposeArgs& a, hipStream_t st);
 
 // input-gradient chain: d[i-1] = (d_i W_i) * (h[i-1] > 0 ? gscale[i-1] : 0), d_4 = dout

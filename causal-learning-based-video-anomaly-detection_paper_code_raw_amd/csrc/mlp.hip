@@ -127,7 +127,8 @@ __global__ __launch_bounds__(NTH) void mlp_tail_fwd_kernel(const MlpTailArgs a) 
   }
 }
 
-// WT[k][n] = W[n][k] for up to 8 matrices (the detector's layer-1..4 weights), once per step: 32x32 tiles through
+// WT[k][n] = W[n][k] for up to 8 matrices (the detector's layer-1..4 weights), when the parameters changed behind the
+// optimizer's back (the fused optimizer keeps WT current itself): 32x32 tiles through
 // LDS so both the read of W rows and the write of WT rows are coalesced.
 __global__ __launch_bounds__(256) void mlp_transpose_kernel(const MlpTransposeArgs a) {
   __shared__ float tile[32][33];
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(256) void mlp_transpose_kernel(const MlpTransposeAr
 #pragma unroll
   for (int j = 0; j < 32; j += 8) {
     const int k = k0 + ty + j, n = n0 + tx;
-    if (k < K && n < N) a.WT[m][(int64_t)k * N + n] = tile[tx][ty + j];
+    if (k < K && n < N) mlp_wt_store(a, m, n, k, tile[tx][ty + j]);
   }
 }
 

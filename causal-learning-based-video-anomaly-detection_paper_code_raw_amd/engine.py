@@ -42,6 +42,9 @@ class _Plan:
                                  e.nbt.data_ptr(), nat.ptr(e.exp_avg), nat.ptr(e.exp_avg_sq), nat.ptr(e.steps)))
         self._sync_cb = None
         self.apply_bn_sync(engine)
+        # CadEngine._weights_version() at which this plan's weight images were last known to hold the parameters
+        # (None: not known, the next forward relayouts)
+        self.img_ver = None
 
     def apply_bn_sync(self, engine):
         """Install (or clear) the SyncBatchNorm callback: an all-reduce of the plan's [2C] double sums buffer over
@@ -133,6 +136,12 @@ class CadEngine:
         # (the stem's Parameter objects, for the per-call requires_grad check: building the named-parameter dict
         # costs ~0.3 ms of host time, twice per step, on the step's critical path where the GPU runs short kernels)
         self._stem_params = [p for k, p in named if k in self.STEM]
+        # the parameters the plans keep derived images of (the 8 conv weights: relayouts; detector layers 1-4:
+        # transposes), for the per-forward check that nobody but the fused optimizer wrote them
+        self._image_params = [p for k, p in named if (k.startswith("backbone.layer") and p.dim() == 4) or (
+            k.startswith("detector.detector_net.") and k.endswith(".weight") and not k.endswith(".0.weight"))]
+        if len(self._image_params) != 12:
+            raise RuntimeError("unexpected number of conv / detector weights with derived images")
         self.exp_avg = self.exp_avg_sq = self.steps = None
         self.bn_sync = None  # (process_group, world) in SyncBatchNorm mode
         self._compute_dtype = torch.float32
@@ -190,6 +199,22 @@ class CadEngine:
             pl = self.plans[key] = _Plan(self, B, T, H, W)
         return pl
 
+    def _weights_version(self) -> int:
+        """Moves whenever torch writes a parameter that has derived weight images: through the module's Parameters
+        (load_state_dict, a torch optimizer, in-place ops: each is a view with a version counter of its own) or
+        through the flat buffer (dist.broadcast(eng.params)).  The fused optimizer does not move it: it keeps the
+        images of the plan it runs on current itself."""
+        v = self.params._version
+        for p in self._image_params:
+            v += p._version
+        return v
+
+    def _check_images(self, pl):
+        ver = self._weights_version()
+        if pl.img_ver != ver:
+            nat.check(nat.lib().vad_cad_set_option(pl.h, b"images_fresh", 0))
+            pl.img_ver = ver
+
     def grad_view(self, i):
         off = self.slot_offset[i]
         return self.grads[off:off + self.slot_numel[i]]
@@ -211,6 +236,7 @@ class CadEngine:
         pl = self.plan(B, T, H, W)
         # (before the forward: a training stem needs conv1's activation stored, a frozen one is recomputed in place)
         self._set_stem_grad(pl)
+        self._check_images(pl)
         armed, self._armed = getattr(self, "_armed", None), None
         if armed is not None and armed is not pl:  # (armed for another plan: that arm must not outlive this call)
             nat.check(nat.lib().vad_cad_set_option(armed.h, b"input_armed", 0))
@@ -352,6 +378,9 @@ class CadEngine:
                        total_norm=None):
         self.init_optimizer_state()
         pl = self._last[0]
+        for q in self.plans.values():  # (the other plans share the parameters, not the images the step rewrites)
+            if q is not pl:
+                q.img_ver = None
         nat.check(nat.lib().vad_cad_optimizer_step(pl.h, lr, betas[0], betas[1], eps, weight_decay, max_norm,
                                                    grad_scale, nat.ptr(total_norm), nat.stream_of(self.device)))
 

@@ -351,7 +351,12 @@ int vad_resize_u8(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int 
  * (BASELINE config 4's bf16 compute; BN, pooling, heads, losses and the optimizer stay fp32).  Default 0: fp32
  * numerics (split-bf16 products).  "stem_grad" (0/1): backbone.conv1 / bn1 train (the module without
  * apply_memory_efficient_training, cad:592-598); set before the forward.  "wgrad_stream" (0/1, default 1): the
- * backbone's weight gradients run on a plan-owned stream beside the input gradients (results identical). */
+ * backbone's weight gradients run on a plan-owned stream beside the input gradients (results identical).
+ * "opt_images" (0/1, default 1): vad_cad_optimizer_step also writes every new conv weight / detector layer-1..4
+ * weight into the plan's derived images of it (relayouts, transposes), so the next forward runs no relayout; results
+ * identical.  "images_fresh" (only 0): the caller changed the parameters itself (any write other than this plan's
+ * vad_cad_optimizer_step -- another plan's step on the same buffer included): the next forward relayouts.  A plan
+ * cannot see such writes; without this call it would compute with the images of the old parameters. */
 int vad_cad_set_option(vad_cad_plan* plan, const char* key, int64_t value);
 /* Kernel family of backbone 3x3 conv `layer` (0..7) for kind 0 forward / 1 input gradient / 2 weight gradient:
  * 6 = split-bf16 (fp32 numerics, six bf16 MFMA products per K step), 1 = bf16 operands, 0 = f32 MFMA; -1 on error.
@@ -360,7 +365,8 @@ int vad_cad_conv_path(vad_cad_plan* plan, int layer, int kind);
 
 /* ------------------------------------------------------------------------------------------
  * Debug introspection (tests only): internal plan buffers, partial backward, device->host copy
- * names: y1, pool, y[0..7], stats[0..8], feats, pooled, dA, dY, d_pooled, d_feat_det, det_logits
+ * names: y1, pool, y[0..7], stats[0..8], feats, pooled, dA, dY, d_pooled, d_feat_det, det_logits, the weight
+ * images wf[0..7], wd[0..7] (whole buffers: fp32 image | bf16 copy or planes), wt[1..4]; images_fresh (value in nfloats)
  * ------------------------------------------------------------------------------------------ */
 int vad_cad_debug_buffer(vad_cad_plan* plan, const char* name, int idx, void** ptr, int64_t* nfloats);
 int vad_cad_set_debug(vad_cad_plan* plan, const char* key, int64_t value);  /* "stop_layer" */
