@@ -166,8 +166,8 @@ class CadTrainer:
             lh = self._loss_host
         kw = {"loss_host": lh} if lh is not None else {}
         o = eng.forward(videos, True, self.seed, self.step_idx, self.rank * B, labels, want_outputs=want_outputs, **kw)
-        # (the forward's per-rank "detector has a grad" flag; an engine without it: the grad buffer's flag after the
-        # backward, see _head_bucket_start)
+        # (the forward's per-rank "detector has a grad" flag; a forward that returns no "flags" (want_outputs=False on
+        # the HIP engine): the grad buffer's flag float, which the forward's tail kernel writes, see _head_bucket_start)
         self._det_flag = o["flags"][:1] if self.skip_zero_detector and "flags" in o else None
         if lh is not None:
             self._loss_ev.record(cur)
@@ -205,11 +205,14 @@ class CadTrainer:
           1. detector + causal head + direct classifier + the has-grad flags, summed on a side stream while the
              backbone backward runs on the compute stream (which waits only for the detector's input gradient).  The
              detector part (13.3 MB) is identically zero on every rank when no box is in range (every frame took the
-             fallback box, cad:221-226) -- it is summed anyway: skipping it would need the flag on the host, i.e. a
-             host wait on the device every step, while its all-reduce runs beside the ~1 ms backbone backward;
+             fallback box, cad:221-226) -- by default it is summed anyway: skipping it needs the flag on the host, i.e.
+             a host wait for the forward every step, while its all-reduce runs beside the ~1 ms backbone backward.
+             With skip_zero_detector the flags are summed first and read on the host (_head_bucket_start: .item()
+             waits for the forward, whose tail kernel writes the flag), and a zero sum leaves the detector's range out;
           2. the backbone in four buckets (self.bb_buckets), each issued behind the plan's event for the last of its
              layers to finish (vad_cad_wait_layer_grads), so layer 7's all-reduce runs beside layers 6-0's backward.
-        The optimizer waits for all of them; the host never waits for the device.  Each element is summed over the
+        The optimizer waits for all of them; the host waits for the device only with skip_zero_detector (for the
+        forward, above).  Each element is summed over the
         same ranks as one all_reduce of the whole buffer, so results are identical to it."""
         eng = self.eng
         main = torch.cuda.current_stream(eng.device)
@@ -239,7 +242,7 @@ class CadTrainer:
         if not self.skip_zero_detector:
             return self.det_range[0]
         src = self._det_flag
-        if src is None:  # (engines whose forward reports no flags: the grad buffer's, final after the backward)
+        if src is None:  # (no flags from the forward: the grad buffer's flag float, written by the forward's tail)
             src = self.eng.grads[self.eng.param_floats:self.eng.param_floats + 1]
         f = src.detach().clone().float()
         self._reduce(f)

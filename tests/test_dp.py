@@ -41,7 +41,7 @@ def _worker(rank, world, port, use_gpu, out_path, frozen=False, skip_det=False):
         x, y = batches[rank]
         if use_gpu:
             m = m.cuda()
-            tr = CadTrainer(m, lr=3e-4, seed=0)
+            tr = CadTrainer(m, lr=3e-4, seed=0, skip_zero_detector=skip_det)
             x, y = x.cuda(), y.cuda()
         else:
             tr = CadTrainer(m, lr=3e-4, seed=0, engine=OracleEngine(m), skip_zero_detector=skip_det)
@@ -123,15 +123,25 @@ def test_dp_protocol_cpu_gloo(skip_det, tmp_path):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("frozen", [False, True], ids=["stem-trains", "stem-frozen"])
-def test_dp_hip_engine_gloo_two_ranks(frozen, tmp_path):
+@pytest.mark.parametrize("skip_det", [False, True], ids=["sum-detector", "skip-zero-detector"])
+def test_dp_hip_engine_gloo_two_ranks(skip_det, frozen, tmp_path):
     """Two gloo ranks on cuda:0 with the bucketed, overlapped all-reduce: params, BN buffers and the summed grads of
     the last step equal the single-process emulation (each rank's backward, then ONE sum of the whole grad buffer)
     bit for bit.  stem-frozen is the trainer default (apply_memory_efficient_training): layer 0's weight gradient
     runs on the caller's stream while layers 1-3's may still run on the weight-gradient stream, and the layers 0-3
-    bucket must wait for both."""
+    bucket must wait for both.  skip-zero-detector: at the reference init every frame takes the fallback box, so the
+    summed has-grad flag is 0, the detector's range stays off the wire and the optimizer's "detector group inactive"
+    path runs behind the overlapped all-reduce -- with the same bits as the sum-detector run (both equal the
+    emulation)."""
     import contextlib
     import io
-    got = _run(True, tmp_path, frozen)
+    got = _run(True, tmp_path, frozen, skip_det)
+    lo, hi = got["det_range"]
+    if skip_det:
+        assert got["det_flag_sum"] == 0.0
+        assert got["allreduce_floats"] == got["grads"].numel() + 1 - (hi - lo)  # the flag on, the detector off
+    else:
+        assert got["allreduce_floats"] == got["grads"].numel()
     from vad_amd.cad import CausalAnomalyDetector
     from vad_amd.train import apply_memory_efficient_training
     torch.manual_seed(0)
