@@ -76,6 +76,14 @@ _SIGS = {
     "vad_maxpool3d_backward": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vad_adaptive_avgpool3d_forward": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vad_adaptive_avgpool3d_backward": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    # dense layers and the fused MLP chain (kernel unit tests; per-layer arguments are host ctypes arrays)
+    "vad_dense_forward_ex": (_I, [_P, _I, _I, _P, _P, _I, _P, _I, ctypes.c_double, _U64, _U32, _U64, _I64, _I, _P, _I64,
+                                  _P]),
+    "vad_dense_dgrad": (_I, [_P, _I, _I, _P, _I, _P, _P, _F, _I, _P, _P, _I64, _P]),
+    "vad_dense_wgrad": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _I64, _I, _P]),
+    "vad_mlp_tail_forward": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _U64, _U64, _I64, _I, _P, _P, _I64, _P]),
+    "vad_mlp_tail_backward": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vad_rows_wgrad": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     # minicausal (config 1)
     "vad_mc_create": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "vad_mc_destroy": (None, [_P]),

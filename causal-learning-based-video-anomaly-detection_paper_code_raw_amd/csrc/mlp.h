@@ -48,6 +48,8 @@ struct MlpTailBwdArgs {
 extern int g_mlp_tail_wide;  // knob "mlp_tail_wide"
 extern int g_mlp_tail_rb;    // knob "mlp_tail_rb"
 int mlp_tail_fwd(const MlpTailArgs& a, hipStream_t st);
+// its host checks alone (layer shapes, rows per block): for a caller that queues work of its own in front of it
+int mlp_tail_fwd_check(const MlpTailArgs& a);
 // Direct classifier (cad:525-538) with its loss-mode backward precomputed as an affine function of the causal score
 // c (cad:655-676): with fin = 0.6 c + 0.4 p1 the upstream gradient of the logits is d_l[b] = A[b] + c[b] beta[b], and
 // the classifier's input-gradient chain is linear in d_l, so it runs on the 2B stacked rows [A; beta] while the causal

@@ -211,6 +211,10 @@ __global__ __launch_bounds__(256) void mlp_tail_bwd_kernel(const MlpTailBwdArgs 
         dout[r][k] = v;
       }
     }
+    // the next layer reads its input in 4-wide batches: zero the columns K .. K4 - 1 it reads past this layer's K
+    // (their weight is 0, but 0 * stale LDS is NaN when the stale word is NaN or Inf); nothing to do when K % 4 == 0
+    if (const int pad = -K & 3)
+      for (int idx = tid; idx < RB * pad; idx += 256) dout[idx / pad][K + idx % pad] = 0.f;
     __syncthreads();
   }
 }
@@ -563,13 +567,20 @@ int g_mlp_tail_rb = 0;  // knob "mlp_tail_rb": rows per block of the detector's 
 int g_mlp_tail_wide = 1;  // knob "mlp_tail_wide": 1024-thread blocks for the detector's layers 1-4 (4 x the K-slices
                           // and split-K loads in flight of 256 threads; profiles/r03_mlp_tail_sweep.txt)
 
-int mlp_tail_fwd(const MlpTailArgs& a, hipStream_t st) {
+int mlp_tail_fwd_check(const MlpTailArgs& a) {
   for (int i = 1; i < 5; ++i)
     VAD_CHECK(a.L[i].N <= MLP_MAXW && a.L[i].N % 4 == 0 && a.L[i].N / 4 <= 256 && a.L[i].K <= MLP_MAXW &&
-                  a.L[i].K % 8 == 0 && a.WT[i],
+                  a.L[i].K % 8 == 0,
               "mlp_tail_fwd: layer shape");
   const int rb = g_mlp_tail_rb ? g_mlp_tail_rb : mlp_rb(a.M);
   VAD_CHECK(rb == 2 || rb == 4 || rb == 8, "mlp_tail_fwd: rows per block 2, 4 or 8");
+  return 0;
+}
+
+int mlp_tail_fwd(const MlpTailArgs& a, hipStream_t st) {
+  VAD_TRY(mlp_tail_fwd_check(a));
+  for (int i = 1; i < 5; ++i) VAD_CHECK(a.WT[i], "mlp_tail_fwd: layer shape");
+  const int rb = g_mlp_tail_rb ? g_mlp_tail_rb : mlp_rb(a.M);
   if (rb == 2 && g_mlp_tail_wide)
     VAD_KLAUNCH((mlp_tail_fwd_kernel<2, 1024>), dim3((unsigned)cdiv(a.M, 2)), dim3(1024), 0, st, a);
   else if (rb == 2)

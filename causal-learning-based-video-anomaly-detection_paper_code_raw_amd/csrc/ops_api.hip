@@ -1,8 +1,9 @@
-// Stand-alone entry points for single building blocks (dense layer, 3x3 conv, the 3-D clip blocks) used by the kernel
-// unit tests.
+// Stand-alone entry points for single building blocks (dense layers, the fused MLP chain, 3x3 conv, the 3-D clip
+// blocks) used by the kernel unit tests.
 #include "../../include/vad.h"
 #include "backbone.h"
 #include "conv3d.h"
+#include "mlp.h"
 
 using namespace vad;
 
@@ -222,4 +223,138 @@ extern "C" int vad_adaptive_avgpool3d_backward(const float* dout, int N, int C, 
   VAD_CHECK(N >= 1 && C >= 1 && D >= 1 && H >= 1 && W >= 1 && OD >= 1 && OH >= 1 && OW >= 1,
             "vad_adaptive_avgpool3d_backward: unsupported shape");
   return adaptive_avgpool3d_bwd(dout, Vol5{N, C, D, H, W}, OD, OH, OW, dx, (hipStream_t)stream, gate);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The dense-layer launchers and the fused MLP chain alone (backbone.h, mlp.h), with every argument the plans give
+// them.  Thin wrappers: they fill the argument structs as the cad plan does and launch nothing of their own.
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the cad plan's act(): dropout after the activation, keyed by (seed, stream_id, step) and the global row
+DenseAct dense_act(int relu, double p, uint64_t seed, uint32_t stream_id, uint64_t step, int64_t row0) {
+  DenseAct a;
+  a.relu = relu ? 1 : 0;
+  if (p > 0) {
+    a.drop = 1;
+    a.h1 = rng_h1(seed, stream_id, step);
+    a.thr = drop_threshold(p);
+    a.dscale = 1.0f / (float)(1.0 - p);
+    a.row0 = row0;
+  }
+  return a;
+}
+
+}  // namespace
+
+extern "C" int vad_dense_forward_ex(const float* X, int M, int K, const float* W, const float* b, int N, float* Y,
+                                    int relu, double drop_p, uint64_t seed, uint32_t stream_id, uint64_t step,
+                                    int64_t row0, int max_splits, float* scratch, int64_t scratch_floats,
+                                    void* stream) {
+  VAD_CHECK(M >= 1 && K >= 1 && N >= 1 && drop_p >= 0 && drop_p < 1 && scratch_floats >= 0,
+            "vad_dense_forward_ex: unsupported shape");
+  return dense_fwd(X, M, K, W, b, N, Y, dense_act(relu, drop_p, seed, stream_id, step, row0), scratch, scratch_floats,
+                   (hipStream_t)stream, max_splits);
+}
+
+extern "C" int vad_dense_dgrad(const float* dY, int M, int N, const float* W, int K, float* dX, const float* gate,
+                               float gscale, int gate_rows, const int* skip, float* scratch, int64_t scratch_floats,
+                               void* stream) {
+  VAD_CHECK(M >= 1 && K >= 1 && N >= 1 && gate_rows >= 0 && scratch_floats >= 0, "vad_dense_dgrad: unsupported shape");
+  return dense_dgrad(dY, M, N, W, K, dX, gate, gscale, skip, (hipStream_t)stream, gate_rows, scratch, scratch_floats);
+}
+
+extern "C" int vad_dense_wgrad(const float* dY, int M, int N, const float* X, int K, float* dW, float* db,
+                               const int* skip, float* scratch, int64_t scratch_floats, int target_blocks,
+                               void* stream) {
+  VAD_CHECK(M >= 1 && K >= 1 && N >= 1 && target_blocks >= 1 && scratch_floats >= 0,
+            "vad_dense_wgrad: unsupported shape");
+  return dense_wgrad(dY, M, N, X, K, dW, db, scratch, scratch_floats, skip, (hipStream_t)stream, target_blocks);
+}
+
+extern "C" int vad_mlp_tail_forward(const float* X, int M, int K0, const int* N, const float* const* W,
+                                    const float* const* b, const int* relu, const double* drop_p,
+                                    const uint32_t* stream_id, uint64_t seed, uint64_t step, int64_t row0, int mode,
+                                    float* const* out, float* scratch, int64_t scratch_floats, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  VAD_CHECK(M >= 1 && K0 >= 1 && (mode == 0 || mode == 1) && scratch_floats >= 0,
+            "vad_mlp_tail_forward: unsupported shape");
+  MlpTailArgs m{};
+  m.M = M;
+  m.row0 = row0;
+  DenseAct a0;
+  for (int i = 0; i < 5; ++i) {
+    VAD_CHECK(N[i] >= 1 && drop_p[i] >= 0 && drop_p[i] < 1, "vad_mlp_tail_forward: unsupported shape");
+    const DenseAct a = dense_act(relu[i], drop_p[i], seed, stream_id[i], step, row0);
+    if (i == 0) a0 = a;
+    MlpLayer& L = m.L[i];
+    L.W = W[i];
+    L.b = b[i];
+    L.out = out[i];
+    L.K = i == 0 ? K0 : N[i - 1];
+    L.N = N[i];
+    L.relu = a.relu;
+    L.drop = a.drop;
+    L.h1 = a.h1;
+    L.thr = a.thr;
+    L.dscale = a.dscale;
+  }
+  VAD_TRY(mlp_tail_fwd_check(m));  // before anything is queued: a refused chain launches nothing
+  // the transposed weights of layers 1-4 first, the split-K slabs in what is left
+  MlpTransposeArgs t{};
+  int64_t off = 0;
+  for (int i = 1; i < 5; ++i, ++t.n) {
+    m.WT[i] = scratch + off;
+    t.W[t.n] = W[i];
+    t.WT[t.n] = scratch + off;
+    t.K[t.n] = m.L[i].K;
+    t.N[t.n] = m.L[i].N;
+    off += up((int64_t)m.L[i].K * m.L[i].N);
+  }
+  VAD_CHECK(scratch && off <= scratch_floats, "vad_mlp_tail_forward: scratch too small");
+  VAD_TRY(mlp_transpose(t, st));
+  if (mode == 0) {
+    VAD_TRY(dense_fwd(X, M, K0, W[0], b[0], N[0], out[0], a0, scratch + off, scratch_floats - off, st));
+  } else {
+    int ns = 0;
+    VAD_TRY(dense_fwd_splitk(X, M, K0, W[0], N[0], scratch + off, scratch_floats - off, &ns, st));
+    m.parts = scratch + off;
+    m.nsplit = ns;
+  }
+  return mlp_tail_fwd(m, st);
+}
+
+extern "C" int vad_mlp_tail_backward(int M, const float* dout, const float* const* W, const int* K, const int* N,
+                                     const float* const* h, const float* gscale, float* const* d, const int* skip,
+                                     void* stream) {
+  VAD_CHECK(M >= 1, "vad_mlp_tail_backward: unsupported shape");
+  MlpTailBwdArgs a{};
+  a.M = M;
+  a.dout = dout;
+  for (int i = 0; i < 5; ++i) {
+    a.W[i] = W[i];
+    a.K[i] = K[i];
+    a.N[i] = N[i];
+    VAD_CHECK(K[i] >= 1 && N[i] >= 1 && (i == 0 || K[i] == N[i - 1]), "vad_mlp_tail_backward: unsupported shape");
+  }
+  for (int i = 0; i < 4; ++i) {
+    a.h[i] = h[i];
+    a.gscale[i] = gscale[i];
+    a.d[i] = d[i];
+  }
+  a.skip = skip;
+  return mlp_tail_bwd(a, (hipStream_t)stream);
+}
+
+extern "C" int vad_rows_wgrad(int R, int nseg, float* const* dW, float* const* db, const float* const* A,
+                              const float* const* X, const int* O, const int* I, const int* skip, void* stream) {
+  RowsWgradArgs a{};
+  a.R = R;
+  a.nseg = nseg;  // (a count outside 1 .. ROWS_WGRAD_MAXSEG is the launcher's to refuse)
+  for (int s = 0; s < nseg && s < ROWS_WGRAD_MAXSEG; ++s) {
+    VAD_CHECK(R >= 1 && O[s] >= 1 && I[s] >= 1, "vad_rows_wgrad: unsupported shape");
+    a.seg[s] = RowsWgradSeg{dW[s], db ? db[s] : nullptr, A[s], X[s], O[s], I[s]};
+  }
+  a.skip = skip;
+  return rows_wgrad(a, (hipStream_t)stream);
 }

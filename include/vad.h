@@ -189,6 +189,40 @@ int vad_adaptive_avgpool3d_forward(const float* x, const float* stats, int relu,
                                    int OD, int OH, int OW, float* out, void* stream);
 int vad_adaptive_avgpool3d_backward(const float* dout, int N, int C, int D, int H, int W, int OD, int OH, int OW,
                                     const float* gate, float* dx, void* stream);
+/* The dense-layer launchers and the fused MLP chain alone, with every argument the plans give them (kernel unit
+ * tests).  Arrays named "host" are host arrays (of device pointers where they hold pointers); `skip` is a nullable
+ * DEVICE flag: 0 -> every kernel of the call returns without writing.
+ * vad_dense_forward with dropout after the activation when drop_p > 0: keep iff u24(seed, stream_id, step, row0 + row,
+ * col) >= floor(drop_p 2^24), kept values times 1 / (1 - drop_p) (oracle/rng.py dropout_keep / dropout_scale);
+ * max_splits > 0 caps the split-K count, scratch_floats bounds it (0: no split) */
+int vad_dense_forward_ex(const float* X, int M, int K, const float* W, const float* b, int N, float* Y, int relu,
+                         double drop_p, uint64_t seed, uint32_t stream_id, uint64_t step, int64_t row0, int max_splits,
+                         float* scratch, int64_t scratch_floats, void* stream);
+/* dX[M,K] = (dY[M,N] W[N,K]) * (gate > 0 ? gscale : 0) (gate nullable, dX's layout; gate_rows > 0: row m is gated by
+ * gate row m % gate_rows); scratch (nullable): split-K slabs */
+int vad_dense_dgrad(const float* dY, int M, int N, const float* W, int K, float* dX, const float* gate, float gscale,
+                    int gate_rows, const int* skip, float* scratch, int64_t scratch_floats, void* stream);
+/* dW[N,K] = dY[M,N]^T X[M,K], db[N] (nullable) = colsum(dY); written, not accumulated.  scratch >= N (K + 1) floats
+ * unless M <= 16 and K % 4 == 0; target_blocks: split-K blocks to aim for (the plans give 256 or 1024) */
+int vad_dense_wgrad(const float* dY, int M, int N, const float* X, int K, float* dW, float* db, const int* skip,
+                    float* scratch, int64_t scratch_floats, int target_blocks, void* stream);
+/* A 5-layer chain out[i] = drop_i(act_i(out[i-1] W[i]^T + b[i])), out[-1] = X[M,K0]; host N[5], W[5], b[5], relu[5],
+ * drop_p[5] (0: none), stream_id[5], out[5]; layers 1-4 need N[i] % 4 == 0, N[i-1] % 8 == 0 and widths <= 512.
+ * mode 0: layer 0 by the dense forward, layers 1-4 by the fused tail; mode 1: layer 0 as split-K partial sums that the
+ * tail finishes.  scratch: the four transposed weights (256-byte aligned each), then the split-K slabs
+ * (mode 1: at least M N[0] floats) */
+int vad_mlp_tail_forward(const float* X, int M, int K0, const int* N, const float* const* W, const float* const* b,
+                         const int* relu, const double* drop_p, const uint32_t* stream_id, uint64_t seed,
+                         uint64_t step, int64_t row0, int mode, float* const* out, float* scratch,
+                         int64_t scratch_floats, void* stream);
+/* the chain's input gradients d[i-1] = (d[i] W[i]) * (h[i-1] > 0 ? gscale[i-1] : 0), i = 4..1, d[4] = dout[M,N[4]];
+ * host W[5], K[5], N[5] (W[i] is [N[i]][K[i]], K[i] = N[i-1]; entry 0 is not read), h[4], gscale[4], d[4] */
+int vad_mlp_tail_backward(int M, const float* dout, const float* const* W, const int* K, const int* N,
+                          const float* const* h, const float* gscale, float* const* d, const int* skip, void* stream);
+/* dW[s][O,I] = A[s][R,O]^T X[s][R,I], db[s][O] (nullable) = colsum(A[s]) for nseg <= 6 layers in one launch, written;
+ * host dW, db, A, X, O, I [nseg] */
+int vad_rows_wgrad(int R, int nseg, float* const* dW, float* const* db, const float* const* A, const float* const* X,
+                   const int* O, const int* I, const int* skip, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * minicausal_vad_complete3.py — SimpleVideoAnomalyDetector (mc:25-102) + StableTrainer step (mc:249-330)

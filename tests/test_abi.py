@@ -117,3 +117,41 @@ def test_conv3d_paths_refuse_what_they_do_not_run():
     assert b"input gradient needs Ci in {8, 16}" in L.vad_last_error()
     assert L.vad_conv3d_scratch_floats(1, 3, 1, 32, 4, 8, 8, 64, 1, 1, 1) < 0
     assert L.vad_conv3d_scratch_floats(0, 0, 2, 3, 5, 37, 27, 16, 1, 2, 2) >= 2 * 5 * 19 * 14 * 81
+
+
+def test_dense_and_mlp_entry_points_refuse_before_any_launch():
+    """The stand-alone dense / MLP-chain entry points hand their arguments to the launchers, whose host checks precede
+    any launch: a refused call returns non-zero with the launcher's text and needs no device."""
+    from vad_amd import _native
+    L = _native.lib()
+    ia = lambda *v: (ctypes.c_int * len(v))(*v)
+    none = (ctypes.c_void_p * 8)()
+    for nseg in (0, 7):
+        assert L.vad_rows_wgrad(4, nseg, none, none, none, none, ia(*[8] * 8), ia(*[8] * 8), None, None) != 0
+        assert b"rows_wgrad: bad segment count" in L.vad_last_error()
+    assert L.vad_dense_wgrad(None, 17, 5, None, 7, None, None, None, None, 5 * 8 - 1, 256, None) != 0
+    assert b"dense_wgrad: scratch too small" in L.vad_last_error()
+    fwd = lambda M, K0, N: L.vad_mlp_tail_forward(
+        None, M, K0, ia(*N), none, none, ia(1, 1, 1, 1, 0), (ctypes.c_double * 5)(), (ctypes.c_uint32 * 5)(), 0, 0, 0,
+        0, none, None, 0, None)
+    for K0, N in [(40, (8, 6, 8, 8, 4)),      # a width that is no multiple of 4
+                  (40, (12, 8, 8, 8, 4)),     # layer 1's input width no multiple of 8
+                  (40, (8, 8, 8, 8, 3)),
+                  (40, (1024, 8, 8, 8, 4)),   # wider than the LDS rows
+                  (40, (8, 8, 520, 8, 4))]:
+        assert fwd(3, K0, N) != 0
+        assert b"mlp_tail_fwd: layer shape" in L.vad_last_error(), (N, L.vad_last_error())
+    try:
+        assert L.vad_set_tuning(b"mlp_tail_rb", 3) == 0
+        assert fwd(3, 40, (8, 8, 8, 8, 4)) != 0
+        assert b"mlp_tail_fwd: rows per block 2, 4 or 8" in L.vad_last_error()
+    finally:
+        L.vad_set_tuning(b"mlp_tail_rb", 0)
+    # a legal chain gets past those checks and stops at the wrapper's own, still before any launch
+    assert fwd(3, 40, (8, 8, 8, 8, 4)) != 0
+    assert b"vad_mlp_tail_forward: scratch too small" in L.vad_last_error()
+    assert L.vad_mlp_tail_backward(3, None, none, ia(40, 8, 8, 8, 8), ia(8, 8, 8, 12, 4), none, None, none, None,
+                                   None) != 0
+    assert b"vad_mlp_tail_backward: unsupported shape" in L.vad_last_error()
+    assert L.vad_dense_forward_ex(None, 4, 8, None, None, 4, None, 1, 1.0, 0, 0, 0, 0, 0, None, 0, None) != 0
+    assert b"vad_dense_forward_ex: unsupported shape" in L.vad_last_error()
