@@ -42,6 +42,11 @@ _SIGS = {
     "vad_cad_workspace_bytes": (_I64, [_P]),
     "vad_cad_bind": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vad_cad_forward": (_I, [_P, _P, _I, _U64, _U64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vad_cad_frame_cache_floats": (_I64, [_I64]),
+    "vad_cad_frame_cache_offset": (_I64, [_I64, _I]),
+    "vad_cad_frames_forward": (_I, [_P, _P, _I64, _P, _I64, _P]),
+    "vad_cad_windows_forward": (_I, [_P, _P, _I64, _I, _I, _I64, _I, _U64, _U64, _I64, _P, _P, _P, _P, _P, _P, _P,
+                                     _P]),
     "vad_cad_backward": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vad_cad_backward_stage": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vad_cad_wait_side": (_I, [_P, _P]),

@@ -221,3 +221,19 @@ class CausalAnomalyDetector(nn.Module):
             "direct_predictions": probs,
             "causal_anomaly_scores": causal,
         }
+
+    def score_video(self, frames, window=16, stride=1, *, chunk=128, seed=0, step=0, clip0=0):
+        """Anomaly scores of the sliding windows of one video, every frame's backbone run once (eval mode, forward
+        only; video.py).  frames: (N, 1, H, W) or (1, N, 1, H, W) on a HIP device.  Window w covers frames
+        w * stride .. w * stride + window - 1, for w < Wn = (N - window) // stride + 1, and returns what the eval
+        forward returns for that clip at clip index clip0 + w (the key of its VAE noise draw).  chunk: frames per
+        backbone pass.  Returns a dict: anomaly_scores (Wn,), direct_predictions (Wn, 2), causal_anomaly_scores (Wn,),
+        kl_losses (Wn,), adjacency_matrices (Wn, 6, 6), causal_factors (list of (nmax_w, 6)), detections (list of N
+        per-frame (count_f, 4) tensors: trailing frames that fill no window have detections but no score) and
+        window_starts (int64 (Wn,), on the host; evaluate.window_frame_scores turns scores + starts into a per-frame
+        curve).  Raises ValueError, before any device work, in training mode, for a wrong rank, N < window,
+        stride < 1 or chunk < 1, and when set_compute_dtype(torch.bfloat16) is active: the scorer computes in fp32
+        only.  No parameter or BatchNorm buffer changes; the plans' activations do, so a backward still pending on an
+        earlier forward raises the "most recent forward only" error."""
+        from . import video as _video
+        return _video.score_video(self, frames, window, stride, chunk=chunk, seed=seed, step=step, clip0=clip0)

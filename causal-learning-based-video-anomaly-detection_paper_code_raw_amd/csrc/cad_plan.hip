@@ -792,7 +792,9 @@ struct CadPlanImpl {
 
   const float* x_last = nullptr;  // the last forward's input (the stem backward's conv1 weight gradient reads it)
 
-  int forward(const float* x, hipStream_t st) {
+  // frames_only (vad_cad_frames_forward, eval mode): the per-frame stage alone -- it stops after head_rows_fwd, before
+  // the recurrence, the direct classifier and the tail, and launches nothing on the side stream but a relayout
+  int forward(const float* x, hipStream_t st, bool frames_only = false) {
     const hipStream_t st0 = st;
     VAD_TRY(join_open_stage2(st));
     ConvPrecision prec(conv_bf16);
@@ -883,11 +885,12 @@ struct CadPlanImpl {
     // the direct classifier and the buffer clears go to the side stream: a cross-stream hand-off costs ~8 us from the
     // producer's end to the consumer's start (tools/exp/xstream_probe.hip), a same-stream one ~1 us, so only the
     // shorter chain pays the fork and the join finds it finished
-    VAD_TRY(fork(st));
+    if (!frames_only) VAD_TRY(fork(st));
     dir_pre = tail_pre = 0;
+    if (frames_only) grads_zeroed = 0;
     // (train-mode forwards with grads bound only: an eval / probe forward with labels is followed by no loss backward)
     const bool affine = labels != nullptr && training && grads != nullptr && g_cad_dir_affine != 0 && B <= 8;
-    {  // side stream: direct_classifier on the mean over T (cad:525-538, 568-570)
+    if (!frames_only) {  // side stream: direct_classifier on the mean over T (cad:525-538, 568-570)
       // (B rows only: one block per 64 columns, so the chain runs layer by layer on many CUs; layers 1-4 unsplit)
       // With labels (and B <= 8) layers 2-4 run in dir_mid together with the loss-mode input-gradient chain of the
       // stacked rows [A; beta], layers 1 and 0 of that chain follow: the backward then only folds in the causal score
@@ -952,6 +955,7 @@ struct CadPlanImpl {
       TIMED("det_fwd", mlp_tail_fwd(m, st));
     }
     TIMED("head_rows", head_rows_fwd(head_args(), dlog, head_out(), st));
+    if (frames_only) return 0;
     TIMED("head_seq", head_seq_fwd(head_args(), head_out(), st));
     VAD_TRY(join(st));
     TailArgs t = tail_args(nullptr, nullptr, nullptr, nullptr);
@@ -960,6 +964,68 @@ struct CadPlanImpl {
       t.nbt = nbt;
       t.nbt_n = 9;
     }
+    TIMED("tail", cad_tail_fwd(t, st));
+    return 0;
+  }
+
+  // The per-frame stage of the eval forward on this plan's NF frames, into frames frame0.. of a frame cache.
+  int frames_forward(const float* x, int64_t nframes, float* cache, int64_t frame0, hipStream_t st) {
+    training = 0;
+    labels = nullptr;
+    have_labels = false;
+    VAD_TRY(forward(x, st, true));
+    TIMED("frame_cache", frame_cache_store(head_args(), head_out(), feats, cache, nframes, frame0, st));
+    return 0;
+  }
+
+  // The per-window stage for windows w0 .. w0 + nw - 1 of a frame cache, nw <= B: the per-clip buffers of this plan
+  // (pooled, the direct classifier's activations, clip_flags) take one row per window.  The outputs go straight to the
+  // caller's arrays; the plan's own result arrays, flags and detector gate stay as the last forward left them.
+  int windows_forward(const float* cache, int64_t nframes, int Tw, int stride, int64_t w0, int nw, float* o_final,
+                      float* o_probs, float* o_causal, float* o_kl, float* o_z, float* o_adj, int* o_nmax,
+                      hipStream_t st) {
+    const CadLayout& LY = layout();
+    VAD_TRY(join_open_stage2(st));
+    training = 0;
+    labels = nullptr;
+    have_labels = false;
+    bwd_state = 0;
+    dir_pre = tail_pre = 0;
+    const FrameCache C(nframes);
+    TIMED("window_mean", window_mean(cache, nframes, Tw, stride, w0, nw, pooled, st));
+    // direct_classifier on the window means (cad:525-538, 568-570), eval activations, through the forward's launchers
+    const int gd[6] = {6144, 512, 256, 128, 64, 2};
+    const float* in = pooled;
+    for (int i = 0; i < 5; ++i) {
+      float* out = i < 4 ? gh[i] : glog;
+      TIMED("dir_fwd", dense_fwd(in, nw, gd[i], P(LY.dir_w[i]), P(LY.dir_b[i]), gd[i + 1], out, act(i < 4, 0, 0.0, 0),
+                                 dense_scratch, dense_scratch_floats, st, i == 0 ? 0 : 1));
+      in = out;
+    }
+    HeadArgs a = head_args();
+    a.B = nw;
+    a.T = Tw;
+    a.ws = nullptr;
+    a.iws = nullptr;
+    a.rows = nullptr;
+    a.grad = nullptr;
+    SeqWindows win{};
+    win.gi = cache + C.gi;
+    win.counts = reinterpret_cast<const int*>(cache) + C.counts;
+    win.slot = reinterpret_cast<const int*>(cache) + C.slot;
+    win.stride = stride;
+    win.w0 = w0;
+    const HeadOut ho{o_causal, o_kl, o_z, o_adj, nullptr, nullptr, o_nmax, clip_flags};
+    TIMED("head_seq_win", head_seq_windows_fwd(a, win, nw, ho, st));
+    TailArgs t{};
+    t.B = nw;
+    t.direct_logits = glog;
+    t.causal = o_causal;
+    t.kl = o_kl;
+    t.clip_flags = clip_flags;
+    t.probs = o_probs;
+    t.final_scores = o_final;
+    t.flags = flags + 2;  // (the two spare words of the 4-word array: flags[0..1] stay the last forward's)
     TIMED("tail", cad_tail_fwd(t, st));
     return 0;
   }
@@ -1427,6 +1493,40 @@ int vad_cad_forward(vad_cad_plan* plan, const float* x, int training, uint64_t s
     VAD_HIP(hipGetLastError());
   }
   return 0;
+}
+
+int vad_cad_frames_forward(vad_cad_plan* plan, const float* x, int64_t nframes, float* cache, int64_t frame0,
+                           void* stream) {
+  VAD_CHECK(plan && x && cache, "vad_cad_frames_forward: null argument");
+  CadPlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_cad_frames_forward: plan not bound");
+  VAD_CHECK(nframes >= 1 && frame0 >= 0 && frame0 + c.NF <= nframes,
+            "vad_cad_frames_forward: frame0 .. frame0 + B*T outside the nframes of the cache");
+  VAD_CHECK((int64_t)c.NF * c.H * c.W * 4 < (1ll << 31), "vad_cad_frames_forward: x is 2 GB or more");
+  VAD_CHECK(FrameCache(nframes).total * 4 < (1ll << 31), "vad_cad_frames_forward: cache is 2 GB or more");
+  return c.frames_forward(x, nframes, cache, frame0, (hipStream_t)stream);
+}
+
+int vad_cad_windows_forward(vad_cad_plan* plan, const float* cache, int64_t nframes, int T, int stride, int64_t w0,
+                            int nw, uint64_t seed, uint64_t step, int64_t clip0, float* final_scores, float* probs,
+                            float* causal, float* kl, float* z, float* adj, int32_t* nmax, void* stream) {
+  VAD_CHECK(plan && cache, "vad_cad_windows_forward: null plan or cache");
+  VAD_CHECK(final_scores && probs && causal && kl && z && adj && nmax, "vad_cad_windows_forward: null output");
+  CadPlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_cad_windows_forward: plan not bound");
+  VAD_CHECK(nframes >= 1, "vad_cad_windows_forward: nframes must be >= 1");
+  VAD_CHECK(T >= 1 && T <= nframes, "vad_cad_windows_forward: T must be in 1..nframes");
+  VAD_CHECK(T <= 4096, "vad_cad_windows_forward: T too large (head: at most 4096 steps)");
+  VAD_CHECK(stride >= 1, "vad_cad_windows_forward: stride must be >= 1");
+  VAD_CHECK(w0 >= 0 && nw >= 1 && (w0 + nw - 1) * (int64_t)stride + T <= nframes,
+            "vad_cad_windows_forward: windows w0 .. w0 + nw - 1 reach outside the video");
+  VAD_CHECK(nw <= c.B, "vad_cad_windows_forward: nw exceeds the plan's B (one per-clip scratch row per window)");
+  VAD_CHECK(FrameCache(nframes).total * 4 < (1ll << 31), "vad_cad_windows_forward: cache is 2 GB or more");
+  c.seed = seed;
+  c.step = step;
+  c.clip0 = clip0;
+  return c.windows_forward(cache, nframes, T, stride, w0, nw, final_scores, probs, causal, kl, z, adj, nmax,
+                           (hipStream_t)stream);
 }
 
 int vad_cad_backward(vad_cad_plan* plan, int use_loss, const float* d_final, const float* d_probs,

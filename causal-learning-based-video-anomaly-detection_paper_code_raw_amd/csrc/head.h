@@ -48,6 +48,7 @@ int head_pack_weights(HeadArgs& a, const int64_t* numel);
 int64_t head_ws_floats(int T);
 int64_t head_iws_ints(int T);
 int64_t head_rows_floats(int B, int T);
+int64_t head_rows_gi_offset(int B, int T);  // of the GRU input projections [B*T*5][192] in the row arrays
 
 // forward: det logits [B*T][20] -> per-clip outputs
 struct HeadOut {
@@ -64,6 +65,39 @@ int head_fwd(const HeadArgs& a, const float* det_logits, const HeadOut& o, hipSt
 // the two launches of head_fwd (row-parallel part, then the per-clip sequence part)
 int head_rows_fwd(const HeadArgs& a, const float* det_logits, const HeadOut& o, hipStream_t st);
 int head_seq_fwd(const HeadArgs& a, const HeadOut& o, hipStream_t st);
+
+// ------------------------------------------------------------------ sliding-window scoring (video.hip)
+// Frame cache of a video of N frames: what the per-frame stage of the eval forward leaves for the windowed stage.
+// Five arrays over the video's frames (float offsets, each 64-float aligned): feats [N][6144], gi [N][5][192] (the
+// GRU input projections of the frame's five trajectory rows), boxes [N][5][4], counts [N] (int), slot [N][5] (int).
+struct FrameCache {
+  int64_t N, feats, gi, boxes, counts, slot, total;
+  __host__ __device__ explicit FrameCache(int64_t N_) : N(N_) {
+    int64_t o = 0;
+    auto take = [&](int64_t w) { int64_t r_ = o; o += (N * w + 63) & ~63ll; return r_; };
+    feats = take(6144); gi = take(NMAX * 3 * GH); boxes = take(NMAX * 4); counts = take(1); slot = take(NMAX);
+    total = o;
+  }
+};
+// copies the B*T frames head_rows_fwd just processed (a.rows / a.iws, o.boxes / o.counts) and their pooled features
+// to frames frame0.. of the cache
+int frame_cache_store(const HeadArgs& a, const HeadOut& o, const float* feats, float* cache, int64_t nframes,
+                      int64_t frame0, hipStream_t st);
+// pooled[i][k] = (sum_{t < T} feats[(w0 + i) * stride + t][k]) / T for i < nw, summed in ascending t from 0 as
+// avgpool_fwd forms a clip's mean
+int window_mean(const float* cache, int64_t nframes, int T, int stride, int64_t w0, int nw, float* pooled,
+                hipStream_t st);
+// head_seq_fwd on windows of the cache, forward only: block i runs window w0 + i (frames (w0 + i) * stride + t) with
+// the RNG key of clip a.clip0 + w0 + i and writes row i of o.causal / kl / z / adj / nmax / clip_flags; a.T is the
+// window length; a.rows / a.ws / a.iws are not used (no backward state is kept)
+struct SeqWindows {
+  const float* gi;    // FrameCache::gi
+  const int* counts;  // FrameCache::counts
+  const int* slot;    // FrameCache::slot
+  int stride;
+  int64_t w0;
+};
+int head_seq_windows_fwd(const HeadArgs& a, const SeqWindows& win, int nw, const HeadOut& o, hipStream_t st);
 
 // backward: upstream grads -> grad slabs [B][slab] and d(det logits) [B*T][20]
 struct HeadUp {

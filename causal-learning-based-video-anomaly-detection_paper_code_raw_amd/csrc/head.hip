@@ -34,6 +34,7 @@ struct RowLayout {
 };
 
 int64_t head_rows_floats(int B, int T) { return RowLayout((int64_t)B * T * NMAX).total; }
+int64_t head_rows_gi_offset(int B, int T) { return RowLayout((int64_t)B * T * NMAX).gi; }
 
 // ------------------------------------------------------------------ per-clip small workspace
 struct HL {
@@ -382,7 +383,14 @@ __global__ __launch_bounds__(256) void head_rows_fwd_kernel(HeadArgs a, const fl
   }
 }
 
-__global__ __launch_bounds__(HT) void head_seq_fwd_kernel(HeadArgs a, HeadOut o) {
+// The per-clip sequence forward, for two callers.  WIN = false (head_seq_fwd_kernel): block b runs clip b of the batch
+// -- frames b*T + t of a.rows / a.iws -- and keeps the recurrence's state (r, z, n, W_hn h, h_prev rows) and its
+// small activations for the backward.  WIN = true (head_seq_win_kernel, sliding-window scoring): block b runs window
+// win.w0 + b of a frame cache -- frames (win.w0 + b) * win.stride + t -- with the RNG key of clip a.clip0 + win.w0 + b,
+// forward only: none of the backward state is stored (most of the clip kernel's memory traffic).  Every difference is
+// an `if constexpr`, so the clip kernel's arithmetic and its order are those of the untemplated kernel.
+template <bool WIN>
+__device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWindows win) {
   const int b = blockIdx.x, T = a.T, tid = threadIdx.x;
   const HL L;
   const RowLayout RL((int64_t)a.B * T * NMAX);
@@ -391,6 +399,14 @@ __global__ __launch_bounds__(HT) void head_seq_fwd_kernel(HeadArgs a, HeadOut o)
   const int* iw = a.iws + (int64_t)b * a.iws_stride;
   const int* cnt = iw;
   const int* slot = iw + T;
+  const float* gi_win = nullptr;  // WIN: the projections of the window's first frame
+  if constexpr (WIN) {
+    const int64_t f0 = (win.w0 + b) * win.stride;
+    cnt = win.counts + f0;
+    slot = win.slot + f0 * NMAX;
+    gi_win = win.gi + f0 * NMAX * G3;
+    a.clip0 += win.w0;  // the RNG key of block b: clip a.clip0 + b
+  }
   __shared__ __attribute__((aligned(16))) float big[HF_BIG];  // W_hh during the recurrence, then the MLP weights
   __shared__ __attribute__((aligned(16))) float sw[HL_TOTAL];
   __shared__ float hs[NMAX * GH];
@@ -450,7 +466,9 @@ __global__ __launch_bounds__(HT) void head_seq_fwd_kernel(HeadArgs a, HeadOut o)
         for (int k = 0; k < TC; ++k) {
           g[k][0] = g[k][1] = g[k][2] = 0.f;
           if (t0 + k < T) {
-            const float* gi = rows + RL.gi + (((int64_t)b * T + t0 + k) * NMAX + nn) * G3;
+            const float* gi;
+            if constexpr (WIN) gi = gi_win + ((int64_t)(t0 + k) * NMAX + nn) * G3;
+            else gi = rows + RL.gi + (((int64_t)b * T + t0 + k) * NMAX + nn) * G3;
             g[k][0] = gi[u]; g[k][1] = gi[GH + u]; g[k][2] = gi[2 * GH + u];
           }
         }
@@ -481,11 +499,13 @@ __global__ __launch_bounds__(HT) void head_seq_fwd_kernel(HeadArgs a, HeadOut o)
             const float r = gate_sigmoid(gc[k][0] + rz[0]);
             const float z = gate_sigmoid(gc[k][1] + rz[1]);
             const float nv = gate_tanh(gc[k][2] + r * an);
-            rows[RL.r + row * GH + u] = r;
-            rows[RL.z + row * GH + u] = z;
-            rows[RL.n + row * GH + u] = nv;
-            rows[RL.ghn + row * GH + u] = an;
-            rows[RL.hp + row * GH + u] = h;
+            if constexpr (!WIN) {
+              rows[RL.r + row * GH + u] = r;
+              rows[RL.z + row * GH + u] = z;
+              rows[RL.n + row * GH + u] = nv;
+              rows[RL.ghn + row * GH + u] = an;
+              rows[RL.hp + row * GH + u] = h;
+            }
             h = (1.f - z) * nv + z * h;
             // every lane's reads of the old h are done (lockstep wave) before the new h is published
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -493,7 +513,7 @@ __global__ __launch_bounds__(HT) void head_seq_fwd_kernel(HeadArgs a, HeadOut o)
             hs[nn * GH + u] = h;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-          } else {  // trajectory slots that do not exist in this clip
+          } else if constexpr (!WIN) {  // trajectory slots that do not exist in this clip
             rows[RL.r + row * GH + u] = 0.f;
             rows[RL.z + row * GH + u] = 0.f;
             rows[RL.n + row * GH + u] = 0.f;
@@ -634,9 +654,18 @@ __global__ __launch_bounds__(HT) void head_seq_fwd_kernel(HeadArgs a, HeadOut o)
   }
   for (int i = tid; i < NMAX * NF_; i += HT) o.z[(int64_t)b * NMAX * NF_ + i] = (i < N * NF_) ? w[L.zz + i] : 0.f;
   for (int i = tid; i < 36; i += HT) o.adj[(int64_t)b * 36 + i] = w[L.A + i];
-  __syncthreads();
-  // hand the activations to the backward kernel
-  block_copy4<3>(wg, sw, HL_HANDOFF / 4, Ident{});
+  if constexpr (!WIN) {
+    __syncthreads();
+    // hand the activations to the backward kernel
+    block_copy4<3>(wg, sw, HL_HANDOFF / 4, Ident{});
+  }
+}
+
+__global__ __launch_bounds__(HT) void head_seq_fwd_kernel(HeadArgs a, HeadOut o) {
+  head_seq_fwd_body<false>(a, o, SeqWindows{});
+}
+__global__ __launch_bounds__(HT) void head_seq_win_kernel(HeadArgs a, HeadOut o, SeqWindows win) {
+  head_seq_fwd_body<true>(a, o, win);
 }
 
 int head_rows_fwd(const HeadArgs& a, const float* det_logits, const HeadOut& o, hipStream_t st) {
@@ -647,6 +676,12 @@ int head_rows_fwd(const HeadArgs& a, const float* det_logits, const HeadOut& o, 
 }
 int head_seq_fwd(const HeadArgs& a, const HeadOut& o, hipStream_t st) {
   VAD_KLAUNCH(head_seq_fwd_kernel, dim3(a.B), dim3(HT), 0, st, a, o);
+  VAD_LAUNCH_CHECK();
+  return 0;
+}
+int head_seq_windows_fwd(const HeadArgs& a, const SeqWindows& win, int nw, const HeadOut& o, hipStream_t st) {
+  VAD_CHECK(a.T >= 1 && a.T <= 4096 && win.stride >= 1 && win.w0 >= 0 && nw >= 1, "head: bad window arguments");
+  VAD_KLAUNCH(head_seq_win_kernel, dim3(nw), dim3(HT), 0, st, a, o, win);
   VAD_LAUNCH_CHECK();
   return 0;
 }

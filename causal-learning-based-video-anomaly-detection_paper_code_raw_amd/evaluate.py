@@ -18,6 +18,30 @@ def frame_scores(clip_scores, clip_lengths) -> np.ndarray:
     return np.repeat(s, n)
 
 
+def window_frame_scores(window_scores, window_starts, window: int, n_frames: int) -> np.ndarray:
+    """Per-frame curve of sliding-window scores (CausalAnomalyDetector.score_video): a frame's score is the mean over
+    the windows [start, start + window) that cover it; a frame no window covers (a gap between windows when the stride
+    exceeds the window, the trailing frames that fill no window) takes the score of the nearest covered frame, the
+    earlier one on a tie.  For non-overlapping windows that tile the video this is ``frame_scores(scores, window)``."""
+    s = np.asarray(window_scores, dtype=np.float64).reshape(-1)
+    st = np.asarray(window_starts, dtype=np.int64).reshape(-1)
+    if s.shape != st.shape or s.size == 0:
+        raise ValueError("window_frame_scores: one start per score, at least one window")
+    if window < 1 or n_frames < 1 or st.min() < 0 or st.max() + window > n_frames:
+        raise ValueError("window_frame_scores: every window must lie inside [0, n_frames)")
+    tot = np.zeros(n_frames, dtype=np.float64)
+    cnt = np.zeros(n_frames, dtype=np.int64)
+    for v, a in zip(s, st):  # (ascending window order: the same sum for every caller)
+        tot[a:a + window] += v
+        cnt[a:a + window] += 1
+    covered = np.flatnonzero(cnt > 0)
+    out = np.empty(n_frames, dtype=np.float64)
+    out[covered] = tot[covered] / cnt[covered]
+    for f in np.flatnonzero(cnt == 0):
+        out[f] = out[covered[np.argmin(np.abs(covered - f))]]  # (argmin: the first, i.e. earlier, of two equally near)
+    return out
+
+
 def roc_auc(scores, labels) -> float:
     """Binary ROC-AUC (mid-ranks for tied scores).  Raises ValueError when only one class is present, as
     roc_auc_score does."""

@@ -124,6 +124,38 @@ int vad_cad_optimizer_step(vad_cad_plan* plan, float lr, float beta1, float beta
 typedef int (*vad_bn_sync_fn)(void* user, int bn_layer, int phase, int64_t n, void* stream);
 int vad_cad_set_bn_sync(vad_cad_plan* plan, vad_bn_sync_fn fn, void* user, int world);
 
+/* Sliding-window scoring of a video (eval mode, forward only).  Replaces test_model's loop over clips
+ * (cad:1210-1232) on the clips UCSDped2Dataset enumerates at stride T/2 (cad:57), which runs every frame's backbone
+ * once per clip that holds it: with running BatchNorm statistics everything up to the GRU input projection depends on
+ * the frame alone, so it runs once per frame into a caller-owned frame cache, and windows then read frames
+ * start + t of the cache.
+ * The cache of a video of nframes frames holds five fields, each [nframes][...] and 64-float aligned:
+ * 0 feats [6144] (cad:560-566), 1 gi [5][192] (W_ih x + b_ih of the frame's zero-padded trajectory rows, cad:248-274,
+ * 298), 2 boxes [5][4] (compacted in-range boxes or the fallback box, cad:198-228), 3 counts (int32), 4 slot [5]
+ * (int32: the detector output a compacted box came from, -1 fallback, -2 padding).
+ * vad_cad_frame_cache_floats: its size in floats; vad_cad_frame_cache_offset: a field's offset in floats (both -1 on
+ * a bad argument). */
+int64_t vad_cad_frame_cache_floats(int64_t nframes);
+int64_t vad_cad_frame_cache_offset(int64_t nframes, int field);
+/* The per-frame stage of CausalAnomalyDetector.forward in eval mode (cad:548-566 backbone + pooled features,
+ * cad:167-179 detector_net, cad:198-228 box decode, cad:248-274 ReID + trajectory rows, and the GRU's input
+ * projection of cad:298) on the plan's B*T frames x [B*T,1,H,W], written to frames frame0 .. frame0 + B*T - 1 of
+ * the cache.  It stops before the recurrence.  No parameter, BatchNorm buffer or counter changes; the plan's
+ * activations of an earlier forward do. */
+int vad_cad_frames_forward(vad_cad_plan* plan, const float* x, int64_t nframes, float* cache, int64_t frame0,
+                           void* stream);
+/* The per-window stage for windows w0 .. w0 + nw - 1 (window w = frames w*stride .. w*stride + T - 1 of the cache; nw
+ * at most the plan's B): the mean over the window's features and the direct classifier on it (cad:568-570), the GRU
+ * recurrence, VAE, structure learner, dynamics and scorers per window (cad:287-502; Nmax = the largest box count
+ * among the window's own frames, cad:262-271) and the blend (cad:573-576).  Row i of every output is window w0 + i,
+ * which equals vad_cad_forward(training = 0) on that clip at clip index clip0 + w0 + i -- the key of its VAE noise
+ * (cad:328-331 draws it in eval mode too).  outputs: final [nw], probs [nw,2], causal [nw], kl [nw], z [nw,5,6],
+ * adj [nw,6,6], nmax int32 [nw]; none may be NULL.  T > nframes, stride < 1 or a window range outside the video is an
+ * error and launches nothing. */
+int vad_cad_windows_forward(vad_cad_plan* plan, const float* cache, int64_t nframes, int T, int stride, int64_t w0,
+                            int nw, uint64_t seed, uint64_t step, int64_t clip0, float* final_scores, float* probs,
+                            float* causal, float* kl, float* z, float* adj, int32_t* nmax, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Single building blocks (kernel unit tests; same kernels as the fused step)
  * ------------------------------------------------------------------------------------------ */
