@@ -1609,6 +1609,11 @@ int vad_cad_debug_buffer(vad_cad_plan* plan, const char* name, int idx, void** p
     *ptr = c.gh[idx];
     *nfloats = (int64_t)c.B * w[idx];
   }
+  else if (n == "det_h" && idx >= 0 && idx < 4) {  // detector MLP hidden layer idx (post ReLU / dropout), NF rows
+    const int w[4] = {512, 256, 128, 64};
+    *ptr = c.dh[idx];
+    *nfloats = NF * w[idx];
+  }
   // the weight images, whole buffers (wf: fp32 image | bf16 copy; wd: fp32 image | bf16 copy or the three bf16 planes)
   else if (n == "wf" && idx >= 0 && idx < 8) { *ptr = c.wf[idx]; *nfloats = (int64_t)c.L[idx].Co * c.L[idx].Ci * 9 * 3 / 2; }
   else if (n == "wd" && idx >= 0 && idx < 8) { *ptr = c.wd[idx]; *nfloats = (int64_t)c.L[idx].Co * c.L[idx].Ci * 9 * 5 / 2; }

@@ -122,12 +122,13 @@ def read_debug(plan, name, idx=0, n=None, dtype=np.float32):
     return out
 
 
-def read_act(plan, name, idx=0):
-    """A backbone activation buffer as float64, whatever its storage (fp32, or bf16 when the plan ran act_bf16)."""
-    if int(read_debug_len(plan, "act_bf16")) == 1 and name in ("y", "pool"):
-        u = read_debug(plan, name, idx, dtype=np.uint16)
+def read_act(plan, name, idx=0, n=None):
+    """A backbone activation buffer as float64, whatever its storage (fp32, or bf16 when the plan ran act_bf16):
+    pool, y, and the backward's dA / dY (n: their element count -- dA is one buffer of the largest map's size)."""
+    if int(read_debug_len(plan, "act_bf16")) == 1 and name in ("y", "pool", "dA", "dY"):
+        u = read_debug(plan, name, idx, n=n, dtype=np.uint16)
         return (u.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-    return read_debug(plan, name, idx).astype(np.float64)
+    return read_debug(plan, name, idx, n=n).astype(np.float64)
 
 
 def read_debug_len(plan, name, idx=0):
@@ -208,7 +209,7 @@ def reshape_masks(masks, x):
 
 
 def pinned_oracle_grads(state_dict, x, labels, draws, masks, sync_group=None, bf16=False, dtype=torch.float64,
-                        head_masks=None):
+                        head_masks=None, det_masks=None, fault=None):
     """float64 oracle forward/backward of one train step with the ReLU decisions of another forward (masks from
     hip_relu_masks): the exact gradient of that forward's piecewise-linear branch, free of kink flips.  Returns
     (grads {name: float64 tensor or None}, losses {name: float64}, the oracle's result dict incl. "bufs" and
@@ -216,7 +217,8 @@ def pinned_oracle_grads(state_dict, x, labels, draws, masks, sync_group=None, bf
     bf16: the backbone as the device computes it in bf16 mode (cad_oracle.backbone_forward_bf16; "reversed": its convs
     sum the input channels in reverse order).  dtype: the oracle's arithmetic (float64; float32 gives further,
     independent restatements at fp32 accumulation).  head_masks: the direct classifier's ReLU decisions too
-    (cad_oracle.direct_forward's masks; its pre-activations land in record["dir_z{i}"])."""
+    (cad_oracle.direct_forward's masks; its pre-activations land in record["dir_z{i}"]); det_masks: the detector
+    MLP's likewise (record["det_z{i}"]); fault: backbone_forward_bf16's ragged-edge faults (tests of the bounds)."""
     from oracle import cad_oracle as co
     params = {k: v.detach().to(dtype).clone() for k, v in state_dict.items()
               if "running" not in k and "num_batches" not in k}
@@ -227,6 +229,10 @@ def pinned_oracle_grads(state_dict, x, labels, draws, masks, sync_group=None, bf
     kw = dict(bf16=bf16) if bf16 else {}
     if head_masks is not None:
         kw["head_masks"] = head_masks
+    if det_masks is not None:
+        kw["det_masks"] = det_masks
+    if fault is not None:
+        kw["fault"] = fault
     res = co.cad_train_step(params, bufs, {}, xd, labels, draws, relu_masks=rm, sync_group=sync_group,
                             record=record, **kw)
     res["bufs"] = bufs  # running stats after the step's forward
@@ -263,6 +269,249 @@ def rel_l2(a, b):
     a = np.asarray(a, np.float64).reshape(-1)
     b = np.asarray(b, np.float64).reshape(-1)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+
+
+# ---------------------------------------------------------------- bf16 mode against its restatements
+# The spread a correct bf16 implementation may show against the float64 restatement, in units of the float32
+# restatements' own distance to it (tests/test_cad_gpu.py has the derivation).
+BF16_SPREAD = 2.0
+
+
+def bf16_step_references(sd, x, y, draws, masks, hm, det_masks=None):
+    """The four pinned oracle steps a bf16 step is judged by, each pinned_oracle_grads' (grads, losses, result):
+    "ref" the float64 restatement of the device's bf16 rounding points, "a1" / "a2" the same in float32 (channel sums
+    as written / reversed), "ex" the exact float64 step (no rounding points)."""
+    kw = dict(head_masks=hm, det_masks=det_masks)
+    return dict(ref=pinned_oracle_grads(sd, x, y, draws, masks, bf16=True, **kw),
+                a1=pinned_oracle_grads(sd, x, y, draws, masks, bf16=True, dtype=torch.float32, **kw),
+                a2=pinned_oracle_grads(sd, x, y, draws, masks, bf16="reversed", dtype=torch.float32, **kw),
+                ex=pinned_oracle_grads(sd, x, y, draws, masks, **kw))
+
+
+def restatement_as_device(triple):
+    """A pinned oracle step in the form check_bf16_step takes for the device."""
+    g, l, res = triple
+    return dict(final=res["out"]["anomaly_scores"].detach().double().numpy(),
+                probs=res["out"]["direct_predictions"].detach().double().numpy(), total=float(l["total"]),
+                grads={n: (None if t is None else t.detach().double().numpy().reshape(-1)) for n, t in g.items()})
+
+
+def check_bf16_step(dev, refs, masks, hm, draws, label, yards=("a1", "a2"), det_hm=None):
+    """bf16 parity of one step: dev (final, probs, total, grads {name: flat array}) against the float64 bf16
+    restatement refs["ref"], with the float32 restatements named by yards as the yardstick (see BF16_SPREAD) and the
+    exact float64 step as a loose backstop.  masks / hm / det_hm: dev's ReLU decisions (backbone, direct classifier,
+    detector MLP or None), which every reference was pinned to.  Returns the worst device / yardstick ratio over the
+    gradient tensors."""
+    from tests.test_oracle_golden import is_pre_bn_bias
+    ref_g, ref_l, ref = refs["ref"]
+    ys = [refs[k] for k in yards]
+    ex_g, ex_l, ex = refs["ex"]
+    keep = [torch.from_numpy(draws.direct_keep1), torch.from_numpy(draws.direct_keep2), None, None]
+    for i in range(4):
+        z = ref["record"][f"dir_z{i}"]
+        live = torch.ones_like(hm[i]) if keep[i] is None else keep[i].to(torch.bool)
+        fl = ((z > 0) != hm[i]) & live
+        rms = float(z.pow(2).mean().sqrt())
+        wz = float(z.abs()[fl].max()) if bool(fl.any()) else 0.0
+        print(f"  bf16 direct_classifier ReLU {i}: {int(fl.sum())} flips against the float64 restatement "
+              f"(worst |z| {wz / rms:.3g} rms)")
+        assert wz <= 2.0 ** -8 * rms, i
+    if det_hm is not None:
+        # the detector MLP's hidden units, pinned the same way; a decision may differ from the float64 restatement's
+        # own sign as far as the float32 restatements' own signs do (the backbone layers' rule below)
+        keep = [torch.from_numpy(draws.det_keep1), torch.from_numpy(draws.det_keep2), None, None]
+        for i in range(4):
+            z = ref["record"][f"det_z{i}"]
+            live = torch.ones_like(det_hm[i]) if keep[i] is None else keep[i].to(torch.bool)
+            fl = ((z > 0) != det_hm[i]) & live
+            fas = [((z > 0) != (a[2]["record"][f"det_z{i}"].double() > 0)) & live for a in ys]
+            rms = float(z.pow(2).mean().sqrt())
+            wz = float(z.abs()[fl].max()) if bool(fl.any()) else 0.0
+            wa = max(float(z.abs()[fa].max()) if bool(fa.any()) else 0.0 for fa in fas)
+            print(f"  bf16 detector ReLU {i}: {int(fl.sum())} flips against the float64 restatement (worst |z| "
+                  f"{wz / rms:.3g} rms; float32 restatements {max(int(fa.sum()) for fa in fas)}, {wa / rms:.3g} rms)")
+            assert wz <= BF16_SPREAD * wa + 2.0 ** -8 * rms, i
+    bad = []
+
+    def within(d, yard, floor, what):
+        if not d <= BF16_SPREAD * yard + floor:
+            bad.append(f"{what}: device {d:.3g} vs float32 restatement {yard:.3g} (bound {BF16_SPREAD} x + {floor:g})")
+
+    for key, out_key, floor in (("final", "anomaly_scores", 1e-6), ("probs", "direct_predictions", 1e-6)):
+        r64 = ref["out"][out_key].detach().double().numpy()
+        d = float(np.abs(dev[key] - r64).max())
+        yard = max(float(np.abs(a[2]["out"][out_key].detach().double().numpy() - r64).max()) for a in ys)
+        print(f"  bf16 {key}: device {d:.3g}, float32 restatements {yard:.3g}")
+        within(d, yard, floor, key)
+    d = abs(dev["total"] - float(ref_l["total"]))
+    yard = max(abs(float(a[1]["total"]) - float(ref_l["total"])) for a in ys)
+    within(d, yard, 1e-6 * abs(float(ref_l["total"])), "total loss")
+    # ReLU decisions: the device's (pinned everywhere) against the float64 restatement's own signs, per layer, beside
+    # the float32 restatement's own signs
+    for l in range(8):
+        z64 = ref["record"][f"z{l}"]
+        m = masks[l].reshape(z64.shape).to(torch.bool)
+        fd = (z64 > 0) != m
+        fas = [(z64 > 0) != (a[2]["record"][f"z{l}"].double() > 0) for a in ys]
+        wd = float(z64.abs()[fd].max()) if bool(fd.any()) else 0.0
+        wa = max(float(z64.abs()[fa].max()) if bool(fa.any()) else 0.0 for fa in fas)
+        na = max(int(fa.sum()) for fa in fas)
+        rms = float(z64.pow(2).mean().sqrt())
+        print(f"  bf16 layer {l} ReLU flips: device {int(fd.sum())} (worst |z| {wd / rms:.3g} rms), float32 "
+              f"restatements {na} ({wa / rms:.3g} rms)")
+        # (floors: a decision within one bf16 ulp of the layer's scale from zero may flip on a single rounding flip)
+        near = int((z64.abs() <= 2.0 ** -8 * rms).sum())
+        assert int(fd.sum()) <= BF16_SPREAD * na + near, l
+        assert wd <= BF16_SPREAD * wa + 2.0 ** -8 * rms, l
+    worst = 0.0
+    for n, mine in dev["grads"].items():
+        r = ref_g.get(n)
+        if r is None:
+            assert mine is None or np.abs(mine).max() == 0.0, n
+            continue
+        if is_pre_bn_bias(n):
+            assert np.abs(mine).max() < 1e-4, n
+            continue
+        r = r.detach().double().numpy()
+        d = rel_l2(mine, r)
+        yard = max(rel_l2(a[0][n].detach().double().numpy(), r) for a in ys)
+        exact = rel_l2(mine, ex_g[n].detach().double().numpy())
+        worst = max(worst, d / max(yard, 1e-12))
+        print(f"  bf16 {n}: device {d:.3g}, float32 restatements {yard:.3g} (device vs the exact step "
+              f"{exact:.3g})")
+        within(d, yard, 1e-5, n)
+        if not exact <= 0.15:
+            bad.append(f"{n}: device vs the exact float64 step {exact:.3g} > 0.15 (backstop)")
+    for key, out_key in (("final", "anomaly_scores"), ("probs", "direct_predictions")):
+        d = float(np.abs(dev[key] - ex["out"][out_key].detach().double().numpy()).max())
+        if not d <= 2e-2:
+            bad.append(f"{key}: device vs the exact float64 step {d:.3g} > 2e-2 (backstop)")
+    if not abs(dev["total"] - float(ex_l["total"])) <= 2e-2 * abs(float(ex_l["total"])):
+        bad.append("total loss: device vs the exact float64 step beyond 2e-2 relative (backstop)")
+    print(f"{label}, bf16: worst device / float32-restatements distance ratio {worst:.3g}")
+    assert not bad, "; ".join(bad)
+    return worst
+
+
+# ---------------------------------------------------------------- bf16 mode layer by layer, local to the map's edges
+BF16_ACT_FLOOR = 2.0 ** -9  # bf16-stored tensors: half a bf16 ulp at the tensor's scale (one rounding flip)
+F32_STAT_FLOOR = 1e-6       # the fp32 BatchNorm statistics
+MIN_SET = 64                # pixel sets smaller than this are not judged
+
+
+def _nhwc(t):
+    return np.ascontiguousarray(t.detach().double().permute(0, 2, 3, 1).numpy())
+
+
+def restatement_layer_tensors(triple, masks):
+    """The per-layer tensors of a pinned bf16 restatement step as the device stores them, {name: float64 array}:
+    "pool" and "y{l}" (NF, OH, OW, C); "dY{l}" and "dA{l}" (the gradients of y{l} and of the post-ReLU activation
+    a{l}, rounded to bf16 as stored); per channel "mean{l}", "invstd{l}", "mdz{l}" = mean(dZ), "mdzx{l}" =
+    mean(dZ * xhat) with dZ = dA{l} masked by the layer's ReLU decision -- taken from the record where a fault
+    injection put its own there."""
+    from oracle.cad_oracle import bf16r
+    rec = triple[2]["record"]
+    out = {"pool": _nhwc(rec["pool_raw"])}
+    for l in range(8):
+        y = rec[f"y{l}"].detach().double()
+        mean = rec[f"mean{l}"].double() if f"mean{l}" in rec else y.mean((0, 2, 3))
+        inv = rec[f"invstd{l}"].double() if f"invstd{l}" in rec else torch.rsqrt(y.var((0, 2, 3), unbiased=False) + 1e-5)
+        da = bf16r(rec[f"da{l}"]).double()
+        dz = da * masks[l].reshape(y.shape).to(torch.float64)
+        xh = (y - mean[None, :, None, None]) * inv[None, :, None, None]
+        bm = rec.get(f"bwd_means{l}")
+        out[f"y{l}"], out[f"dA{l}"], out[f"dY{l}"] = _nhwc(y), _nhwc(da), _nhwc(bf16r(rec[f"dy{l}"]))
+        out[f"mean{l}"], out[f"invstd{l}"] = mean.numpy(), inv.numpy()
+        out[f"mdz{l}"] = (bm["mdz"].double() if bm else dz.mean((0, 2, 3))).numpy()
+        out[f"mdzx{l}"] = (bm["mdzx"].double() if bm else (dz * xh).mean((0, 2, 3))).numpy()
+    return out
+
+
+def device_layer_tensors(eng, run, shapes):
+    """The same tensors read from the device after one whole forward + backward of the step.  run() repeats that step
+    (called once per layer with the plan's stop_layer debug set, so that layer's dY and the dA under it are still in
+    their buffers); shapes: per layer (NF, OH, OW, C).  dA7 (the average pool's backward output) is overwritten inside
+    every backward and is not read."""
+    from vad_amd import _native as nat
+    pl = eng._last[0]
+    out = {"pool": read_act(pl, "pool").reshape(shapes[0][:3] + (32,))}  # (layer 0 has stride 1: the pooled map's size)
+    for l in range(8):
+        C = shapes[l][3]
+        st = read_debug(pl, "stats", l + 1).astype(np.float64)
+        out[f"y{l}"] = read_act(pl, "y", l).reshape(shapes[l])
+        for j, k in ((0, "mean"), (1, "invstd"), (5, "mdz"), (6, "mdzx")):
+            out[f"{k}{l}"] = st[j * C:(j + 1) * C]
+    try:
+        for l in range(7, -1, -1):
+            nat.check(nat.lib().vad_cad_set_debug(pl.h, b"stop_layer", l))
+            run()
+            assert eng._last[0] is pl
+            out[f"dY{l}"] = read_act(pl, "dY", 0, n=int(np.prod(shapes[l]))).reshape(shapes[l])
+            if l > 0:
+                out[f"dA{l - 1}"] = read_act(pl, "dA", 0, n=int(np.prod(shapes[l - 1]))).reshape(shapes[l - 1])
+    finally:
+        nat.check(nat.lib().vad_cad_set_debug(pl.h, b"stop_layer", -1))
+    return out
+
+
+def edge_sets(shape, tiles=()):
+    """The pixel sets of an (NF, OH, OW, C) map that the edge-local bound is taken over: {label: index}.  tiles:
+    (name, NI, TH, TW) of the kernels that tile this map; where the map's edge cuts a tile (or the last frame group is
+    partly empty) that tile's last row / column is the map's last one (already a set), and the whole cut strip is
+    added.  Sets with the same pixels are listed once."""
+    NF, OH, OW, _ = shape
+    al = slice(None)
+    sets = {"whole": (al, al, al), "first row": (al, slice(0, 1), al), "last row": (al, slice(OH - 1, OH), al),
+            "first column": (al, al, slice(0, 1)), "last column": (al, al, slice(OW - 1, OW)),
+            "last frame": (slice(NF - 1, NF), al, al)}
+    for name, ni, th, tw in tiles:
+        if OH % th:
+            sets[f"rows of the cut {name} tile"] = (al, slice(OH - OH % th, OH), al)
+        if OW % tw:
+            sets[f"columns of the cut {name} tile"] = (al, al, slice(OW - OW % tw, OW))
+        if NF % ni:
+            sets[f"frames of the last {name} group"] = (slice(NF - NF % ni, NF), al, al)
+    seen, out = set(), {}
+    for k, ix in sets.items():
+        key = tuple(s.indices(n) for s, n in zip(ix, (NF, OH, OW)))
+        if key not in seen:
+            seen.add(key)
+            out[k] = ix
+    return out
+
+
+def check_edge_local(dev, ref, yards, tiles, label, quiet=False):
+    """The per-layer, edge-local bf16 bound.  dev / ref / yards: {name: array} (restatement_layer_tensors /
+    device_layer_tensors) of the device, the float64 restatement and the float32 restatements; tiles: {tensor name:
+    edge_sets' tiles}.  For every tensor V and pixel set S: E(S) = rms over S of (V - V64) / rms of V64 over the
+    whole tensor; the device's must not exceed BF16_SPREAD x the largest of the yardsticks' + the floor (2^-9 for the
+    bf16-stored maps, 1e-6 for the fp32 statistics).  Pixel sets under MIN_SET elements are skipped (printed); a
+    statistics vector is one set whatever its channel count: each element is already a mean over every pixel.
+    Returns (worst E_dev / max E_f32 over the sets the yardstick moved at all, the failures as strings)."""
+    worst, bad = 0.0, []
+    for name, v64 in ref.items():
+        if name not in dev:
+            continue
+        scale = max(float(np.sqrt(np.mean(v64 * v64))), 1e-300)
+        stat = v64.ndim == 1
+        floor = F32_STAT_FLOOR if stat else BF16_ACT_FLOOR
+        sets = {"whole": (slice(None),)} if stat else edge_sets(v64.shape, tiles.get(name, ()))
+        for sname, ix in sets.items():
+            r = v64[ix]
+            if not stat and r.size < MIN_SET:
+                print(f"  {label} {name} [{sname}]: skipped, {r.size} elements")
+                continue
+            e = float(np.sqrt(np.mean((dev[name][ix] - r) ** 2))) / scale
+            ey = max(float(np.sqrt(np.mean((a[name][ix] - r) ** 2))) / scale for a in yards)
+            ratio = e / ey if ey > 0 else (0.0 if e == 0 else float("inf"))
+            if ey > 0:
+                worst = max(worst, ratio)
+            if not quiet:
+                print(f"  {label} {name} [{sname}]: device {e:.3g}, float32 restatements {ey:.3g}, ratio {ratio:.3g}")
+            if not e <= BF16_SPREAD * ey + floor:
+                bad.append(f"{name} [{sname}]: device {e:.3g} vs float32 restatements {ey:.3g} "
+                           f"(bound {BF16_SPREAD} x + {floor:.3g})")
+    return worst, bad
 
 
 def check_running_stats(flat_bufs, ref_bufs, rtol=1e-4, atol=1e-5):

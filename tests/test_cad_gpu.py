@@ -15,8 +15,8 @@ import pytest
 import torch
 
 from oracle import cad_oracle as co
-from tests.golden_util import (cad_cases, check_mask_flips, hip_relu_masks, load, make_cad_model,
-                               pinned_oracle_grads, rel_l2)
+from tests.golden_util import (BF16_SPREAD, cad_cases, check_mask_flips, hip_relu_masks, load,  # noqa: F401
+                               make_cad_model, pinned_oracle_grads, rel_l2)
 from tests.test_oracle_golden import is_pre_bn_bias
 
 pytestmark = pytest.mark.gpu
@@ -397,96 +397,29 @@ def test_module_api_train_mode_unfrozen_227():
 # direct classifier unpinned, one of its hidden units within 1.6e-3 rms of zero took the other branch on the device,
 # which moved d_pooled and with it every backbone gradient by ~6 % and direct_classifier.3 / .6 by 5-8 % -- that
 # was the earlier "bf16 drift", not the rounding cascade.)
-BF16_SPREAD = 2.0
+# (BF16_SPREAD = 2.0 and the checks themselves: tests/golden_util.py, shared with test_cad_bf16_ragged_gpu.py)
 
 
-def _bf16_vs_restatement(o, eng, masks, gr, x, y, sd, draws):
-    """config-4 bf16 parity: the device (o, eng, gr) vs the float64 bf16 restatement, with the two float32
-    restatements as the yardstick (see BF16_SPREAD)."""
+def _bf16_vs_restatement(o, eng, masks, gr, x, y, sd, draws, label="config 4 per rank", det_pin=False):
+    """bf16 parity of one step: the device (o, eng, gr) vs the float64 bf16 restatement, with the two float32
+    restatements as the yardstick (see BF16_SPREAD; the checks are tests.golden_util.check_bf16_step).  det_pin: the
+    detector MLP's hidden ReLU decisions are taken from the device too (forced-detection cases, where they carry a
+    gradient).  Returns (worst gradient ratio, the references, the direct classifier's and detector's masks)."""
     # the direct classifier's ReLU decisions are the device's too (its hidden units are pinned like the backbone's: a
     # unit within rounding of zero may otherwise flip between two correct runs and move the head's weight gradients
     # by O(1) in relative terms -- round 5: one such unit moved direct_classifier.3 / .6 by 5-8 %)
-    from tests.golden_util import read_debug
-    B = y.shape[0]
+    from tests.golden_util import bf16_step_references, check_bf16_step, read_debug
+    B, NF = y.shape[0], x.shape[0] * x.shape[1]
     hm = [torch.from_numpy(read_debug(eng._last[0], "dir_h", i).reshape(B, w) > 0)
           for i, w in enumerate((512, 256, 128, 64))]
-    ref_g, ref_l, ref = pinned_oracle_grads(sd, x, y, draws, masks, bf16=True, head_masks=hm)
-    a1 = pinned_oracle_grads(sd, x, y, draws, masks, bf16=True, dtype=torch.float32, head_masks=hm)
-    a2 = pinned_oracle_grads(sd, x, y, draws, masks, bf16="reversed", dtype=torch.float32, head_masks=hm)
-    keep = [torch.from_numpy(draws.direct_keep1), torch.from_numpy(draws.direct_keep2), None, None]
-    for i in range(4):
-        z = ref["record"][f"dir_z{i}"]
-        live = torch.ones_like(hm[i]) if keep[i] is None else keep[i].to(torch.bool)
-        fl = ((z > 0) != hm[i]) & live
-        rms = float(z.pow(2).mean().sqrt())
-        wz = float(z.abs()[fl].max()) if bool(fl.any()) else 0.0
-        print(f"  bf16 direct_classifier ReLU {i}: {int(fl.sum())} flips against the float64 restatement "
-              f"(worst |z| {wz / rms:.3g} rms)")
-        assert wz <= 2.0 ** -8 * rms, i
-    # the exact (float64, no bf16 rounding) step: a loose backstop beside the restatement-based bounds, so a rounding
-    # point that the device and the bf16 restatement share by mistake cannot pass unnoticed
-    ex_g, ex_l, ex = pinned_oracle_grads(sd, x, y, draws, masks, head_masks=hm)
-
-    bad = []
-
-    def within(dev, yard, floor, what):
-        if not dev <= BF16_SPREAD * yard + floor:
-            bad.append(f"{what}: device {dev:.3g} vs float32 restatement {yard:.3g} (bound {BF16_SPREAD} x + {floor:g})")
-
-    for key, out_key, floor in (("final", "anomaly_scores", 1e-6), ("probs", "direct_predictions", 1e-6)):
-        r64 = ref["out"][out_key].detach().double().numpy()
-        dev = float(np.abs(o[key].cpu().numpy() - r64).max())
-        yard = max(float(np.abs(a[2]["out"][out_key].detach().double().numpy() - r64).max()) for a in (a1, a2))
-        print(f"  bf16 {key}: device {dev:.3g}, float32 restatements {yard:.3g}")
-        within(dev, yard, floor, key)
-    dev = abs(float(o["losses"][4]) - float(ref_l["total"]))
-    yard = max(abs(float(a[1]["total"]) - float(ref_l["total"])) for a in (a1, a2))
-    within(dev, yard, 1e-6 * abs(float(ref_l["total"])), "total loss")
-    # ReLU decisions: the device's (pinned everywhere) against the float64 restatement's own signs, per layer, beside
-    # the float32 restatement's own signs
-    for l in range(8):
-        z64 = ref["record"][f"z{l}"]
-        m = masks[l].reshape(z64.shape).to(torch.bool)
-        fd = (z64 > 0) != m
-        fas = [(z64 > 0) != (a[2]["record"][f"z{l}"].double() > 0) for a in (a1, a2)]
-        wd = float(z64.abs()[fd].max()) if bool(fd.any()) else 0.0
-        wa = max(float(z64.abs()[fa].max()) if bool(fa.any()) else 0.0 for fa in fas)
-        na = max(int(fa.sum()) for fa in fas)
-        rms = float(z64.pow(2).mean().sqrt())
-        print(f"  bf16 layer {l} ReLU flips: device {int(fd.sum())} (worst |z| {wd / rms:.3g} rms), float32 "
-              f"restatements {na} ({wa / rms:.3g} rms)")
-        # (floors: a decision within one bf16 ulp of the layer's scale from zero may flip on a single rounding flip)
-        near = int((z64.abs() <= 2.0 ** -8 * rms).sum())
-        assert int(fd.sum()) <= BF16_SPREAD * na + near, l
-        assert wd <= BF16_SPREAD * wa + 2.0 ** -8 * rms, l
-    worst = 0.0
-    for i, n in enumerate(eng.slot_names):
-        r = ref_g.get(n)
-        mine = gr[eng.slot_offset[i]:eng.slot_offset[i] + eng.slot_numel[i]].astype(np.float64)
-        if r is None:
-            assert np.abs(mine).max() == 0.0, n
-            continue
-        if is_pre_bn_bias(n):
-            assert np.abs(mine).max() < 1e-4, n
-            continue
-        r = r.detach().double().numpy()
-        dev = rel_l2(mine, r)
-        yard = max(rel_l2(a[0][n].detach().double().numpy(), r) for a in (a1, a2))
-        exact = rel_l2(mine, ex_g[n].detach().double().numpy())
-        worst = max(worst, dev / max(yard, 1e-12))
-        print(f"  bf16 {n}: device {dev:.3g}, float32 restatements {yard:.3g} (device vs the exact step "
-              f"{exact:.3g})")
-        within(dev, yard, 1e-5, n)
-        if not exact <= 0.15:
-            bad.append(f"{n}: device vs the exact float64 step {exact:.3g} > 0.15 (backstop)")
-    for key, out_key in (("final", "anomaly_scores"), ("probs", "direct_predictions")):
-        d = float(np.abs(o[key].cpu().numpy() - ex["out"][out_key].detach().double().numpy()).max())
-        if not d <= 2e-2:
-            bad.append(f"{key}: device vs the exact float64 step {d:.3g} > 2e-2 (backstop)")
-    if not abs(float(o["losses"][4]) - float(ex_l["total"])) <= 2e-2 * abs(float(ex_l["total"])):
-        bad.append("total loss: device vs the exact float64 step beyond 2e-2 relative (backstop)")
-    print(f"config 4 per rank, bf16: worst device / float32-restatements distance ratio {worst:.3g}")
-    assert not bad, "; ".join(bad)
+    dm = [torch.from_numpy(read_debug(eng._last[0], "det_h", i).reshape(NF, w) > 0)
+          for i, w in enumerate((512, 256, 128, 64))] if det_pin else None
+    refs = bf16_step_references(sd, x, y, draws, masks, hm, dm)
+    dev = dict(final=o["final"].cpu().numpy(), probs=o["probs"].cpu().numpy(), total=float(o["losses"][4]),
+               grads={n: gr[eng.slot_offset[i]:eng.slot_offset[i] + eng.slot_numel[i]].astype(np.float64)
+                      for i, n in enumerate(eng.slot_names)})
+    worst = check_bf16_step(dev, refs, masks, hm, draws, label, det_hm=dm)
+    return worst, refs, hm, dm
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
