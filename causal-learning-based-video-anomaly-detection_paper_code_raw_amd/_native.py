@@ -89,6 +89,10 @@ _SIGS = {
     "vad_mlp_tail_forward": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _U64, _U64, _I64, _I, _P, _P, _I64, _P]),
     "vad_mlp_tail_backward": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vad_rows_wgrad": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # the causal head alone (kernel unit tests)
+    "vad_head_scratch_floats": (_I64, [_I, _I]),
+    "vad_head_forward": (_I, [_P, _I, _I, _P, _I, _U64, _U64, _I64] + [_P] * 8 + [_P, _I64, _P]),
+    "vad_head_backward": (_I, [_P, _I, _I, _P, _I, _U64, _U64, _I64] + [_P] * 8 + [_P] * 5 + [_P, _P, _P, _I64, _P]),
     # minicausal (config 1)
     "vad_mc_create": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "vad_mc_destroy": (None, [_P]),

@@ -133,6 +133,39 @@ static const CadLayout& layout() {
   return L;
 }
 
+// The head's arguments on this layout (head.h): the plan and the stand-alone entry points of ops_api.hip both fill
+// HeadArgs here
+HeadArgs cad_head_args(int B, int T, int64_t clip0, int training, uint64_t seed, uint64_t step, const float* params,
+                       float* grads, float* ws, int* iws, float* rows) {
+  const CadLayout& LY = layout();
+  HeadArgs a{};
+  a.B = B;
+  a.T = T;
+  a.clip0 = clip0;
+  a.training = training;
+  a.h1_eps = rng_h1(seed, S_EPS, step);
+  a.h1_drop = rng_h1(seed, S_SCORER_DROP, step);
+  a.thr_drop = drop_threshold(0.2);
+  a.pbase = params;
+  for (int i = 0; i < H_NUM; ++i) a.off[i] = LY.slots[LY.head0 + i].offset;
+  a.head_begin = LY.slots[LY.head0].offset;
+  int64_t numel[H_NUM];
+  for (int i = 0; i < H_NUM; ++i) numel[i] = LY.slots[LY.head0 + i].numel;
+  head_pack_weights(a, numel);  // sizes are fixed by the architecture; checked once in vad_cad_create()
+  a.ws = ws;
+  a.ws_stride = head_ws_floats(T);
+  a.iws = iws;
+  a.iws_stride = head_iws_ints(T);
+  a.rows = rows;
+  a.grad = grads;
+  return a;
+}
+int64_t cad_head_grad_begin() { return layout().slots[layout().head0].offset; }
+int64_t cad_head_slab_len() {
+  const CadLayout& LY = layout();
+  return LY.slots[LY.dir_w[0]].offset - LY.slots[LY.head0].offset;
+}
+
 constexpr int64_t FLAG_FLOATS = 256;  // grad buffer tail: [0] det flag, [1] struct flag (summed under DP)
 
 // ------------------------------------------------------------------ optimizer kernels
@@ -580,7 +613,7 @@ struct CadPlanImpl {
     d_glog = w.take<float>(B * 2);
     d_dlog = w.take<float>(nf * 20);
     const CadLayout& LY = layout();
-    slab_len = LY.slots[LY.dir_w[0]].offset - LY.slots[LY.head0].offset;
+    slab_len = cad_head_slab_len();
     slabs = w.take<float>((int64_t)B * slab_len);
     d_feat_det = w.take<float>(nf * 6144);
     d_pooled = w.take<float>((int64_t)B * 6144);
@@ -617,28 +650,7 @@ struct CadPlanImpl {
   float* RV(int i) const { return bufs + layout().bufs[layout().rv[i]].offset; }
 
   HeadArgs head_args() const {
-    const CadLayout& LY = layout();
-    HeadArgs a{};
-    a.B = B;
-    a.T = T;
-    a.clip0 = clip0;
-    a.training = training;
-    a.h1_eps = rng_h1(seed, S_EPS, step);
-    a.h1_drop = rng_h1(seed, S_SCORER_DROP, step);
-    a.thr_drop = drop_threshold(0.2);
-    a.pbase = params;
-    for (int i = 0; i < H_NUM; ++i) a.off[i] = LY.slots[LY.head0 + i].offset;
-    a.head_begin = LY.slots[LY.head0].offset;
-    int64_t numel[H_NUM];
-    for (int i = 0; i < H_NUM; ++i) numel[i] = LY.slots[LY.head0 + i].numel;
-    head_pack_weights(a, numel);  // sizes are fixed by the architecture; checked once in create()
-    a.ws = head_ws;
-    a.ws_stride = head_ws_floats(T);
-    a.iws = head_iws;
-    a.iws_stride = head_iws_ints(T);
-    a.rows = head_rows;
-    a.grad = grads;
-    return a;
+    return cad_head_args(B, T, clip0, training, seed, step, params, grads, head_ws, head_iws, head_rows);
   }
   HeadOut head_out() const { return HeadOut{causal, kl, z, adj, boxes, counts, nmax, clip_flags}; }
 
@@ -1256,7 +1268,7 @@ struct CadPlanImpl {
     TIMED("det_bwd", rows_wgrad(mlp_wgrad_args(NF, d_dlog, dd, LY.det_w, LY.det_b, dh, ddh, flags), st));
     TIMED("det_bwd", dense_wgrad(ddh[0], NF, 512, feats, 6144, G(LY.det_w[0]), G(LY.det_b[0]), dense_scratch2,
                                  dense_scratch_floats, flags, st));
-    TIMED("head_bwd", head_slab_reduce(slabs, B, slab_len, grads + LY.slots[LY.head0].offset, st));
+    TIMED("head_bwd", head_slab_reduce(slabs, B, slab_len, grads + cad_head_grad_begin(), st));
     TIMED("head_bwd", head_rows_wgrad(head_args(), st));
     return 0;
   }

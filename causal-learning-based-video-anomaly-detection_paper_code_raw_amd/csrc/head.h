@@ -45,6 +45,14 @@ constexpr int HW_LDS = 20480;  // capacity (floats) of the sequence kernels' LDS
 // sets lw_len from a.off and the last slot's size; nonzero if the image does not fit or a slot is not 16-B aligned
 int head_pack_weights(HeadArgs& a, const int64_t* numel);
 
+// HeadArgs of one head call on the cad parameter layout (cad_plan.hip): RNG keys of (seed, step), slot offsets and the
+// LDS image length from the layout, the caller's parameter / gradient buffers and workspaces.  The plan and the
+// stand-alone entry points (ops_api.hip) both fill their arguments here.
+HeadArgs cad_head_args(int B, int T, int64_t clip0, int training, uint64_t seed, uint64_t step, const float* params,
+                       float* grads, float* ws, int* iws, float* rows);
+int64_t cad_head_grad_begin();  // offset of the first head slot in the flat parameter / gradient buffers
+int64_t cad_head_slab_len();    // floats from there to the first slot after the head: one per-clip gradient slab
+
 int64_t head_ws_floats(int T);
 int64_t head_iws_ints(int T);
 int64_t head_rows_floats(int B, int T);

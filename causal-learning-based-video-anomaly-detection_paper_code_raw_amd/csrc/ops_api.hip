@@ -1,8 +1,11 @@
 // Stand-alone entry points for single building blocks (dense layers, the fused MLP chain, 3x3 conv, the 3-D clip
-// blocks) used by the kernel unit tests.
+// blocks, the causal head) used by the kernel unit tests.
+#include <string>
+
 #include "../../include/vad.h"
 #include "backbone.h"
 #include "conv3d.h"
+#include "head.h"
 #include "mlp.h"
 
 using namespace vad;
@@ -357,4 +360,84 @@ extern "C" int vad_rows_wgrad(int R, int nseg, float* const* dW, float* const* d
   }
   a.skip = skip;
   return rows_wgrad(a, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The causal head alone (head.h): head_fwd, and head_bwd + head_slab_reduce + head_rows_wgrad in the plan's order, on
+// logits the caller chose.  Thin wrappers: HeadArgs comes from cad_head_args, the function the plan fills its own
+// with; rows, per-clip workspaces and gradient slabs are carved from the caller's scratch; they launch nothing of
+// their own.
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct HeadScratch {
+  int64_t rows, ws, iws, slabs, total;
+  HeadScratch(int B, int T) {
+    int64_t o = 0;
+    auto take = [&](int64_t n) { int64_t r = o; o += up(n); return r; };
+    rows = take(head_rows_floats(B, T));
+    ws = take((int64_t)B * head_ws_floats(T));
+    iws = take((int64_t)B * head_iws_ints(T));  // ints, one float's size each
+    slabs = take((int64_t)B * cad_head_slab_len());
+    total = o;
+  }
+};
+
+int head_call(const char* who, int B, int T, int training, const void* logits, const void* params, const float* scratch,
+              int64_t scratch_floats) {
+  const std::string w(who);
+  VAD_CHECK(B >= 1 && T >= 1 && T <= 4096 && (int64_t)B * T * NMAX < (1ll << 24) && (training == 0 || training == 1),
+            w + ": unsupported shape");
+  VAD_CHECK(logits && params, w + ": null argument");
+  VAD_CHECK(scratch && scratch_floats >= HeadScratch(B, T).total, w + ": scratch too small");
+  VAD_CHECK(reinterpret_cast<uintptr_t>(scratch) % 16 == 0 && reinterpret_cast<uintptr_t>(params) % 16 == 0,
+            w + ": params and scratch must be 16-byte aligned");
+  return 0;
+}
+
+HeadArgs head_call_args(int B, int T, int training, uint64_t seed, uint64_t step, int64_t clip0, const float* params,
+                        float* grads, float* scratch) {
+  const HeadScratch s(B, T);
+  return cad_head_args(B, T, clip0, training, seed, step, params, grads, scratch + s.ws,
+                       reinterpret_cast<int*>(scratch + s.iws), scratch + s.rows);
+}
+
+}  // namespace
+
+extern "C" int64_t vad_head_scratch_floats(int B, int T) {
+  if (B < 1 || T < 1 || T > 4096 || (int64_t)B * T * NMAX >= (1ll << 24)) {
+    set_error("vad_head_scratch_floats: unsupported shape");
+    return -1;
+  }
+  return HeadScratch(B, T).total;
+}
+
+extern "C" int vad_head_forward(const float* det_logits, int B, int T, const float* params, int training, uint64_t seed,
+                                uint64_t step, int64_t clip0, float* causal, float* kl, float* z, float* adj,
+                                float* boxes, int* counts, int* nmax, int* clip_flags, float* scratch,
+                                int64_t scratch_floats, void* stream) {
+  VAD_TRY(head_call("vad_head_forward", B, T, training, det_logits, params, scratch, scratch_floats));
+  VAD_CHECK(causal && kl && z && adj && boxes && counts && nmax && clip_flags, "vad_head_forward: null argument");
+  const HeadArgs a = head_call_args(B, T, training, seed, step, clip0, params, nullptr, scratch);
+  return head_fwd(a, det_logits, HeadOut{causal, kl, z, adj, boxes, counts, nmax, clip_flags}, (hipStream_t)stream);
+}
+
+extern "C" int vad_head_backward(const float* det_logits, int B, int T, const float* params, int training,
+                                 uint64_t seed, uint64_t step, int64_t clip0, float* causal, float* kl, float* z,
+                                 float* adj, float* boxes, int* counts, int* nmax, int* clip_flags,
+                                 const float* d_causal, const float* d_kl, const float* d_z, const float* d_adj,
+                                 const float* d_boxes, float* grads, float* d_det_logits, float* scratch,
+                                 int64_t scratch_floats, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  VAD_TRY(head_call("vad_head_backward", B, T, training, det_logits, params, scratch, scratch_floats));
+  VAD_CHECK(causal && kl && z && adj && boxes && counts && nmax && clip_flags && d_causal && d_kl && grads &&
+                d_det_logits,
+            "vad_head_backward: null argument");
+  const HeadArgs a = head_call_args(B, T, training, seed, step, clip0, params, grads, scratch);
+  float* slabs = scratch + HeadScratch(B, T).slabs;
+  const int64_t slab_len = cad_head_slab_len();
+  VAD_TRY(head_bwd(a, det_logits, HeadOut{causal, kl, z, adj, boxes, counts, nmax, clip_flags},
+                   HeadUp{d_causal, d_kl, d_z, d_adj, d_boxes}, slabs, slab_len, d_det_logits, st));
+  VAD_TRY(head_slab_reduce(slabs, B, slab_len, grads + cad_head_grad_begin(), st));
+  return head_rows_wgrad(a, st);
 }

@@ -255,6 +255,27 @@ int vad_mlp_tail_backward(int M, const float* dout, const float* const* W, const
  * host dW, db, A, X, O, I [nseg] */
 int vad_rows_wgrad(int R, int nseg, float* const* dW, float* const* db, const float* const* A, const float* const* X,
                    const int* O, const int* I, const int* skip, void* stream);
+/* The causal head alone (cad:194-502: box decode and compaction, ReID, GRU, VAE + KL, structure learner, dynamics,
+ * scorers) on detector logits [B*T][20] the caller chose, with the arguments the cad plan gives it (kernel unit tests).
+ * params / grads: flat buffers in the cad slot layout (vad_cad_slot_offset; only the head's slots are read / written;
+ * grads has vad_cad_param_floats() floats).  The VAE noise and the scorer dropout are those of vad_cad_forward at
+ * (seed, step, clip0); training = 0: no scorer dropout.  Outputs: causal [B], kl [B], z [B][5][6] (rows >= nmax zero),
+ * adj [B][6][6], boxes [B][T][5][4] (in-range boxes compacted per frame, the fallback box when none), counts [B][T],
+ * nmax [B], clip_flags [B][2] (a detection in range, nmax >= 2).  scratch (16-byte aligned, at least
+ * vad_head_scratch_floats(B, T) floats) carries the forward's state to the backward: same buffer, untouched between.
+ * vad_head_backward: upstream gradients d_causal [B], d_kl [B] and the nullable d_z, d_adj, d_boxes (the outputs'
+ * shapes) -> every head slot of grads (written, not accumulated; the rest of grads is left alone) and
+ * d_det_logits [B*T][20] (zero at every slot that is out of range or in a fallback frame); the forward's outputs are
+ * passed again.  A refused call returns non-zero before anything is queued. */
+int64_t vad_head_scratch_floats(int B, int T);
+int vad_head_forward(const float* det_logits, int B, int T, const float* params, int training, uint64_t seed,
+                     uint64_t step, int64_t clip0, float* causal, float* kl, float* z, float* adj, float* boxes,
+                     int* counts, int* nmax, int* clip_flags, float* scratch, int64_t scratch_floats, void* stream);
+int vad_head_backward(const float* det_logits, int B, int T, const float* params, int training, uint64_t seed,
+                      uint64_t step, int64_t clip0, float* causal, float* kl, float* z, float* adj, float* boxes,
+                      int* counts, int* nmax, int* clip_flags, const float* d_causal, const float* d_kl,
+                      const float* d_z, const float* d_adj, const float* d_boxes, float* grads, float* d_det_logits,
+                      float* scratch, int64_t scratch_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * minicausal_vad_complete3.py — SimpleVideoAnomalyDetector (mc:25-102) + StableTrainer step (mc:249-330)

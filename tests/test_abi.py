@@ -155,3 +155,40 @@ def test_dense_and_mlp_entry_points_refuse_before_any_launch():
     assert b"vad_mlp_tail_backward: unsupported shape" in L.vad_last_error()
     assert L.vad_dense_forward_ex(None, 4, 8, None, None, 4, None, 1, 1.0, 0, 0, 0, 0, 0, None, 0, None) != 0
     assert b"vad_dense_forward_ex: unsupported shape" in L.vad_last_error()
+
+
+def test_head_entry_points_refuse_before_any_launch():
+    """vad_head_forward / vad_head_backward check shape, pointers, scratch size and alignment on the host, before
+    anything is queued: a refused call returns non-zero with a text and needs no device."""
+    from vad_amd import _native
+    L = _native.lib()
+    need = L.vad_head_scratch_floats(2, 3)
+    names = [L.vad_cad_slot_name(i).decode() for i in range(L.vad_cad_num_slots())]
+    slab = (L.vad_cad_slot_offset(names.index("direct_classifier.0.weight"))  # the first slot after the head
+            - L.vad_cad_slot_offset(names.index("tracker.reid_net.0.weight")))
+    assert need >= 2 * slab + 2 * 3 * 5 * (192 * 3 + 68) and L.vad_head_scratch_floats(3, 3) > need
+    for B, T in [(0, 3), (2, 0), (2, 4097)]:
+        assert L.vad_head_scratch_floats(B, T) < 0
+        assert b"vad_head_scratch_floats: unsupported shape" in L.vad_last_error()
+    buf = (ctypes.c_float * 64)()
+    a = ctypes.addressof(buf)
+    a += -a % 16
+    outs = [a] * 8
+    fwd = lambda B, T, training, lg, par, scr, n: L.vad_head_forward(lg, B, T, par, training, 0, 0, 0, *outs, scr, n, None)
+    bwd = lambda B, T, training, lg, par, scr, n, o=outs, g=a: L.vad_head_backward(
+        lg, B, T, par, training, 0, 0, 0, *o, a, a, None, None, None, g, a, scr, n, None)
+    for who, f in ((b"vad_head_forward", fwd), (b"vad_head_backward", bwd)):
+        for args, text in [((0, 3, 1, a, a, a, need), b": unsupported shape"),
+                           ((2, 4097, 1, a, a, a, need), b": unsupported shape"),
+                           ((2, 3, 2, a, a, a, need), b": unsupported shape"),
+                           ((2, 3, 1, None, a, a, need), b": null argument"),
+                           ((2, 3, 1, a, None, a, need), b": null argument"),
+                           ((2, 3, 1, a, a, None, need), b": scratch too small"),
+                           ((2, 3, 1, a, a, a, need - 1), b": scratch too small"),
+                           ((2, 3, 1, a, a, a + 4, need), b": params and scratch must be 16-byte aligned")]:
+            assert f(*args) != 0
+            assert who + text in L.vad_last_error(), (args, L.vad_last_error())
+    assert L.vad_head_forward(a, 2, 3, a, 1, 0, 0, 0, *([a] * 7 + [None]), a, need, None) != 0
+    assert b"vad_head_forward: null argument" in L.vad_last_error()
+    assert bwd(2, 3, 1, a, a, a, need, g=None) != 0
+    assert b"vad_head_backward: null argument" in L.vad_last_error()
