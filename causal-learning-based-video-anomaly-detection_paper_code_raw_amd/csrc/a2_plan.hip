@@ -8,7 +8,7 @@
 //   backward  loss + head backward in the same block-wide style (weight grads as fixed-order sums over the batch),
 //             fc weight / input grads as GEMMs, avg-pool backward, then per stage ReLU gate -> weight+bias grad GEMM
 //             over the saved columns -> input grad GEMM + col2im
-//   update    clip_grad_norm_(0.5) (norm of per-parameter norms) -> AdamW (decoupled weight decay)
+//   update    clip_grad_norm_(0.5) (norm of per-parameter norms) -> AdamW (decoupled weight decay) (optim.h)
 // losses[]: 0 total, 1 anomaly(focal), 2 acyclicity, 3 sparsity, 4 consistency, 5 structure, 6 edge_count,
 //           7 sparsity_ratio, 8 grad total norm, 9 status (0 skipped: NaN loss, 2 stepped)
 #include <cmath>
@@ -18,6 +18,7 @@
 #include "../../include/vad.h"
 #include "backbone.h"
 #include "conv3d.h"
+#include "optim.h"
 #include "plan_util.h"
 
 namespace vad {
@@ -755,70 +756,6 @@ static int relu_gate(float* d, const float* y, int64_t n, hipStream_t st) {
   return 0;
 }
 
-// ------------------------------------------------------------------ AdamW with clip_grad_norm_(max_norm)
-struct A2SlotTab {
-  int64_t off[A2_NSLOT], numel[A2_NSLOT];
-};
-// per-slot squared sums in A2_SQ_CHUNKS fixed strided parts (block (slot, part)); a2_opt_prepare adds the parts in
-// order and takes each slot's norm (torch's per-tensor norm, then the norm of norms)
-constexpr int A2_SQ_CHUNKS = 16;
-__global__ __launch_bounds__(256) void a2_sqsum_kernel(const float* __restrict__ g, A2SlotTab t, double* sqp) {
-  const int s = blockIdx.x;
-  __shared__ double red[256];
-  double acc = 0.0;
-  for (int64_t i = blockIdx.y * 256ll + threadIdx.x; i < t.numel[s]; i += 256ll * A2_SQ_CHUNKS) {
-    const float v = g[t.off[s] + i];
-    acc += (double)v * (double)v;
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sqp[s * A2_SQ_CHUNKS + blockIdx.y] = red[0];
-}
-// ctrl: [0] step?, [1] clip coefficient, [2] -lr/bc1, [3] sqrt(bc2), [4] 1 - lr*wd
-__global__ void a2_opt_prepare_kernel(const double* sqp, float* losses, int32_t* steps, float lr, float b1, float b2,
-                                      float wd, float max_norm, float* ctrl, float* user_losses) {
-  if (threadIdx.x != 0) return;
-  ctrl[0] = 0.f;
-  if (losses[9] < 1.f) return;
-  double tot = 0.0;
-  for (int s = 0; s < A2_NSLOT; ++s) {
-    double q = 0.0;
-    for (int c = 0; c < A2_SQ_CHUNKS; ++c) q += sqp[s * A2_SQ_CHUNKS + c];
-    const float nrm = (float)sqrt(q);
-    tot += (double)nrm * (double)nrm;
-  }
-  const float total = (float)sqrt(tot);
-  losses[8] = total;
-  if (user_losses) user_losses[8] = total;
-  ctrl[1] = fminf(1.f, max_norm / (total + 1e-6f));
-  const int step = steps[0] + 1;
-  for (int s = 0; s < A2_NSLOT; ++s) steps[s] = step;
-  const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-  ctrl[2] = (float)(-(double)lr / bc1);
-  ctrl[3] = (float)sqrt(bc2);
-  ctrl[4] = (float)(1.0 - (double)lr * (double)wd);
-  ctrl[0] = 1.f;
-}
-__global__ __launch_bounds__(256) void a2_adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                       const float* ctrl, float b1, float b2, float eps) {
-  if (ctrl[0] == 0.f) return;
-  const float coef = ctrl[1], step_size = ctrl[2], bc2s = ctrl[3], decay = ctrl[4];
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float gv = g[i] * coef;
-    const float pv = p[i] * decay;  // param.mul_(1 - lr * weight_decay)
-    const float mv = m[i] + (1.f - b1) * (gv - m[i]);
-    const float vv = fmaf(v[i], b2, (1.f - b2) * gv * gv);
-    m[i] = mv;
-    v[i] = vv;
-    p[i] = fmaf(step_size, mv / (sqrtf(vv) / bc2s + eps), pv);
-  }
-}
-
 // ------------------------------------------------------------------ the plan
 struct A2PlanImpl {
   int B, T, H, W;
@@ -828,8 +765,8 @@ struct A2PlanImpl {
   int32_t* steps = nullptr;
   float *cols[3], *y[3], *pooled, *f, *hc0, *sig, *adj, *g1, *g1d, *g2, *cat, *hp0, *s, *losses, *pseudo, *d_s,
       *d_adj, *red, *pairs, *lsc, *dz_ap2, *dz_ap0, *dg2, *dz_ge0, *dz_cn2, *dz_cn0, *dfeat, *dpooled, *dA, *dcols,
-      *scratch, *ctrl;
-  double* sqp;
+      *scratch;
+  AdamWs aws{};
   int64_t* off_dev;
   float* xin = nullptr;  // (a2_direct) the forward's clip, kept for conv3d_1's weight gradient
   const float* xsrc = nullptr;  // the clip conv3d_1 reads: xin, or the caller's x itself with option borrow_input
@@ -901,8 +838,7 @@ struct A2PlanImpl {
     dcols = w.take<float>(max_dcols);
     scratch_floats = 8ll << 20;
     scratch = w.take<float>(scratch_floats);
-    sqp = w.take<double>(A2_NSLOT * A2_SQ_CHUNKS);
-    ctrl = w.take<float>(8);
+    aws.carve(w);
     off_dev = w.take<int64_t>(A2_NSLOT);
   }
 
@@ -1098,21 +1034,12 @@ struct A2PlanImpl {
 
   int optimizer(float lr, float b1, float b2, float eps, float wd, float max_norm, hipStream_t st,
                 float* user_losses = nullptr) {
-    A2SlotTab t{};
-    for (int i = 0; i < A2_NSLOT; ++i) {
-      t.off[i] = a2_offsets().off[i];
-      t.numel[i] = A2_SLOTS[i].numel;
-    }
-    hipLaunchKernelGGL(a2_sqsum_kernel, dim3(A2_NSLOT, A2_SQ_CHUNKS), dim3(256), 0, st, grads, t, sqp);
-    VAD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(a2_opt_prepare_kernel, dim3(1), dim3(64), 0, st, sqp, losses, steps, lr, b1, b2, wd,
-                       max_norm, ctrl, user_losses);
-    VAD_LAUNCH_CHECK();
-    const int64_t n = a2_offsets().total;
-    hipLaunchKernelGGL(a2_adamw_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 1024)), dim3(256), 0, st,
-                       params, grads, m, v, n, ctrl, b1, b2, eps);
-    VAD_LAUNCH_CHECK();
-    return 0;
+    const AdamSlots t = adam_slots(A2_NSLOT, [](int i) { return a2_offsets().off[i]; },
+                                   [](int i) { return A2_SLOTS[i].numel; });
+    // AdamW, clipped on every step, no finiteness gate and no status: only the norm, losses[8], is written
+    const AdamStep a{lr, b1, b2, eps, wd, true, -1.f, max_norm, 1.f, losses + 9, losses + 8,
+                     user_losses ? user_losses + 8 : nullptr, nullptr, nullptr};
+    return adam_clip_step(t, params, grads, m, v, a2_offsets().total, steps, aws, a, st);
   }
 };
 

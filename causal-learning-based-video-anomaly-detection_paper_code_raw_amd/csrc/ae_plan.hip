@@ -915,10 +915,8 @@ struct AePlanImpl {
     scratch = w.take<float>(scratch_floats);
     if (side) scratch2 = w.take<float>(scratch_floats);
     bad = w.take<int>(4);
-    aws.sq = w.take<double>(ADAM_MAX_SLOTS * ADAM_SQ_CHUNKS);
-    aws.bad = w.take<int>(ADAM_MAX_SLOTS * ADAM_SQ_CHUNKS);
     sum_parts = w.take<double>(AE_SUM_BLOCKS);
-    aws.ctrl = w.take<float>(4);
+    aws.carve(w);
   }
 
   // train-mode statistics (+ running stats) or eval-mode affine, then A = LeakyReLU(BN(y))
@@ -1184,16 +1182,13 @@ struct AePlanImpl {
 
   int optimizer(float lr, float b1, float b2, float eps, float wd, float max_norm, float grad_scale, hipStream_t st) {
     const AeLayout& L = ae_layout();
-    AdamSlots t{};
-    t.n = (int)L.slots.size();
-    VAD_CHECK(t.n <= ADAM_MAX_SLOTS, "vad_ae_optimizer_step: slot table overflow");
-    for (int i = 0; i < t.n; ++i) {
-      t.off[i] = L.slots[i].offset;
-      t.numel[i] = L.slots[i].numel;
-    }
-    // clip_grad_norm_(max_norm) on every step (cad1:424): clip_above < 0
-    return adam_clip_step(t, params, grads, m, v, L.param_floats, steps, losses, aws, lr, b1, b2, eps, wd, -1.f,
-                          max_norm, grad_scale, st);
+    const AdamSlots t = adam_slots((int)L.slots.size(), [&](int i) { return L.slots[i].offset; },
+                                   [&](int i) { return L.slots[i].numel; });
+    // coupled decay; clip_grad_norm_(max_norm) on every step (cad1:424): clip_above < 0; losses[1] norm, [2] clipped,
+    // [3] the status word
+    const AdamStep a{lr, b1, b2, eps, wd, false, -1.f, max_norm, grad_scale, losses + 3, losses + 1, nullptr,
+                     losses + 2, losses + 3};
+    return adam_clip_step(t, params, grads, m, v, L.param_floats, steps, aws, a, st);
   }
 };
 

@@ -7,8 +7,8 @@
 //   backward  classifier kernel (BCE/sigmoid/ReLU/dropout backward, classifier weight grads over the batch)
 //             -> avg-pool backward -> per stage: MaxPool3d gather backward -> BN3d backward (reduce / finalize /
 //             apply) -> weight+bias grad GEMM over the saved im2col columns -> input-grad GEMM + col2im
-//   update    per-slot squared norms (float64) and finiteness -> grad norm, clip to max_norm only when the norm
-//             exceeds clip_above (mc:304-306) -> Adam with coupled L2 weight decay (torch.optim.Adam semantics)
+//   update    (optim.h) per-slot squared norms (float64) and finiteness -> grad norm, clip to max_norm only when the
+//             norm exceeds clip_above (mc:304-306) -> Adam with coupled L2 weight decay (torch.optim.Adam semantics)
 // Status word (losses[3]): 0 = skipped before backward (non-finite outputs or loss, mc:281-291), 1 = counted but
 // not stepped (non-finite grads: zero_grad() then a no-op step, mc:296-301), 2 = stepped.
 #include <cmath>
@@ -18,6 +18,7 @@
 #include "../../include/vad.h"
 #include "backbone.h"
 #include "conv3d.h"
+#include "optim.h"
 #include "plan_util.h"
 
 namespace vad {
@@ -221,90 +222,6 @@ __global__ __launch_bounds__(256) void mc_head_bwd_kernel(McHeadBwdArgs a) {
   }
 }
 
-// ------------------------------------------------------------------ update
-struct McSlotTab {
-  int n;
-  int64_t off[24], numel[24];
-};
-
-__global__ __launch_bounds__(256) void mc_sqsum_kernel(const float* __restrict__ g, McSlotTab t, double* sq,
-                                                       int* bad) {
-  const int s = blockIdx.x;
-  __shared__ double red[256];
-  __shared__ int rb[256];
-  double acc = 0.0;
-  int nf = 0;
-  for (int64_t i = threadIdx.x; i < t.numel[s]; i += 256) {
-    const float v = g[t.off[s] + i];
-    if (!isfinite(v)) nf = 1;
-    acc += (double)v * (double)v;
-  }
-  red[threadIdx.x] = acc;
-  rb[threadIdx.x] = nf;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if (threadIdx.x < k) {
-      red[threadIdx.x] += red[threadIdx.x + k];
-      rb[threadIdx.x] |= rb[threadIdx.x + k];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    sq[s] = red[0];
-    bad[s] = rb[0];
-  }
-}
-
-// ctrl: [0] step? (1/0), [1] clip coefficient, [2] -lr / bias_correction1, [3] sqrt(bias_correction2)
-__global__ void mc_opt_prepare_kernel(const double* sq, const int* bad, int n, float* losses, int32_t* steps,
-                                      float lr, float b1, float b2, float clip_above, float max_norm, float* ctrl) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  ctrl[0] = 0.f;
-  ctrl[1] = 1.f;
-  if (losses[3] < 1.f) return;  // skipped before backward
-  double tot = 0.0;
-  int nonfin = 0;
-  for (int s = 0; s < n; ++s) {
-    tot += (double)(float)sqrt(sq[s]) * (double)(float)sqrt(sq[s]);  // host sum of per-param norm**2 (mc:302)
-    nonfin |= bad[s];
-  }
-  if (nonfin) {
-    losses[3] = 1.f;
-    return;
-  }
-  const double gn = sqrt(tot);
-  losses[1] = (float)gn;
-  if (gn > (double)clip_above) {
-    // clip_grad_norm_(params, max_norm): total = ||(||g_p||)||, coef = max_norm / (total + 1e-6), clamped to 1
-    const float total = (float)gn;
-    ctrl[1] = fminf(1.f, max_norm / (total + 1e-6f));
-    losses[2] = 1.f;
-  }
-  const int step = steps[0] + 1;
-  for (int s = 0; s < n; ++s) steps[s] = step;
-  const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-  ctrl[0] = 1.f;
-  ctrl[2] = (float)(-(double)lr / bc1);
-  ctrl[3] = (float)sqrt(bc2);
-  losses[3] = 2.f;
-}
-
-__global__ __launch_bounds__(256) void mc_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                      float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                      const float* ctrl, float b1, float b2, float eps, float wd) {
-  if (ctrl[0] == 0.f) return;
-  const float coef = ctrl[1], step_size = ctrl[2], bc2s = ctrl[3];
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float pv = p[i];
-    const float gv = fmaf(wd, pv, g[i] * coef);            // grad.add(param, alpha=wd) after clipping
-    const float mv = m[i] + (1.f - b1) * (gv - m[i]);       // exp_avg.lerp_(grad, 1 - beta1)
-    const float vv = fmaf(v[i], b2, (1.f - b2) * gv * gv);  // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
-    m[i] = mv;
-    v[i] = vv;
-    p[i] = fmaf(step_size, mv / (sqrtf(vv) / bc2s + eps), pv);
-  }
-}
-
 __global__ void mc_nbt_kernel(int64_t* nbt, int n) {
   if (threadIdx.x < n) nbt[threadIdx.x] += 1;
 }
@@ -322,9 +239,8 @@ struct McPlanImpl {
   // workspace
   float *cols[3], *y[3], *pooled[3], *stats[3], *wf[3], *wd[3], *xin;
   float *parts, *bparts, *feats, *fd, *h1, *h1d, *h2, *o, *dz1, *dz2, *dz3, *dfeat, *dpool, *dA, *dY, *dcols;
-  float *scratch, *labels_copy, *losses, *ctrl;
-  double* sq;
-  int* bad;
+  float *scratch, *labels_copy, *losses;
+  AdamWs aws{};
   int32_t* flags = nullptr;
   int64_t parts_floats = 0, scratch_floats = 0;
   // per-call state
@@ -390,9 +306,7 @@ struct McPlanImpl {
     scratch = w.take<float>(scratch_floats);
     labels_copy = w.take<float>(B);
     losses = w.take<float>(4);
-    ctrl = w.take<float>(4);
-    sq = w.take<double>(32);
-    bad = w.take<int>(32);
+    aws.carve(w);
   }
 
   McHeadArgs head_args() const {
@@ -500,23 +414,12 @@ struct McPlanImpl {
   }
 
   int optimizer(float lr, float b1, float b2, float eps, float wd, float clip_above, float max_norm, hipStream_t st) {
-    McSlotTab t{};
-    t.n = (int)LY.slots.size();
-    VAD_CHECK(t.n <= 24, "mc optimizer: slot table overflow");
-    for (int i = 0; i < t.n; ++i) {
-      t.off[i] = LY.slots[i].offset;
-      t.numel[i] = LY.slots[i].numel;
-    }
-    hipLaunchKernelGGL(mc_sqsum_kernel, dim3(t.n), dim3(256), 0, st, grads, t, sq, bad);
-    VAD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mc_opt_prepare_kernel, dim3(1), dim3(64), 0, st, sq, bad, t.n, losses, steps, lr, b1, b2,
-                       clip_above, max_norm, ctrl);
-    VAD_LAUNCH_CHECK();
-    const int64_t n = LY.param_floats;
-    hipLaunchKernelGGL(mc_adam_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 1024)), dim3(256), 0, st,
-                       params, grads, m, v, n, ctrl, b1, b2, eps, wd);
-    VAD_LAUNCH_CHECK();
-    return 0;
+    const AdamSlots t = adam_slots((int)LY.slots.size(), [&](int i) { return LY.slots[i].offset; },
+                                   [&](int i) { return LY.slots[i].numel; });
+    // coupled decay; the clip only above clip_above (mc:304-306); losses[1] norm, [2] clipped, [3] the status word
+    const AdamStep a{lr, b1, b2, eps, wd, false, clip_above, max_norm, 1.f, losses + 3, losses + 1, nullptr,
+                     losses + 2, losses + 3};
+    return adam_clip_step(t, params, grads, m, v, LY.param_floats, steps, aws, a, st);
   }
 };
 

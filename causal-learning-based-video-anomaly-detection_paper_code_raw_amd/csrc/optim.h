@@ -1,12 +1,11 @@
-// torch.optim.Adam (coupled L2 weight decay) behind a finiteness-gated, optionally norm-gated clip_grad_norm_, over
-// one flat parameter / grad / moment buffer split into slots (= named_parameters()).  Used by the cad1 memory
-// autoencoder's train step (cad1:413-425); the minicausal plan carries the same sequence inline (mc_plan.hip).
-//
-// Status word (status[3], float): < 1 on entry = the step was skipped before backward (nothing happens); on exit
-// 1 = non-finite grads (no step: the reference's skip), 2 = stepped.  status[1] = grad norm sqrt(sum_p ||g_p||^2)
-// (per-slot norms rounded to float, summed in double, as torch's clip_grad_norm_), status[2] = 1 when clipped.
+// The slot-wise Adam step of the minicausal, a2 and cad1-autoencoder plans: clip_grad_norm_ (norm of the per-slot
+// norms: each rounded to float, summed in double, as torch), then torch.optim.Adam (coupled L2 decay) or AdamW
+// (decoupled) over one flat parameter / grad / moment buffer split into slots (= named_parameters()).  What differs
+// between the plans is data (AdamStep), not code.  (cad's optimizer, with slot groups and weight images, is its own:
+// cad_plan.hip.)
 #pragma once
 #include "common.h"
+#include "plan_util.h"
 
 namespace vad {
 
@@ -18,17 +17,46 @@ struct AdamSlots {
   int64_t off[ADAM_MAX_SLOTS], numel[ADAM_MAX_SLOTS];
 };
 
+// the table of a plan's n slots: off(i), numel(i) in floats (n above the cap is refused by adam_clip_step)
+template <class Off, class Numel>
+AdamSlots adam_slots(int n, Off off, Numel numel) {
+  AdamSlots t{};
+  t.n = n;
+  for (int i = 0; i < n && i < ADAM_MAX_SLOTS; ++i) {
+    t.off[i] = off(i);
+    t.numel[i] = numel(i);
+  }
+  return t;
+}
+
 struct AdamWs {
   double* sq;   // [ADAM_MAX_SLOTS][ADAM_SQ_CHUNKS]
   int* bad;     // [ADAM_MAX_SLOTS][ADAM_SQ_CHUNKS]
-  float* ctrl;  // [4]
+  float* ctrl;  // [8], five used
+  void carve(Ws& w) {
+    sq = w.take<double>(ADAM_MAX_SLOTS * ADAM_SQ_CHUNKS);
+    bad = w.take<int>(ADAM_MAX_SLOTS * ADAM_SQ_CHUNKS);
+    ctrl = w.take<float>(8);
+  }
 };
 
-// clip_grad_norm_(max_norm) only when norm > clip_above (clip_above < 0: always, plain torch semantics), then Adam
-// (lr, betas, eps, coupled weight_decay) over params[0, nfloats); steps: int32 per slot (torch per-param counters).
-// grad_scale multiplies the grads first (1/world after a data-parallel sum).
+// One step's hyperparameters and the device words it reads and writes.
+struct AdamStep {
+  float lr, b1, b2, eps, wd;
+  bool decoupled;    // AdamW: param *= 1 - lr * wd; otherwise wd * param joins the clipped grad
+  float clip_above;  // clip only when the norm exceeds it; < 0: always (plain clip_grad_norm_)
+  float max_norm;
+  float grad_scale;  // multiplies the grads first (1/world after a data-parallel sum)
+  const float* gate;  // < 1 on entry: the step was skipped before backward, nothing happens
+  float* norm;        // <- grad norm sqrt(sum_p ||g_p||^2)
+  float* norm_host;   // nullable: a second place for the norm (device-visible host memory)
+  float* clipped;     // nullable: <- 1 when clipped, else 0
+  float* status;      // nullable: non-finite grads skip the step (the reference's skip) and leave 1 here, a step 2;
+                      // null: no finiteness gate
+};
+
+// steps: int32 per slot (torch's per-param counters)
 int adam_clip_step(const AdamSlots& t, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                   int64_t nfloats, int32_t* steps, float* status, const AdamWs& w, float lr, float b1, float b2,
-                   float eps, float wd, float clip_above, float max_norm, float grad_scale, hipStream_t st);
+                   int64_t nfloats, int32_t* steps, const AdamWs& w, const AdamStep& a, hipStream_t st);
 
 }  // namespace vad
