@@ -70,6 +70,8 @@ _SIGS = {
     "vad_cad_profile_read": (_I, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I), _I]),
     "vad_cad_profile_marks": (_I, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _I]),
     "vad_set_tuning": (_I, [ctypes.c_char_p, _I]),
+    "vad_get_tuning": (_I, [ctypes.c_char_p, ctypes.POINTER(_I)]),
+    "vad_tuning_name": (ctypes.c_char_p, [_I]),
     "vad_conv3x3_wgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I64, _P]),
     "vad_bn_bwd_apply": (_I, [_P, _P, _P, _I, _I, _P, _I, _P]),
     # 3-D building blocks (kernel unit tests)

@@ -23,9 +23,6 @@
 
 namespace vad {
 
-int g_a2_head_clip = 1;  // knob "a2_head_clip": the head forward / backward one block per clip (0: one launch per layer)
-int g_a2_direct = 1;  // knob "a2_direct": conv3d_1 direct on the VALU (latched per plan; 0: im2col + GEMM)
-
 constexpr int A2_NSLOT = 20;
 constexpr int A2_CO[3] = {16, 32, 64};
 constexpr int A2_MAXB = 256;

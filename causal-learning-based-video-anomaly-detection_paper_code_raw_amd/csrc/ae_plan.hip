@@ -43,11 +43,6 @@
 
 namespace vad {
 
-int g_ae_direct = 1;  // knob "ae_direct" (latched per plan)
-// knob "ae_wgrad_stream" (latched per plan, direct mode): the backward's weight gradients run on a low-priority stream
-// of the plan beside the input-gradient chain, on their own split-K scratch, with dY alternating between two buffers
-int g_ae_wgrad_stream = 1;
-
 constexpr int AE_HW = 64;  // frame side: the encoder's Linear(128 * 4 * 4) fixes 64x64 frames (cad1:151)
 constexpr int AE_PIX = AE_HW * AE_HW;
 constexpr int AE_CHUNKS = AE_PIX / 256;
@@ -58,8 +53,9 @@ constexpr int AE_MEM = 500;  // memory_size (cad1:191-193)
 constexpr float AE_SLOPE = 0.1f;
 constexpr int AE_ST = 8;  // floats per channel of one BN group's stats block
 constexpr int AE_NBN = 7;
-int g_ae_wgrad_blocks = 1024;  // knob "ae_wgrad_blocks": split-K target grid of the implicit-GEMM weight gradients
-                               // (sweep: 1024 3.149, 2048 3.206, 4096 3.202 ms, profiles/r05_cad1_direct.json)
+// split-K target grid of the implicit-GEMM weight gradients (sweep: 1024 3.149, 2048 3.206, 4096 3.202 ms,
+// profiles/r05_cad1_direct.json)
+constexpr int AE_WGRAD_BLOCKS = 1024;
 constexpr int ENC_CI[4] = {1, 32, 64, 128}, ENC_CO[4] = {32, 64, 128, 128}, ENC_IN[4] = {64, 32, 16, 8};
 constexpr int DEC_CI[4] = {128, 128, 64, 32}, DEC_CO[4] = {128, 64, 32, 1}, DEC_IN[4] = {4, 8, 16, 32};
 
@@ -1098,7 +1094,7 @@ struct AePlanImpl {
         int ns = 0;
         VAD_TRY(fork(st, &ws));
         VAD_TRY(conv4_wgrad(dx[j], Ci, dcur, DEC_CO[j], B, DEC_IN[j], DEC_IN[j], scr2, &ns, scratch_floats,
-                            g_ae_wgrad_blocks, ws));
+                            AE_WGRAD_BLOCKS, ws));
         VAD_TRY(conv4_wgrad_reduce(scr2, ns, Ci, DEC_CO[j], G(L.dec_w[j]), ws));
         VAD_TRY(wg_mark(kb));
         VAD_TRY(conv4_fwd(dcur, B, 2 * DEC_IN[j], 2 * DEC_IN[j], DEC_CO[j], dwk[j], nullptr, Ci, bufA, st, scratch,
@@ -1162,7 +1158,7 @@ struct AePlanImpl {
         VAD_CHECK(dY != nullptr, "vad_ae_backward: stream wait failed");
         VAD_TRY(bn_bwd(bufA, ey[l], enc_bn(l), L.ebn_w[l], L.ebn_b[l], est[l], dY, G(L.enc_b[l]), st, kb));
         VAD_TRY(fork(st, &ws));
-        VAD_TRY(conv4_wgrad(dY, Co, ea[l - 1], ENC_CI[l], NF, OH, OH, scr2, &ns, scratch_floats, g_ae_wgrad_blocks,
+        VAD_TRY(conv4_wgrad(dY, Co, ea[l - 1], ENC_CI[l], NF, OH, OH, scr2, &ns, scratch_floats, AE_WGRAD_BLOCKS,
                             ws));
         VAD_TRY(conv4_wgrad_reduce(scr2, ns, Co, ENC_CI[l], G(L.enc_w[l]), ws));
         VAD_TRY(wg_mark(kb));

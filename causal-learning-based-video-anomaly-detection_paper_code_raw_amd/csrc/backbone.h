@@ -2,6 +2,7 @@
 // shared dense-layer GEMMs.  All tensors are fp32, activations NHWC, frames folded into the batch axis.
 #pragma once
 #include "common.h"
+#include "tuning.h"
 #include "weight_images.h"
 
 namespace vad {
@@ -13,16 +14,6 @@ int conv1_num_parts(int NF, int OH);
 // frozen-stem forward without the conv1 activation (stem.hip): conv1 + bias, its BN partial sums ([P][64], the
 // conv1_fwd layout and P) and the 3x3/s2 pooling of the RAW output (max where gamma >= 0, min where gamma < 0);
 // the consumer applies bn1+ReLU on load (exact: the affine+ReLU is monotone per channel)
-extern int g_x3_dgrad_blocks;  // knob "conv_dgrad_blocks"
-extern int g_x3_big;  // knob "conv_split_big"
-extern int g_x3_pipe;  // knob "conv_split_pipe"
-extern int g_x3_s2big;  // knob "conv_split_s2big"
-extern int g_cad_dir_affine;  // knob "cad_dir_affine": the direct classifier's loss-mode backward precomputed in the forward
-extern int g_cad_stem_early;
-extern int g_cad_prep_stream, g_cad_wgrad_stream, g_cad_det_gate, g_cad_last_wgrad_main, g_cad_event_sysfence,
-    g_cad_dy_per_layer, g_cad_l0_slab, g_cad_stream_prio;  // knobs "cad_prep_stream", "cad_wgrad_stream" (A/B)
-extern int g_cad_opt_images;  // knob "cad_opt_images" (A/B of the plan option opt_images)
-extern int g_stem_fused;  // knob "stem_fused" (default 1)
 bool stem_fused_ok(int OW);  // conv1 output width the fused stem handles
 int stem_fused(const float* x, int NF, int H, int W, const float* w, const float* b, const float* gamma, int OH,
                int OW, float* pool, int HP, int WP, float* partials, int* nparts, hipStream_t st);
@@ -106,18 +97,13 @@ int conv3_dgrad(const Conv3Layer& L, const float* dY, const float* wd, float* dX
                 const BnBwdFuse* f = nullptr, const __bf16* w3 = nullptr);
 // direct LDS-patch kernels (conv_patch.hip) for stride-1 layers; conv3_fwd / conv3_dgrad route there by default
 bool conv3_patch_supported(const Conv3Layer& L, bool fwd);
-extern int g_patch_persist;  // single-chunk (C == 32) stride-1 layers on the persistent patch kernel
 int64_t conv3_patch_blocks(int NF, int OH, int OW);  // BN partial blocks of a patch forward
 int conv3_patch_fwd(const Conv3Layer& L, const float* src, const float* src_stats, const float* wf, const float* bias,
                     float* y, float* partials, int* nparts, hipStream_t st);
 int conv3_patch_dgrad(const Conv3Layer& L, const float* dY, const float* wd, float* dX, hipStream_t st);
 // split-bf16 patch kernels (conv_x3.hip): fp32 operands as three bf16 planes, six bf16 MFMA products per K step
-extern int g_conv_split;  // 0 disables them (f32 MFMA patch kernels)
-extern int g_x3_nt;       // output channels per block: 0 auto, 1 -> 32, 2 -> 64
-extern int g_x3_wres;     // 32-channel stride-1 layers: all split weights resident in LDS (1, default) or restaged
 // bf16-operand mode of the split kernels (one plane, one bf16 product per K step, fp32 accumulation): BASELINE
 // config 4's bf16 compute.  Thread-local, set for the duration of a plan call by ConvPrecision.
-extern thread_local int g_conv_bf16;
 struct ConvPrecision {
   int saved;
   explicit ConvPrecision(int bf16) : saved(g_conv_bf16) { g_conv_bf16 = bf16; }
@@ -127,7 +113,6 @@ struct ConvPrecision {
 // float* arguments of the launchers below then point at bf16 data). Only with g_conv_bf16 (the split kernels'
 // bf16 instantiations read and write it); BN statistics, partial sums, weights and grads stay fp32. Thread-local,
 // set per plan call by ActStorage.
-extern thread_local int g_act_bf16;
 struct ActStorage {
   int saved;
   explicit ActStorage(int bf16) : saved(g_act_bf16) { g_act_bf16 = bf16; }
@@ -140,23 +125,16 @@ int conv3_x3_dgrad(const Conv3Layer& L, const float* dY, const float* wd, float*
                    const BnBwdFuse* f = nullptr);
 // stride-2 input gradient on the split-bf16 (or, with conv_bf16, bf16) MFMA: parity classes of a 16x16 dX tile
 // sharing one dY patch; Wd in the plain [Ci][9][Co] layout (conv3_prep_weights with classes == 0)
-extern int g_dgrad_s2_x3;  // knob "conv_dgrad_s2_x3"
 bool conv3_x3_dgrad_s2_supported(const Conv3Layer& L);
 // w3 (nullable): the Wd image pre-split into bf16 planes [Ci][9][Co/16][3][16] (conv3_prep_weights_all's w3 image):
 // the weight staging copies it instead of splitting fp32 weights in every block
 int conv3_x3_dgrad_s2(const Conv3Layer& L, const float* dY, const float* wd, float* dX, hipStream_t st,
                       const BnBwdFuse* f = nullptr, const __bf16* w3 = nullptr);
-extern int g_dgrad_s2_w3, g_dgrad_s2_nt;  // knob "conv_dgrad_s2_w3": the plan pre-splits the stride-2 Wd images (1, default)
 bool conv3_dgrad_w3_wanted(const Conv3Layer& L);
-extern int g_wgrad_split;     // stride-1 weight gradients on the split-bf16 kernel (knob "conv_wgrad_split")
-extern int g_wgrad_s1_nt, g_wgrad_s1_nt_blocks, g_wgrad_s1_nt_wide;  // knobs "conv_wgrad_s1_nt", "conv_wgrad_s1_nt_blocks"
-extern int g_wgrad_s2_blocks;  // their target grid size (knob "conv_wgrad_s2_blocks")
-extern int g_wgrad_split_s2;  // stride-2 weight gradients on the split-bf16 kernel (knob "conv_wgrad_split_s2")
 bool conv3_wgrad_x3_supported(const Conv3Layer& L);
 int conv3_wgrad_x3(const Conv3Layer& L, const float* dY, const float* src, const float* src_stats, float* slab,
                    int* nsplit, int64_t partial_cap, int target_blocks, hipStream_t st);
 // fp32 weight gradients (both strides) on the split-bf16 MFMA with transposed LDS fragment reads (conv_x3w.hip)
-extern int g_wgrad_tr, g_wgrad_tr_blocks, g_wgrad_tr_pft;  // knobs "conv_wgrad_tr", "conv_wgrad_tr_blocks", "conv_wgrad_tr_pft"
 bool x3_wgrad_tr_supported(const Conv3Layer& L);
 int x3_wgrad_tr(const Conv3Layer& L, const float* dY, const float* src, const float* src_stats, float* slab,
                 int* nsplit, int64_t partial_cap, int target_blocks, hipStream_t st);
@@ -166,8 +144,6 @@ int conv3_wgrad_patch(const Conv3Layer& L, const float* dY, const float* src, co
 // native bf16 kernels (conv_bf.hip; bf16 operands AND bf16 activation storage, i.e. config 4): forward and stride-1
 // input gradient.  Their weights are the bf16 copies the prep writes behind the fp32 images (when conv_bf16 and
 // act_bf16 are set), so in that mode a wf / wd buffer holds Co*Ci*9 floats + Co*Ci*9 bf16.
-extern int g_bfc, g_bfc_blocks;  // knobs "conv_bfc", "conv_bfc_blocks"
-extern int g_bfc_s2_ni2;         // knob "conv_bfc_s2_ni2"
 bool bfc_supported(const Conv3Layer& L, bool fwd);
 inline const __bf16* conv3_bf16_image(const float* img, const Conv3Layer& L) {
   return reinterpret_cast<const __bf16*>(img + (int64_t)L.Co * L.Ci * 9);
@@ -177,7 +153,6 @@ int bfc_fwd(const Conv3Layer& L, const __bf16* src, const float* src_stats, cons
 int bfc_dgrad(const Conv3Layer& L, const __bf16* dY, const __bf16* wdb, __bf16* dX, hipStream_t st,
               const BnBwdFuse* f);
 // weight gradient (both strides) into split-K slabs [S][Co][9 Ci] (conv3_wgrad_reduce)
-extern int g_bfw_blocks;  // knob "conv_bfw_blocks"
 bool bfc_wgrad_supported(const Conv3Layer& L);
 int bfc_wgrad(const Conv3Layer& L, const __bf16* dY, const __bf16* src, const float* src_stats, float* slab,
               int* nsplit, int64_t partial_cap, hipStream_t st);
@@ -270,9 +245,5 @@ int conv4_c1_tfwd(const float* src, int NF, int SH, int SW, const float* w, cons
                   hipStream_t st);
 int conv4_c1_wgrad(const float* A, const float* src, int NF, int AH, int AW, float* dW, float* slab,
                    int64_t slab_floats, hipStream_t st);
-
-// conv GEMM tuning knobs: conv_fwd_tile / conv_dgrad_tile / conv_wgrad_tile (tile id, -1 = heuristic),
-// conv_wgrad_blocks, conv_wgrad_min_ktiles
-int set_tuning(const char* key, int value);
 
 }  // namespace vad

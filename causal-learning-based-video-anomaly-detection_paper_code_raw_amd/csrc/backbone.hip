@@ -1,31 +1,13 @@
-// Per-frame CNN kernels for gfx950: conv1 (direct, VALU), 3x3 convs (implicit GEMM on f32 MFMA),
-// train-mode BatchNorm forward/backward, max/adaptive-avg pooling, and the dense-layer GEMMs.
+// Per-frame CNN kernels for gfx950: conv1 (f32 MFMA, K = 49) and the stem backward, the 3x3 convs' dispatch and their
+// implicit-GEMM path on f32 MFMA, train-mode BatchNorm forward/backward, max/adaptive-avg pooling, and the dense-layer
+// GEMMs.  The GEMM's launch side is gemm_launch.h; the 4x4 and 3-D stride-2 conv families are conv4.hip / conv3s2.hip.
 // Reference semantics: ResNetBackbone (causal_anomaly_detection.py:110-158), nn.BatchNorm2d train mode,
 // nn.MaxPool2d(3,2,1), nn.AdaptiveAvgPool2d((4,6)), nn.Linear / ReLU / Dropout stacks (cad:167-179, 525-538).
 #include <type_traits>
 
-#include "backbone.h"
-#include "conv3d.h"
-#include "mlp.h"
-#include "gemm.h"
-#include "head.h"
+#include "gemm_launch.h"
 
 namespace vad {
-
-int g_cad_prep_stream = 1;   // knob "cad_prep_stream": weight relayouts on the plan's side stream (A/B measurement)
-int g_cad_last_wgrad_main = 1;  // knob "cad_last_wgrad_main": layer 0's weight gradient on the caller's stream
-int g_cad_event_sysfence = 0;  // knob "cad_event_sysfence": system-scope fence on the plan's stream-order events
-int g_cad_dy_per_layer = 1;  // knob "cad_dy_per_layer" (A/B of the plan option dy_per_layer)
-int g_cad_stem_early = 1;  // knob "cad_stem_early": an armed forward (vad_cad_input_ready) runs its stem early (0: off)
-int g_cad_det_gate = 1;      // knob "cad_det_gate": the backbone backward waits on the device detector gate
-int g_cad_dir_affine = 1;  // knob "cad_dir_affine": direct classifier backward as A + c beta, precomputed in the forward
-int g_cad_wgrad_stream = 1;  // knob "cad_wgrad_stream": backbone weight gradients on their own stream
-// knob "bn_bwd_fuse": the BN-backward reduce in the input gradients' epilogues -- bit 0 the stride-1 kernels, bit 1 the
-// stride-2 one (A/B at config 2: both 1.922 -> 1.893 ms, stride-1 only 1.927 -> 1.922, profiles/r03_bnfuse_ab.json)
-int g_bn_bwd_fuse = 3;
-int g_cad_stream_prio = 1;  // knob "cad_stream_prio" (cad_plan.hip streams(); A/B profiles/r03_prio_ab.json)
-int g_cad_opt_images = 1;  // knob "cad_opt_images": the fused optimizer writes the weight images it invalidates (0: the forward relayouts every time)
-int g_cad_l0_slab = 1;  // knob "cad_l0_slab": layer 0's weight gradient on a split-K slab of its own (no wait for layer 1's)
 
 // =====================================================================================================
 // conv1: 1 -> 32 channels, 7x7, stride 2, pad 3, as a K=49 (padded to 56) GEMM on f32 MFMA.
@@ -656,14 +638,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_v_kernel(const act_t<AB>* __
   }
 }
 
-int g_bn_apply_v = 1;  // knob "bn_apply_v": the streaming apply kernel (0: the 4-channel row loop)
-int g_bn_apply_u = 4;          // knob "bn_apply_u": rows in flight per thread (2, 4, 8)
-int g_bn_apply_blocks = 2048;  // knob "bn_apply_blocks": grid cap (grid-stride beyond it)
-
 int bn_bwd_apply(const float* dA, const float* y, const float* stats, int M, int C, float* dY, float* bias_partials,
                  int* nparts, hipStream_t st) {
   const int P = bn_rows_parts(M, C);
-  if (g_bn_apply_v && !bias_partials && C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0) {
+  if (!bias_partials && C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0) {
     const int U = g_bn_apply_u == 8 ? 8 : (g_bn_apply_u == 2 ? 2 : 4);
     const int rpp = 256 / (C / 8);
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(M, (int64_t)rpp * U), g_bn_apply_blocks));
@@ -864,159 +842,6 @@ int avgpool_bwd(const float* dfeat, const float* dpooled, int B, int T, int H, i
   return 0;
 }
 
-// =====================================================================================================
-// GEMM epilogues
-// =====================================================================================================
-struct EpiConvFwd {  // y = acc + bias (NHWC rows), plus per-block BN partial sums
-  static constexpr int SCRATCH = 2 * 4 * 256;
-  struct Params { float* y; const float* bias; int C; float* partials; };
-  template <class Cfg>
-  static __device__ void apply(const Params& P, f32x16 (&acc)[Cfg::TM][Cfg::TN], int m0, int n0, int wm, int wn,
-                               int lane, int M, int N, float* lds) {
-    float s1[Cfg::TN], s2[Cfg::TN];
-#pragma unroll
-    for (int j = 0; j < Cfg::TN; ++j) {
-      s1[j] = s2[j] = 0.f;
-      const int col = n0 + acc_col<Cfg>(wn, j, lane);
-      const float bj = col < N ? P.bias[col] : 0.f;
-#pragma unroll
-      for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + acc_row<Cfg>(wm, i, r, lane);
-          if (row < M && col < N) {
-            const float v = acc[i][j][r] + bj;
-            P.y[(int64_t)row * P.C + col] = v;
-            s1[j] += v;
-            s2[j] = fmaf(v, v, s2[j]);
-          }
-        }
-      s1[j] += __shfl_xor(s1[j], 32, 64);
-      s2[j] += __shfl_xor(s2[j], 32, 64);
-    }
-    // lds is free: the main loop ended with a barrier
-    constexpr int BN = Cfg::BN;
-    if (lane < 32) {
-#pragma unroll
-      for (int j = 0; j < Cfg::TN; ++j) {
-        const int c = (wn * Cfg::TN + j) * 32 + lane;
-        lds[wm * BN + c] = s1[j];
-        lds[Cfg::WM * BN + wm * BN + c] = s2[j];
-      }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < BN; c += 256) {
-      float a = 0.f, b = 0.f;
-#pragma unroll
-      for (int w = 0; w < Cfg::WM; ++w) {
-        a += lds[w * BN + c];
-        b += lds[Cfg::WM * BN + w * BN + c];
-      }
-      if (n0 + c < N) {
-        P.partials[(int64_t)blockIdx.x * 2 * P.C + n0 + c] = a;
-        P.partials[(int64_t)blockIdx.x * 2 * P.C + P.C + n0 + c] = b;
-      }
-    }
-  }
-};
-
-struct EpiConvDgrad {  // scatter rows of a (parity-class) grid back to the full NHWC input gradient (+ bias)
-  static constexpr int SCRATCH = 0;
-  struct Params { float* dst; int GA, GB, ra, pa, rb, pb, DH, DW, C; const float* bias; };
-  template <class Cfg>
-  static __device__ void apply(const Params& P, f32x16 (&acc)[Cfg::TM][Cfg::TN], int m0, int n0, int wm, int wn,
-                               int lane, int M, int N, float*) {
-#pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + acc_row<Cfg>(wm, i, r, lane);
-        if (row >= M) continue;
-        const int img = row / (P.GA * P.GB);
-        const int rem = row - img * P.GA * P.GB;
-        const int a = rem / P.GB, b = rem - a * P.GB;
-        const int64_t base = (((int64_t)img * P.DH + a * P.ra + P.pa) * P.DW + b * P.rb + P.pb) * P.C;
-#pragma unroll
-        for (int j = 0; j < Cfg::TN; ++j) {
-          const int col = n0 + acc_col<Cfg>(wn, j, lane);
-          if (col < N) P.dst[base + col] = acc[i][j][r] + (P.bias ? P.bias[col] : 0.f);
-        }
-      }
-  }
-};
-
-struct EpiPartial {  // split-K slab: part[z][row][col]
-  static constexpr int SCRATCH = 0;
-  struct Params { float* part; int64_t ld; };
-  template <class Cfg>
-  static __device__ void apply(const Params& P, f32x16 (&acc)[Cfg::TM][Cfg::TN], int m0, int n0, int wm, int wn,
-                               int lane, int M, int N, float*) {
-    float* base = P.part + (int64_t)blockIdx.z * M * P.ld;
-#pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + acc_row<Cfg>(wm, i, r, lane);
-        if (row >= M) continue;
-#pragma unroll
-        for (int j = 0; j < Cfg::TN; ++j) {
-          const int col = n0 + acc_col<Cfg>(wn, j, lane);
-          if (col < N) base[(int64_t)row * P.ld + col] = acc[i][j][r];
-        }
-      }
-  }
-};
-
-struct DenseEpiArgs {
-  float* out; int64_t ldc; const float* bias; int relu; int drop; uint64_t h1; uint32_t thr; float dscale;
-  int64_t row0; const float* gate; float gscale;
-  int gmod;  // gate row = row % gmod when > 0 (the stacked rows of the direct classifier's affine backward)
-};
-
-__device__ inline float dense_finish(const DenseEpiArgs& P, int row, int col, float v) {
-  if (P.bias) v += P.bias[col];
-  if (P.relu) v = relu_nan(v);
-  if (P.drop) v = (rng_u24(P.h1, (uint64_t)(P.row0 + row), (uint64_t)col) >= P.thr) ? v * P.dscale : 0.f;
-  if (P.gate) v = P.gate[(int64_t)(P.gmod > 0 ? row % P.gmod : row) * P.ldc + col] > 0.f ? v * P.gscale : 0.f;
-  return v;
-}
-
-struct EpiDense {
-  static constexpr int SCRATCH = 0;
-  using Params = DenseEpiArgs;
-  template <class Cfg>
-  static __device__ void apply(const Params& P, f32x16 (&acc)[Cfg::TM][Cfg::TN], int m0, int n0, int wm, int wn,
-                               int lane, int M, int N, float*) {
-#pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + acc_row<Cfg>(wm, i, r, lane);
-        if (row >= M) continue;
-#pragma unroll
-        for (int j = 0; j < Cfg::TN; ++j) {
-          const int col = n0 + acc_col<Cfg>(wn, j, lane);
-          if (col < N) P.out[(int64_t)row * P.ldc + col] = dense_finish(P, row, col, acc[i][j][r]);
-        }
-      }
-  }
-};
-
-// sum_{z < S} p[z * stride] in z order, 8 loads in flight (clamped, unconditional): the slab sums of the split-K
-// reduces (a plain loop leaves one dependent load round trip per slab)
-__device__ __forceinline__ float slab_sum(const float* __restrict__ p, int S, int64_t stride) {
-  float s = 0.f;
-  for (int z0 = 0; z0 < S; z0 += 8) {
-    float u[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) u[k] = p[(int64_t)min(z0 + k, S - 1) * stride];
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if (z0 + k < S) s += u[k];
-  }
-  return s;
-}
-
 __global__ __launch_bounds__(256) void dense_splitk_reduce_kernel(const float* __restrict__ part, int S, int M, int N,
                                                                   DenseEpiArgs P, const int* skip) {
   if (skip && *skip == 0) return;
@@ -1026,6 +851,15 @@ __global__ __launch_bounds__(256) void dense_splitk_reduce_kernel(const float* _
     const int row = (int)(i / N), col = (int)(i % N);
     P.out[(int64_t)row * P.ldc + col] = dense_finish(P, row, col, s);
   }
+}
+
+int dense_splitk_reduce(const float* part, int S, int M, int N, const DenseEpiArgs& pe, const int* skip,
+                        hipStream_t st) {
+  const int64_t total = (int64_t)M * N;
+  hipLaunchKernelGGL(dense_splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 1024)), dim3(256),
+                     0, st, part, S, M, N, pe, skip);
+  VAD_LAUNCH_CHECK();
+  return 0;
 }
 
 // weight grad of a Linear: part[S][N][K+1] -> dW[N][K], db[N]
@@ -1041,164 +875,6 @@ __global__ __launch_bounds__(256) void dense_wgrad_reduce_kernel(const float* __
     if (col < K) dW[(int64_t)row * K + col] = s;
     else if (db) db[row] = s;
   }
-}
-
-// =====================================================================================================
-// launch helpers
-// =====================================================================================================
-template <class Cfg, template <int> class LA, template <int> class LB, class Epi>
-static int launch_gemm(const typename LA<Cfg::BM>::Params& pa, const typename LB<Cfg::BN>::Params& pb,
-                       const typename Epi::Params& pe, int M, int N, int K, int splits, const int* skip,
-                       hipStream_t st, int* used_splits = nullptr) {
-  if (M <= 0 || N <= 0) return 0;
-  splits = std::max(1, splits);
-  int kps = (int)(cdiv(cdiv(K, splits), BK) * BK);
-  if (kps <= 0) kps = BK;
-  splits = (int)cdiv(K, kps);
-  if (splits < 1) splits = 1;
-  dim3 grid((unsigned)cdiv(M, Cfg::BM), (unsigned)cdiv(N, Cfg::BN), (unsigned)splits);
-  VAD_KLAUNCH((gemm_kernel<Cfg, LA<Cfg::BM>, LB<Cfg::BN>, Epi>), grid, dim3(256), 0, st, pa, pb, pe, M, N, K,
-                     kps, skip);
-  VAD_LAUNCH_CHECK();
-  if (used_splits) *used_splits = splits;
-  return 0;
-}
-
-using T128x32 = TileCfg<4, 1, 1, 1>;
-using T128x64 = TileCfg<2, 2, 2, 1>;
-using T64x64 = TileCfg<2, 2, 1, 1>;
-using T128x128 = TileCfg<2, 2, 2, 2>;
-using T32x128 = TileCfg<1, 4, 1, 1>;
-
-// runtime-selectable tile shapes for the conv GEMMs (tuning / sweeps); id -> TileCfg
-template <class F>
-static int with_tile(int id, F&& f) {
-  switch (id) {
-    case 0: return f(TileCfg<4, 1, 1, 1>{});  // 128 x 32
-    case 1: return f(TileCfg<4, 1, 2, 1>{});  // 256 x 32
-    case 2: return f(TileCfg<2, 2, 1, 1>{});  //  64 x 64
-    case 3: return f(TileCfg<2, 2, 2, 1>{});  // 128 x 64
-    case 4: return f(TileCfg<2, 2, 1, 2>{});  //  64 x 128
-    case 5: return f(TileCfg<2, 2, 2, 2>{});  // 128 x 128
-    case 6: return f(TileCfg<4, 1, 2, 2>{});  // 256 x 64
-    case 7: return f(TileCfg<1, 4, 1, 1>{});  //  32 x 128
-    case 8: return f(TileCfg<1, 4, 1, 2>{});  //  32 x 256
-    case 9: return f(TileCfg<2, 2, 1, 4>{});  //  64 x 256
-    default: set_error("unknown tile id"); return 1;
-  }
-}
-static int tile_bm(int id) {
-  static const int bm[10] = {128, 256, 64, 128, 64, 128, 256, 32, 32, 64};
-  return (id >= 0 && id < 10) ? bm[id] : 64;
-}
-
-struct ConvTuning {
-  int fwd = -1, dgrad = -1, wgrad = -1;  // forced tile ids (-1: heuristic)
-  int wgrad_blocks = 1024;               // target grid size of the split-K weight gradient
-  int wgrad_min_ktiles = 16;             // minimum BK-slices per split
-  int patch = 1;                         // stride-1 fwd/dgrad on the LDS-patch kernels
-  int wgrad_patch = 1;                   // weight gradients on the LDS-patch kernel: 1 stride-1 layers, 2 all
-  int wgrad_alone_blocks = 448;          // the same for a weight gradient nothing else runs beside (the last layer's;
-                                         // 512 / 1024 measured no faster)
-  int wgrad_patch_blocks = 448;          // its target grid size (below 2 per CU: the weight gradients share the GPU with the input gradients, own stream)
-};
-static ConvTuning g_tune;
-
-extern int g_bbox_im2col;  // bbox_plan.hip
-extern int g_maxpool_bwd_win;  // conv3d.hip
-extern int g_ae_direct, g_ae_wgrad_blocks, g_ae_wgrad_stream;  // ae_plan.hip
-extern int g_conv4_cls_batch_min, g_conv4_split_tiles;
-extern int g_a2_direct, g_a2_head_clip;     // a2_plan.hip
-extern int g_conv3s2_fwd_blocks;
-int set_tuning(const char* key, int value) {
-  const std::string k(key);
-  if (k == "conv_fwd_tile") g_tune.fwd = value;
-  else if (k == "conv_dgrad_tile") g_tune.dgrad = value;
-  else if (k == "conv_wgrad_tile") g_tune.wgrad = value;
-  else if (k == "conv_wgrad_blocks") g_tune.wgrad_blocks = value;
-  else if (k == "conv_wgrad_min_ktiles") g_tune.wgrad_min_ktiles = value;
-  else if (k == "conv_patch") g_tune.patch = value;
-  else if (k == "conv_patch_persist") g_patch_persist = value;
-  else if (k == "conv_split") g_conv_split = value;
-  else if (k == "conv_split_nt") g_x3_nt = value;
-  else if (k == "conv_split_wres") g_x3_wres = value;
-  else if (k == "conv_wgrad_patch") g_tune.wgrad_patch = value;
-  else if (k == "conv_wgrad_split") g_wgrad_split = value;
-  else if (k == "conv_wgrad_split_s2") g_wgrad_split_s2 = value;
-  else if (k == "conv_wgrad_tr") g_wgrad_tr = value;
-  else if (k == "conv_wgrad_tr_blocks") g_wgrad_tr_blocks = value;
-  else if (k == "conv_wgrad_tr_pft") g_wgrad_tr_pft = value;
-  else if (k == "conv_wgrad_s2_blocks") g_wgrad_s2_blocks = value;
-  else if (k == "stem_fused") g_stem_fused = value;
-  else if (k == "conv_dgrad_s2_x3") g_dgrad_s2_x3 = value;
-  else if (k == "conv_dgrad_blocks") g_x3_dgrad_blocks = value;
-  else if (k == "conv_split_big") g_x3_big = value;
-  else if (k == "conv_split_s2big") g_x3_s2big = value;
-  else if (k == "bbox_im2col") g_bbox_im2col = value;
-  else if (k == "ae_direct") g_ae_direct = value;
-  else if (k == "ae_wgrad_blocks") g_ae_wgrad_blocks = value;
-  else if (k == "ae_wgrad_stream") g_ae_wgrad_stream = value;
-  else if (k == "conv4_cls_batch_min") g_conv4_cls_batch_min = value;
-  else if (k == "conv4_split_tiles") g_conv4_split_tiles = value;
-  else if (k == "a2_direct") g_a2_direct = value;
-  else if (k == "a2_head_clip") g_a2_head_clip = value;
-  else if (k == "cad_prep_stream") g_cad_prep_stream = value;
-  else if (k == "conv3s2_fwd_blocks") g_conv3s2_fwd_blocks = value;
-  else if (k == "cad_wgrad_stream") g_cad_wgrad_stream = value;
-  else if (k == "cad_dir_affine") g_cad_dir_affine = value;
-  else if (k == "cad_det_gate") g_cad_det_gate = value;
-  else if (k == "cad_stem_early") g_cad_stem_early = value;
-  else if (k == "cad_dy_per_layer") g_cad_dy_per_layer = value;
-  else if (k == "cad_event_sysfence") g_cad_event_sysfence = value;
-  else if (k == "mlp_tail_wide") g_mlp_tail_wide = value;
-  else if (k == "mlp_tail_rb") g_mlp_tail_rb = value;
-  else if (k == "cad_last_wgrad_main") g_cad_last_wgrad_main = value;
-  else if (k == "cad_l0_slab") g_cad_l0_slab = value;
-  else if (k == "cad_opt_images") g_cad_opt_images = value;
-  else if (k == "cad_stream_prio") g_cad_stream_prio = value;
-  else if (k == "conv_split_pipe") g_x3_pipe = value;
-  else if (k == "bn_bwd_fuse") g_bn_bwd_fuse = value;
-  else if (k == "bn_apply_v") g_bn_apply_v = value;
-  else if (k == "conv_wgrad_s1_nt") g_wgrad_s1_nt = value;
-  else if (k == "conv_wgrad_s1_nt_wide") g_wgrad_s1_nt_wide = value;
-  else if (k == "conv_wgrad_s1_nt_blocks") g_wgrad_s1_nt_blocks = value;
-  else if (k == "conv_bf16") g_conv_bf16 = value;  // ops API only (calling thread); plans use their own option
-  else if (k == "act_bf16") g_act_bf16 = value;    // ops API only: bf16 activation storage for the calling thread
-  else if (k == "conv_bfc") g_bfc = value;
-  else if (k == "conv_bfc_blocks") g_bfc_blocks = value;
-  else if (k == "conv_bfc_s2_ni2") g_bfc_s2_ni2 = value;
-  else if (k == "conv3d_direct") g_conv3d_direct = value;
-  else if (k == "maxpool3d_bwd_win") g_maxpool_bwd_win = value;
-  else if (k == "conv3d_wgrad_blocks") g_conv3d_wg_blocks = value;
-  else if (k == "conv_dgrad_s2_w3") g_dgrad_s2_w3 = value;
-  else if (k == "conv_dgrad_s2_nt") g_dgrad_s2_nt = value;
-  else if (k == "bn_apply_u") g_bn_apply_u = value;
-  else if (k == "bn_apply_blocks") g_bn_apply_blocks = value;
-  else if (k == "conv_bfw_blocks") g_bfw_blocks = value;
-  else if (k == "conv_wgrad_patch_blocks") g_tune.wgrad_patch_blocks = value;
-  else if (k == "conv_wgrad_alone_blocks") g_tune.wgrad_alone_blocks = value;
-  else {
-    set_error("unknown tuning key " + k);
-    return 1;
-  }
-  return 0;
-}
-
-// heuristics (fallback when no tile is forced); BM >= 64 keeps the forward BN partial count within bounds
-static int pick_fwd_tile(int M, int N) {
-  if (g_tune.fwd >= 0 && tile_bm(g_tune.fwd) >= 64) return g_tune.fwd;
-  if (N == 32) return 0;
-  return M >= 64 * 1024 ? 3 : 2;
-}
-static int pick_dgrad_tile(int M, int N) {
-  if (g_tune.dgrad >= 0) return g_tune.dgrad;
-  if (N <= 32) return 0;  // (128 x 32: a2's 16-channel input gradient wastes half a tile instead of three quarters)
-  return M >= 64 * 1024 ? 3 : 2;
-}
-static int pick_wgrad_tile(int M, int N) {
-  (void)N;
-  if (g_tune.wgrad >= 0) return g_tune.wgrad;
-  return M == 32 ? 7 : 2;
 }
 
 // =====================================================================================================
@@ -1290,7 +966,7 @@ int conv3_prep_table(int n, const float* const* w, const Conv3Layer* L, float* c
     VAD_CHECK(!t.w3[l] || L[l].Co % 16 == 0, "conv3_prep_weights_all: pre-split Wd needs Co % 16 == 0");
     t.Ci[l] = L[l].Ci;
     t.Co[l] = L[l].Co;
-    t.classes[l] = L[l].stride == 2 && !(g_tune.patch && conv3_patch_supported(L[l], false));
+    t.classes[l] = L[l].stride == 2 && !(g_conv_patch && conv3_patch_supported(L[l], false));
     acc += (int64_t)L[l].Co * L[l].Ci * 9;
     t.end[l] = acc;
   }
@@ -1327,7 +1003,7 @@ int conv3_fwd(const Conv3Layer& L, const float* src, const float* src_stats, con
   }
   VAD_CHECK(L.Ci % 32 == 0, "conv3_fwd: Ci must be a multiple of 32");
   // (the patch grid may exceed ceil(M/64) BN partial blocks on tiny images: those stay on the GEMM path)
-  if (g_tune.patch && conv3_patch_blocks(L.NF, L.OH, L.OW) <= cdiv((int64_t)L.NF * L.OH * L.OW, 64)) {
+  if (g_conv_patch && conv3_patch_blocks(L.NF, L.OH, L.OW) <= cdiv((int64_t)L.NF * L.OH * L.OW, 64)) {
     if (conv3_x3_supported(L, true))
       return conv3_x3_fwd(L, src, src_stats, wf, bias, y, partials, nparts, st, parts_cm);
     VAD_CHECK(!g_act_bf16, "conv3_fwd: bf16 activations need the split kernels");
@@ -1352,18 +1028,6 @@ int conv3_fwd(const Conv3Layer& L, const float* src, const float* src_stats, con
   });
 }
 
-static int dgrad_launch(const ConvGeom& g, const TapTable& taps, const float* dY, const float* wd, int N,
-                        const EpiConvDgrad::Params& pe, hipStream_t st) {
-  const int M = g.imgs * g.GA * g.GB, K = taps.ntaps * g.C;
-  return with_tile(pick_dgrad_tile(M, N), [&](auto cfg) -> int {
-    using C = decltype(cfg);
-    VAD_CHECK(gather_fits((int64_t)g.imgs * g.SH * g.SW * g.C), "conv gather: source over 2 GB");
-    typename ConvGatherKC<C::BM>::Params pa{dY, g, taps, nullptr, nullptr};
-    typename DenseKC<C::BN>::Params pb{wd, K, N, K};
-    return launch_gemm<C, ConvGatherKC, DenseKC, EpiConvDgrad>(pa, pb, pe, M, N, K, 1, nullptr, st);
-  });
-}
-
 int conv3_dgrad(const Conv3Layer& L, const float* dY, const float* wd, float* dX, hipStream_t st,
                 const BnBwdFuse* f, const __bf16* w3) {
   VAD_CHECK(L.Co % 32 == 0, "conv3_dgrad: Co must be a multiple of 32");
@@ -1371,14 +1035,14 @@ int conv3_dgrad(const Conv3Layer& L, const float* dY, const float* wd, float* dX
   if (f) *f->nparts = 0;
   if (bfc_supported(L, false))
     return bfc_dgrad(L, reinterpret_cast<const __bf16*>(dY), conv3_bf16_image(wd, L), reinterpret_cast<__bf16*>(dX), st,
-                     (g_bn_bwd_fuse & 1) ? f : nullptr);
-  if (g_tune.patch && conv3_x3_supported(L, false))
-    return conv3_x3_dgrad(L, dY, wd, dX, st, (g_bn_bwd_fuse & 1) ? f : nullptr);
+                     f);
+  if (g_conv_patch && conv3_x3_supported(L, false))
+    return conv3_x3_dgrad(L, dY, wd, dX, st, f);
   // (the split kernel reads the plain Wd layout, which the prep writes exactly when the f32 patch kernel is usable)
-  if (g_tune.patch && conv3_patch_supported(L, false) && conv3_x3_dgrad_s2_supported(L))
-    return conv3_x3_dgrad_s2(L, dY, wd, dX, st, (g_bn_bwd_fuse & 2) ? f : nullptr, w3);
+  if (g_conv_patch && conv3_patch_supported(L, false) && conv3_x3_dgrad_s2_supported(L))
+    return conv3_x3_dgrad_s2(L, dY, wd, dX, st, f, w3);
   VAD_CHECK(!g_act_bf16, "conv3_dgrad: bf16 activations need the split kernels");
-  if (g_tune.patch && conv3_patch_supported(L, false)) return conv3_patch_dgrad(L, dY, wd, dX, st);
+  if (g_conv_patch && conv3_patch_supported(L, false)) return conv3_patch_dgrad(L, dY, wd, dX, st);
   if (L.stride == 1) {
     ConvGeom g{L.NF, L.IH, L.IW, 1, 1, L.OH, L.OW, L.Co};
     TapTable taps;
@@ -1415,14 +1079,14 @@ bool conv3_act_bf16_ok(const Conv3Layer& L, bool dgrad) {
   {
     ActStorage abf(1);  // (the native bf16 kernels exist for bf16 storage only)
     if (bfc_supported(L, true) && (!dgrad || bfc_supported(L, false) || conv3_x3_dgrad_s2_supported(L)) &&
-        (bfc_wgrad_supported(L) || (g_tune.wgrad_patch && conv3_wgrad_x3_supported(L))))
+        (bfc_wgrad_supported(L) || (g_conv_wgrad_patch && conv3_wgrad_x3_supported(L))))
       return true;
   }
-  const bool fwd = g_tune.patch && conv3_patch_blocks(L.NF, L.OH, L.OW) <= cdiv((int64_t)L.NF * L.OH * L.OW, 64) &&
+  const bool fwd = g_conv_patch && conv3_patch_blocks(L.NF, L.OH, L.OW) <= cdiv((int64_t)L.NF * L.OH * L.OW, 64) &&
                    conv3_x3_supported(L, true);
-  const bool dg = !dgrad || (g_tune.patch && (conv3_x3_supported(L, false) ||
+  const bool dg = !dgrad || (g_conv_patch && (conv3_x3_supported(L, false) ||
                                               (conv3_patch_supported(L, false) && conv3_x3_dgrad_s2_supported(L))));
-  const bool wg = g_tune.wgrad_patch && conv3_wgrad_x3_supported(L);
+  const bool wg = g_conv_wgrad_patch && conv3_wgrad_x3_supported(L);
   return fwd && dg && wg;
 }
 
@@ -1430,36 +1094,39 @@ int conv3_path(const Conv3Layer& L, int kind) {
   if (kind < 2 ? bfc_supported(L, kind == 0) : bfc_wgrad_supported(L)) return 2;
   bool x3 = false;
   if (kind == 1 && L.stride == 2)  // stride-2 input gradients: the parity-class split kernel when supported
-    x3 = g_tune.patch && conv3_patch_supported(L, false) && conv3_x3_dgrad_s2_supported(L);
+    x3 = g_conv_patch && conv3_patch_supported(L, false) && conv3_x3_dgrad_s2_supported(L);
   else if (kind == 0)
-    x3 = g_tune.patch && conv3_patch_blocks(L.NF, L.OH, L.OW) <= cdiv((int64_t)L.NF * L.OH * L.OW, 64) &&
+    x3 = g_conv_patch && conv3_patch_blocks(L.NF, L.OH, L.OW) <= cdiv((int64_t)L.NF * L.OH * L.OW, 64) &&
          conv3_x3_supported(L, true);
   else if (kind == 1)
-    x3 = g_tune.patch && conv3_x3_supported(L, false);
+    x3 = g_conv_patch && conv3_x3_supported(L, false);
   else
-    x3 = g_tune.wgrad_patch && (x3_wgrad_tr_supported(L) || conv3_wgrad_x3_supported(L));
+    x3 = g_conv_wgrad_patch && (x3_wgrad_tr_supported(L) || conv3_wgrad_x3_supported(L));
   return x3 ? (g_conv_bf16 ? 1 : 6) : 0;
 }
+
+// target grid of a weight gradient nothing else runs beside (the last layer's; 512 / 1024 measured no faster)
+constexpr int WGRAD_ALONE_BLOCKS = 448;
 
 int conv3_wgrad(const Conv3Layer& L, const float* dY, const float* src, const float* src_stats, float* partial,
                 int* nsplit, int64_t partial_cap, hipStream_t st, bool alone) {
   if (bfc_wgrad_supported(L))
     return bfc_wgrad(L, reinterpret_cast<const __bf16*>(dY), reinterpret_cast<const __bf16*>(src), src_stats, partial,
                      nsplit, partial_cap, st);
-  if (g_tune.wgrad_patch && x3_wgrad_tr_supported(L))
-    return x3_wgrad_tr(L, dY, src, src_stats, partial, nsplit, partial_cap, alone ? g_tune.wgrad_alone_blocks : 0, st);
-  if (g_tune.wgrad_patch && conv3_wgrad_x3_supported(L))
+  if (g_conv_wgrad_patch && x3_wgrad_tr_supported(L))
+    return x3_wgrad_tr(L, dY, src, src_stats, partial, nsplit, partial_cap, alone ? WGRAD_ALONE_BLOCKS : 0, st);
+  if (g_conv_wgrad_patch && conv3_wgrad_x3_supported(L))
     return conv3_wgrad_x3(L, dY, src, src_stats, partial, nsplit, partial_cap,
-                          alone ? g_tune.wgrad_alone_blocks : g_tune.wgrad_patch_blocks, st);
+                          alone ? WGRAD_ALONE_BLOCKS : g_conv_wgrad_patch_blocks, st);
   VAD_CHECK(!g_act_bf16, "conv3_wgrad: bf16 activations need the split kernels");
-  if (g_tune.wgrad_patch && conv3_wgrad_patch_supported(L) && (L.stride == 1 || g_tune.wgrad_patch == 2))
-    return conv3_wgrad_patch(L, dY, src, src_stats, partial, nsplit, partial_cap, g_tune.wgrad_patch_blocks, st);
+  if (g_conv_wgrad_patch && conv3_wgrad_patch_supported(L) && (L.stride == 1 || g_conv_wgrad_patch == 2))
+    return conv3_wgrad_patch(L, dY, src, src_stats, partial, nsplit, partial_cap, g_conv_wgrad_patch_blocks, st);
   const int M = L.Co, N = 9 * L.Ci, K = L.NF * L.OH * L.OW;
   return with_tile(pick_wgrad_tile(M, N), [&](auto cfg) -> int {
     using C = decltype(cfg);
     const int tiles = (int)(cdiv(M, C::BM) * cdiv(N, C::BN));
     int splits = (int)std::max<int64_t>(
-        1, std::min<int64_t>(cdiv(g_tune.wgrad_blocks, tiles), cdiv(K, (int64_t)g_tune.wgrad_min_ktiles * BK)));
+        1, std::min<int64_t>(cdiv(g_conv_wgrad_blocks, tiles), cdiv(K, (int64_t)g_conv_wgrad_min_ktiles * BK)));
     while ((int64_t)splits * M * N > partial_cap && splits > 1) splits /= 2;
     VAD_CHECK(gather_fits((int64_t)K * L.Co), "dense gather: operand over 2 GB");
     typename DenseKM<C::BM>::Params pa{dY, L.Co, L.Co, K, -1};
@@ -1739,11 +1406,7 @@ int dense_fwd(const float* X, int M, int K, const float* W, const float* b, int 
   EpiPartial::Params pp{scratch, N};
   int used = 1;
   VAD_TRY((launch_gemm<C, DenseKC, DenseKC, EpiPartial>(pa, pb, pp, M, N, K, splits, nullptr, st, &used)));
-  const int64_t total = (int64_t)M * N;
-  hipLaunchKernelGGL(dense_splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 1024)), dim3(256),
-                     0, st, scratch, used, M, N, pe, nullptr);
-  VAD_LAUNCH_CHECK();
-  return 0;
+  return dense_splitk_reduce(scratch, used, M, N, pe, nullptr, st);
 }
 
 int dense_fwd_splitk(const float* X, int M, int K, const float* W, int N, float* scratch, int64_t scratch_floats,
@@ -1788,11 +1451,7 @@ int dense_dgrad(const float* dY, int M, int N, const float* W, int K, float* dX,
       int used = 1;
       EpiPartial::Params pp{scratch, K};
       VAD_TRY((launch_gemm<C, DenseKC, DenseKM, EpiPartial>(pa, pb, pp, M, K, N, splits, skip, st, &used)));
-      const int64_t total = (int64_t)M * K;
-      hipLaunchKernelGGL(dense_splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 1024)),
-                         dim3(256), 0, st, scratch, used, M, K, pe, skip);
-      VAD_LAUNCH_CHECK();
-      return 0;
+      return dense_splitk_reduce(scratch, used, M, K, pe, skip, st);
     }
   }
   return launch_gemm<C, DenseKC, DenseKM, EpiDense>(pa, pb, pe, M, K, N, 1, skip, st);
@@ -1822,728 +1481,6 @@ int dense_wgrad(const float* dY, int M, int N, const float* X, int K, float* dW,
   const int64_t total = (int64_t)N * GN;
   hipLaunchKernelGGL(dense_wgrad_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 2048)), dim3(256),
                      0, st, scratch, used, N, K, dW, db, skip);
-  VAD_LAUNCH_CHECK();
-  return 0;
-}
-
-// =====================================================================================================
-// Conv2d(kernel 4, stride 2, padding 1) and ConvTranspose2d(4, 2, 1) as implicit GEMMs over NHWC frames (cad1's
-// VideoAutoEncoder, causal_anomaly_detection1.py:129-188): the im2col / col2im columns are never written.
-//   conv4_fwd   out[p][n] = sum_{tap, c} src[2a - 1 + ky][2b - 1 + kx][c] wk[n][tap C + c] (+ bias): the 16-tap
-//               gather (Conv2d forward; ConvTranspose2d input gradient with src = dY)
-//   conv4_cls   the transposed direction, one GEMM per output parity class (py, px): rows 2a + py take ky in {1, 3}
-//               (py = 0: source rows a, a - 1) or {0, 2} (py = 1: source rows a + 1, a), 2 x 2 taps scattered to
-//               (2a + py, 2b + px) (+ bias) (Conv2d input gradient with src = dY; ConvTranspose2d forward)
-//   conv4_wgrad the correlation sum over A's pixels p of A[p][r] src[2a - 1 + ky][2b - 1 + kx][c] into split-K slabs
-//               [S][R][16 C] (Conv2d: A = dY, src = X; ConvTranspose2d: A = X, src = dY), summed by
-//               conv4_wgrad_reduce into torch's [R][C][4][4] (Conv2d [Co][Ci], ConvTranspose2d [Ci][Co])
-// =====================================================================================================
-__global__ __launch_bounds__(256) void conv4_prep_kernel(const float* __restrict__ w, int D0, int D1,
-                                                         float* __restrict__ wk, float* __restrict__ wc) {
-  const int64_t total = (int64_t)D0 * D1 * 16;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int tap = (int)(i % 16), d1 = (int)((i / 16) % D1);
-    const int64_t d0 = i / (16 * D1);
-    const float v = w[i];
-    if (wk) wk[d0 * 16 * D1 + tap * D1 + d1] = v;
-    if (wc) {
-      const int ky = tap / 4, kx = tap % 4;
-      const int py = (ky & 1) ? 0 : 1, px = (kx & 1) ? 0 : 1;  // (odd ky: class row 0)
-      const int r = ky >> 1, q = kx >> 1;                      // index among the class's 2 x 2 taps
-      wc[((int64_t)(2 * py + px) * D1 + d1) * 4 * D0 + (2 * r + q) * D0 + d0] = v;
-    }
-  }
-}
-
-int conv4_prep(const float* w, int D0, int D1, float* wk, float* wc, hipStream_t st) {
-  const int64_t total = (int64_t)D0 * D1 * 16;
-  hipLaunchKernelGGL(conv4_prep_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 1024)), dim3(256), 0, st, w,
-                     D0, D1, wk, wc);
-  VAD_LAUNCH_CHECK();
-  return 0;
-}
-
-// split-K when the tile grid leaves most CUs idle (the decoder's 4x4 / 8x8 frames): slabs [S][M][N] in scratch, summed
-// in order (+ bias) by dense_splitk_reduce / conv4_cls_reduce
-// knob "conv4_split_tiles": implicit-GEMM convs with fewer 64 x 64 output tiles than this split K (slabs + a reduce)
-int g_conv4_split_tiles = 512;
-static int conv4_splits(int M, int N, int K, int64_t scratch_floats) {
-  const int64_t tiles = cdiv(M, 64) * cdiv(N, 64);
-  if (tiles >= g_conv4_split_tiles || scratch_floats <= 0) return 1;
-  int s = (int)std::min<int64_t>(cdiv(1024, tiles), K / (2 * BK));
-  while (s > 1 && (int64_t)s * M * N > scratch_floats) s /= 2;
-  return std::max(1, s);
-}
-
-int conv4_fwd(const float* src, int NF, int H, int W, int C, const float* wk, const float* bias, int N, float* out,
-              hipStream_t st, float* scratch, int64_t scratch_floats) {
-  VAD_CHECK(C % 32 == 0 && H % 2 == 0 && W % 2 == 0 && N >= 1, "conv4_fwd: C % 32 == 0, even frames");
-  const int OH = H / 2, OW = W / 2;
-  const ConvGeom g{NF, OH, OW, 2, 2, H, W, C};
-  TapTable taps;
-  taps.ntaps = 16;
-  for (int k = 0; k < 16; ++k) {
-    taps.dh[k] = (int8_t)(k / 4 - 1);
-    taps.dw[k] = (int8_t)(k % 4 - 1);
-  }
-  const int M = NF * OH * OW, K = 16 * C;
-  const DenseEpiArgs pe{out, N, bias, 0, 0, 0, 0, 1.f, 0, nullptr, 1.f};
-  const int splits = conv4_splits(M, N, K, scratch_floats);
-  if (splits > 1) {
-    int used = 1;
-    VAD_CHECK(gather_fits((int64_t)g.imgs * g.SH * g.SW * g.C), "conv gather: source over 2 GB");
-    typename ConvGatherKC<64>::Params pa{src, g, taps, nullptr, nullptr};
-    typename DenseKC<64>::Params pb{wk, K, N, K};
-    const EpiPartial::Params pp{scratch, N};
-    VAD_TRY((launch_gemm<T64x64, ConvGatherKC, DenseKC, EpiPartial>(pa, pb, pp, M, N, K, splits, nullptr, st, &used)));
-    const int64_t total = (int64_t)M * N;
-    hipLaunchKernelGGL(dense_splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 1024)),
-                       dim3(256), 0, st, scratch, used, M, N, pe, nullptr);
-    VAD_LAUNCH_CHECK();
-    return 0;
-  }
-  return with_tile(pick_fwd_tile(M, N), [&](auto cfg) -> int {
-    using Cf = decltype(cfg);
-    VAD_CHECK(gather_fits((int64_t)g.imgs * g.SH * g.SW * g.C), "conv gather: source over 2 GB");
-    typename ConvGatherKC<Cf::BM>::Params pa{src, g, taps, nullptr, nullptr};
-    typename DenseKC<Cf::BN>::Params pb{wk, K, N, K};
-    return launch_gemm<Cf, ConvGatherKC, DenseKC, EpiDense>(pa, pb, pe, M, N, K, 1, nullptr, st);
-  });
-}
-
-struct EpiConv3DgradCls {  // EpiConv3Dgrad for the class-batched GEMM: class = blockIdx.z, its own grid
-  static constexpr int SCRATCH = 0;
-  struct Params {
-    float* dst; int imgs; int GD[8], GA[8], GB[8]; int DD, DH, DW, C; const float* bias;
-    const float* gate;  // nullable, dst's layout: dst = 0 where !(gate > 0) (the producing ReLU's backward, fused)
-    int rev;            // blockIdx.z = 7 - class (the heaviest classes dispatched first); the tables are in z order
-  };
-  template <class Cfg>
-  static __device__ void apply(const Params& P, f32x16 (&acc)[Cfg::TM][Cfg::TN], int m0, int n0, int wm, int wn,
-                               int lane, int, int N, float*) {
-    const int z = blockIdx.z, cls = P.rev ? 7 - z : z, pd = (cls >> 2) & 1, ph = (cls >> 1) & 1, pw = cls & 1;
-    const int GD = P.GD[z], GA = P.GA[z], GB = P.GB[z], per = GD * GA * GB;
-    if (per == 0) return;
-    // a lane's 16 rows come in 4 runs of 4 consecutive rows (acc_row): the first row of a run is decomposed into
-    // (img, a, b, c) by division, the next three by a carrying +1 (the divisions by the class grid were most of the
-    // kernel's VALU work: 38 VALU per MFMA)
-#pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int row0 = m0 + acc_row<Cfg>(wm, i, 4 * q, lane);
-        int img = row0 / per;
-        const int rem = row0 - img * per;
-        int a = rem / (GA * GB);
-        const int r2 = rem - a * GA * GB;
-        int b = r2 / GB, c = r2 - b * GB;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (u > 0) {  // row0 + u: c + 1 with carries into b, a, img
-            ++c;
-            const bool cb = c == GB;
-            c = cb ? 0 : c;
-            b += cb;
-            const bool ca = b == GA;
-            b = ca ? 0 : b;
-            a += ca;
-            const bool ci = a == GD;
-            a = ci ? 0 : a;
-            img += ci;
-          }
-          if (img >= P.imgs) continue;
-          const int64_t base = ((((int64_t)img * P.DD + 2 * a + pd) * P.DH + 2 * b + ph) * P.DW + 2 * c + pw) * P.C;
-          const int r = 4 * q + u;
-#pragma unroll
-          for (int j = 0; j < Cfg::TN; ++j) {
-            const int col = n0 + acc_col<Cfg>(wn, j, lane);
-            if (col < N) {
-              const float v = acc[i][j][r] + (P.bias ? P.bias[col] : 0.f);
-              P.dst[base + col] = (P.gate && !(P.gate[base + col] > 0.f)) ? 0.f : v;
-            }
-          }
-        }
-      }
-  }
-};
-
-// out[img][2a + py][2b + px][n] = bias[n] + sum over the slabs of part[s][(img SH + a) SW + b][n]
-__global__ __launch_bounds__(256) void conv4_cls_reduce_kernel(const float* __restrict__ part, int S, int M, int SH,
-                                                               int SW, int N, int py, int px,
-                                                               const float* __restrict__ bias, float* __restrict__ out) {
-  const int64_t total = (int64_t)M * N;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const float v = slab_sum(part + i, S, total);
-    const int n = (int)(i % N);
-    const int64_t m = i / N;
-    const int b = (int)(m % SW);
-    const int64_t ia = m / SW;
-    const int a = (int)(ia % SH);
-    const int64_t img = ia / SH;
-    out[((img * 2 * SH + 2 * a + py) * 2 * SW + 2 * b + px) * N + n] = v + (bias ? bias[n] : 0.f);
-  }
-}
-
-// knob "conv4_cls_batch_min": the four parity classes go to one batched launch (whole K per block, bias in the
-// epilogue) from this many 64 x 64 class tiles up; below it, per-class split-K launches with a reduce each
-int g_conv4_cls_batch_min = 0;  // (sweep at cad1: 512 1.845-1.850, 128 1.813-1.817, 0 1.785-1.795 ms)
-int conv4_cls(const float* src, int NF, int SH, int SW, int C, const float* wc, const float* bias, int N, float* out,
-              hipStream_t st, float* scratch, int64_t scratch_floats) {
-  VAD_CHECK(C % 32 == 0 && N >= 1, "conv4_cls: C % 32 == 0");
-  const int Mc = NF * SH * SW;
-  if (cdiv(Mc, 64) * cdiv(N, 64) * 4 >= g_conv4_cls_batch_min || scratch_floats <= 0) {
-    // the four classes in one launch (blockIdx.z = class, the 3-D class-batched GEMM with a depth of 1)
-    Conv3ClsGeom g{};
-    g.imgs = NF; g.SD = 1; g.SH = SH; g.SW = SW; g.C = C;
-    EpiConv3DgradCls::Params pe{};
-    pe.dst = out; pe.imgs = NF; pe.DD = 1; pe.DH = 2 * SH; pe.DW = 2 * SW; pe.C = N; pe.bias = bias;
-    for (int cls = 0; cls < 4; ++cls) {
-      const int py = cls >> 1, px = cls & 1;
-      g.GD[cls] = pe.GD[cls] = 1;
-      g.GA[cls] = pe.GA[cls] = SH;
-      g.GB[cls] = pe.GB[cls] = SW;
-      TapTable3& taps = g.taps[cls];
-      taps.ntaps = 4;
-      for (int r = 0; r < 2; ++r)
-        for (int q = 0; q < 2; ++q) {
-          taps.dd[2 * r + q] = 0;
-          taps.dh[2 * r + q] = (int8_t)(py == 0 ? -r : 1 - r);
-          taps.dw[2 * r + q] = (int8_t)(px == 0 ? -q : 1 - q);
-        }
-    }
-    const int K = 4 * C;
-    return with_tile(pick_dgrad_tile(Mc, N), [&](auto cfg) -> int {
-      using Cf = decltype(cfg);
-      VAD_CHECK(gather_fits((int64_t)g.imgs * g.SD * g.SH * g.SW * g.C), "conv gather: source over 2 GB");
-      typename ConvGather3ClsKC<Cf::BM>::Params pa{src, g};
-      typename DenseKCz<Cf::BN>::Params pb{wc, {}, {}, N};
-      for (int c = 0; c < 4; ++c) {
-        pb.off[c] = (int64_t)c * N * K;
-        pb.kdim[c] = K;
-      }
-      const dim3 grid((unsigned)cdiv(Mc, Cf::BM), (unsigned)cdiv(N, Cf::BN), 4u);
-      VAD_KLAUNCH((gemm_kernel<Cf, ConvGather3ClsKC<Cf::BM>, DenseKCz<Cf::BN>, EpiConv3DgradCls>), grid, dim3(256), 0,
-                  st, pa, pb, pe, Mc, N, K, -1, nullptr);
-      VAD_LAUNCH_CHECK();
-      return 0;
-    });
-  }
-  for (int cls = 0; cls < 4; ++cls) {
-    const int py = cls >> 1, px = cls & 1;
-    const ConvGeom g{NF, SH, SW, 1, 1, SH, SW, C};
-    TapTable taps;
-    taps.ntaps = 4;
-    for (int r = 0; r < 2; ++r)
-      for (int q = 0; q < 2; ++q) {
-        taps.dh[2 * r + q] = (int8_t)(py == 0 ? -r : 1 - r);
-        taps.dw[2 * r + q] = (int8_t)(px == 0 ? -q : 1 - q);
-      }
-    const int M = NF * SH * SW, K = 4 * C;
-    const int splits = conv4_splits(M, N, K, scratch_floats);
-    if (splits > 1) {
-      int used = 1;
-      VAD_CHECK(gather_fits((int64_t)g.imgs * g.SH * g.SW * g.C), "conv gather: source over 2 GB");
-      typename ConvGatherKC<64>::Params pa{src, g, taps, nullptr, nullptr};
-      typename DenseKC<64>::Params pb{wc + (int64_t)cls * N * 4 * C, K, N, K};
-      const EpiPartial::Params pp{scratch, N};
-      VAD_TRY((launch_gemm<T64x64, ConvGatherKC, DenseKC, EpiPartial>(pa, pb, pp, M, N, K, splits, nullptr, st,
-                                                                     &used)));
-      const int64_t total = (int64_t)M * N;
-      hipLaunchKernelGGL(conv4_cls_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 1024)),
-                         dim3(256), 0, st, scratch, used, M, SH, SW, N, py, px, bias, out);
-      VAD_LAUNCH_CHECK();
-      continue;
-    }
-    const EpiConvDgrad::Params pe{out, SH, SW, 2, py, 2, px, 2 * SH, 2 * SW, N, bias};
-    VAD_TRY(dgrad_launch(g, taps, src, wc + (int64_t)cls * N * 4 * C, N, pe, st));
-  }
-  return 0;
-}
-
-int conv4_wgrad(const float* A, int R, const float* src, int C, int NF, int AH, int AW, float* part, int* nsplit,
-                int64_t part_cap, int target_blocks, hipStream_t st) {
-  VAD_CHECK(C % 4 == 0 && R % 4 == 0, "conv4_wgrad: channel counts % 4 == 0");
-  const int M = R, N = 16 * C, K = NF * AH * AW;
-  VAD_CHECK((int64_t)M * N <= part_cap, "conv4_wgrad: slab too small");
-  return with_tile(pick_wgrad_tile(M, N), [&](auto cfg) -> int {
-    using Cf = decltype(cfg);
-    const int tiles = (int)(cdiv(M, Cf::BM) * cdiv(N, Cf::BN));
-    int splits = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(target_blocks, tiles), cdiv(K, 16 * BK)));
-    while ((int64_t)splits * M * N > part_cap && splits > 1) splits /= 2;
-    VAD_CHECK(gather_fits((int64_t)K * R), "dense gather: operand over 2 GB");
-    typename DenseKM<Cf::BM>::Params pa{A, R, R, K, -1};
-    VAD_CHECK(gather_fits((int64_t)NF * 2 * AH * 2 * AW * C), "conv patch: source over 2 GB");
-    typename ConvPatchKM<Cf::BN>::Params pb{src, NF, AH, AW, 2, 1, 2 * AH, 2 * AW, C, 4, N, nullptr, nullptr};
-    const EpiPartial::Params pe{part, N};
-    return launch_gemm<Cf, DenseKM, ConvPatchKM, EpiPartial>(pa, pb, pe, M, N, K, splits, nullptr, st, nsplit);
-  });
-}
-
-// dW[r][c][tap] = sum over the S slabs, in order, of part[s][r][tap C + c] (NT taps: 16 for the 4x4 convs, 27 for
-// the 3-D ones)
-// (slab rows of ld floats: the NT C weight columns, then with db the bias column NT C)
-__global__ __launch_bounds__(256) void conv4_wgrad_reduce_kernel(const float* __restrict__ part, int S, int R, int C,
-                                                                 int NT, int ld, float* __restrict__ dW,
-                                                                 float* __restrict__ db) {
-  const int W1 = NT * C + (db ? 1 : 0);
-  const int64_t total = (int64_t)R * W1, slab = (int64_t)R * ld;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / W1;
-    const int col = (int)(i - r * W1);
-    const float s = slab_sum(part + r * ld + col, S, slab);
-    if (col == NT * C) {
-      db[r] = s;
-    } else {
-      const int c = col % C, tap = col / C;
-      dW[(r * C + c) * NT + tap] = s;
-    }
-  }
-}
-
-// the same for many slabs: 64 consecutive entries x 4 slab lanes per block (lane l adds slabs l, l + 4, ... in order
-// with 8 loads in flight, coalesced across the 64 entries), the 4 lane sums combined in a fixed order
-__global__ __launch_bounds__(256) void conv4_wgrad_reduce_small_kernel(const float* __restrict__ part, int S, int R,
-                                                                       int C, int NT, int ld, float* __restrict__ dW,
-                                                                       float* __restrict__ db) {
-  __shared__ float red[4][64];
-  const int W1 = NT * C + (db ? 1 : 0);
-  const int64_t total = (int64_t)R * W1, slab = (int64_t)R * ld;
-  const int e = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const int64_t i = (int64_t)blockIdx.x * 64 + e;
-  const int64_t row = i / W1, col = i - row * W1, pi = row * ld + col;
-  float v = 0.f;
-  if (i < total) {
-    const int n = S > sl ? (S - sl + 3) / 4 : 0;
-    for (int k0 = 0; k0 < n; k0 += 8) {
-      float u[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) u[q] = part[(int64_t)(sl + 4 * min(k0 + q, n - 1)) * slab + pi];
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        if (k0 + q < n) v += u[q];
-    }
-  }
-  red[sl][e] = v;
-  __syncthreads();
-  if (sl == 0 && i < total) {
-    const float t = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
-    if (col == NT * C) {
-      db[row] = t;
-    } else {
-      const int c = (int)(col % C), tap = (int)(col / C);
-      dW[(row * C + c) * NT + tap] = t;
-    }
-  }
-}
-
-// slabs [S][R][ld] -> dW (torch [R][C][taps]) and, with db, the bias column NT C of each row
-static int taps_wgrad_reduce(const float* part, int S, int R, int C, int NT, float* dW, hipStream_t st, int ld = 0,
-                             float* db = nullptr) {
-  if (ld <= 0) ld = NT * C;
-  const int64_t total = (int64_t)R * (NT * C + (db ? 1 : 0));
-  if (S >= 16) {
-    hipLaunchKernelGGL(conv4_wgrad_reduce_small_kernel, dim3((unsigned)cdiv(total, 64)), dim3(256), 0, st, part, S, R, C,
-                       NT, ld, dW, db);
-    VAD_LAUNCH_CHECK();
-    return 0;
-  }
-  hipLaunchKernelGGL(conv4_wgrad_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 2048)), dim3(256), 0,
-                     st, part, S, R, C, NT, ld, dW, db);
-  VAD_LAUNCH_CHECK();
-  return 0;
-}
-
-int conv4_wgrad_reduce(const float* part, int S, int R, int C, float* dW, hipStream_t st) {
-  return taps_wgrad_reduce(part, S, R, C, 16, dW, st);
-}
-
-// ---------------------------------------------------------------- the single-channel ends (cad1:131, cad1:185)
-// conv4_c1_fwd  out[p][n] = sum_tap src[2a - 1 + ky][2b - 1 + kx] w[n][tap] (+ bias[n]), 1-channel NHWC source, 32
-//               outputs per pixel on the VALU (Conv2d(1, 32) forward; ConvTranspose2d(32, 1) input gradient with
-//               src = dY, w = the [32][1][4][4] weight)
-// conv4_c1_tfwd out[2a + py][2b + px] = bias + sum over the class taps and the 32 source channels (ConvTranspose2d(32,
-//               1) forward)
-// conv4_c1_wgrad slab[block][r][tap] = sum over the block's pixels p of A[p][r] src[2a - 1 + ky][2b - 1 + kx] (r < 32;
-//               Conv2d(1, 32): A = dY; ConvTranspose2d(32, 1): A = X, src = dY)
-__global__ __launch_bounds__(256) void conv4_c1_fwd_kernel(const float* __restrict__ src, int NF, int H, int W,
-                                                           const float* __restrict__ w, const float* __restrict__ bias,
-                                                           float* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float ws[16][32];  // [tap][n]
-  __shared__ __attribute__((aligned(16))) float os[256 * 33];  // the block's 256 output rows, written back coalesced
-  for (int i = threadIdx.x; i < 512; i += 256) ws[i % 16][i / 16] = w[i];
-  const int OH = H / 2, OW = W / 2;
-  const int64_t total = (int64_t)NF * OH * OW;
-  for (int64_t p0 = blockIdx.x * 256ll; p0 < total; p0 += (int64_t)gridDim.x * 256) {
-    __syncthreads();
-    const int64_t p = p0 + threadIdx.x;
-    if (p < total) {
-      const int ox = (int)(p % OW);
-      const int64_t r = p / OW;
-      const int oy = (int)(r % OH);
-      const float* img = src + (r / OH) * H * W;
-      float x[16];
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const int iy = 2 * oy - 1 + t / 4, ix = 2 * ox - 1 + t % 4;
-        x[t] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? img[iy * W + ix] : 0.f;
-      }
-#pragma unroll
-      for (int n4 = 0; n4 < 8; ++n4) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-          const f32x4 wv = *reinterpret_cast<const f32x4*>(&ws[t][4 * n4]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[e] = fmaf(x[t], wv[e], acc[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) os[threadIdx.x * 33 + 4 * n4 + e] = acc[e] + (bias ? bias[4 * n4 + e] : 0.f);
-      }
-    }
-    __syncthreads();
-    const int64_t nrow = min((int64_t)256, total - p0);
-    for (int i = threadIdx.x; i < nrow * 8; i += 256) {  // 8 float4 per output row, consecutive lanes -> consecutive
-      const int row = i >> 3, c4 = (i & 7) * 4;
-      const f32x4 v = {os[row * 33 + c4], os[row * 33 + c4 + 1], os[row * 33 + c4 + 2], os[row * 33 + c4 + 3]};
-      *reinterpret_cast<f32x4*>(out + (p0 + row) * 32 + c4) = v;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void conv4_c1_tfwd_kernel(const float* __restrict__ src, int NF, int SH, int SW,
-                                                            const float* __restrict__ w, const float* __restrict__ bias,
-                                                            float* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float ws[16][32];  // [tap][source channel]
-  for (int i = threadIdx.x; i < 512; i += 256) ws[i % 16][i / 16] = w[i];
-  __syncthreads();
-  const int OH = 2 * SH, OW = 2 * SW;
-  const int64_t total = (int64_t)NF * OH * OW;
-  const float b0 = bias ? bias[0] : 0.f;
-  for (int64_t p = blockIdx.x * 256ll + threadIdx.x; p < total; p += (int64_t)gridDim.x * 256) {
-    const int ox = (int)(p % OW);
-    const int64_t r = p / OW;
-    const int oy = (int)(r % OH);
-    const int64_t img = r / OH;
-    const int py = oy & 1, px = ox & 1, a = oy >> 1, b = ox >> 1;
-    float acc = 0.f;
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int sy = a + (py == 0 ? -rr : 1 - rr), sx = b + (px == 0 ? -q : 1 - q);
-        if (sy < 0 || sy >= SH || sx < 0 || sx >= SW) continue;
-        const int ky = py == 0 ? 1 + 2 * rr : 2 * rr, kx = px == 0 ? 1 + 2 * q : 2 * q;
-        const float* xs = src + ((img * SH + sy) * SW + sx) * 32;
-        const float* wt = ws[ky * 4 + kx];
-#pragma unroll
-        for (int c4 = 0; c4 < 8; ++c4) {
-          const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + 4 * c4);
-          const f32x4 wv = *reinterpret_cast<const f32x4*>(wt + 4 * c4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc = fmaf(xv[e], wv[e], acc);
-        }
-      }
-    out[p] = acc + b0;
-  }
-}
-
-// conv4_c1_wgrad: a block walks tiles of 256 consecutive A pixels (256 / AW whole rows of one image); the tile's A rows
-// (256 x 32) and its 1-channel source halo ((2 TR + 2) x (2 AW + 2)) in LDS, thread (channel r, tap pair) sums over the
-// tile's pixels (three LDS reads, two FMAs per pixel)
-constexpr int C1_TILE = 256;
-
-// thread = 4 output channels (quad q) x 2 taps (pair p) over one wave's share of the tile's pixel rows (wave w takes
-// rows w, w + 4, ...): per pixel one 16-B read of the dY quad and two halo reads feed 8 FMAs; the four waves' sums are
-// combined in a fixed order at the end
-__global__ __launch_bounds__(256) void conv4_c1_wgrad_kernel(const float* __restrict__ A, const float* __restrict__ src,
-                                                             int NF, int AH, int AW, float* __restrict__ slab) {
-  __shared__ __attribute__((aligned(16))) float as[C1_TILE][32];
-  __shared__ float xs[(2 * C1_TILE / 8 + 2) * (2 * 64 + 2)];  // (AW >= 8, AW <= 64)
-  __shared__ float red[4][512];
-  const int H = 2 * AH, W = 2 * AW, TR = C1_TILE / AW, XW = 2 * AW + 2, XR = 2 * TR + 2;
-  const int64_t ntiles = (int64_t)NF * AH / TR;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, q = lane & 7, p = lane >> 3;
-  const int k0 = 2 * p, k1 = 2 * p + 1;
-  const int o0 = (k0 / 4) * XW + k0 % 4, o1 = (k1 / 4) * XW + k1 % 4;  // tap offsets in the halo
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t img = tile / (AH / TR);
-    const int y0 = (int)(tile % (AH / TR)) * TR;  // first A row of the tile
-    __syncthreads();
-    const float* arow = A + ((img * AH + y0) * (int64_t)AW) * 32;
-    for (int i = t; i < C1_TILE * 8; i += 256)
-      *reinterpret_cast<f32x4*>(&as[i >> 3][(i & 7) * 4]) = *reinterpret_cast<const f32x4*>(arow + (int64_t)i * 4);
-    const float* simg = src + img * (int64_t)H * W;
-    for (int i = t; i < XR * XW; i += 256) {
-      const int hy = i / XW, hx = i - hy * XW;
-      const int iy = 2 * y0 - 1 + hy, ix = hx - 1;
-      xs[i] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? simg[(int64_t)iy * W + ix] : 0.f;
-    }
-    __syncthreads();
-    for (int vy = wv; vy < TR; vy += 4) {  // (pixel v = vy * AW + vx, walked without divisions)
-      const float* xrow = xs + 2 * vy * XW;
-#pragma unroll 4
-      for (int vx = 0; vx < AW; ++vx) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(&as[vy * AW + vx][4 * q]);
-        const float x0 = xrow[2 * vx + o0], x1 = xrow[2 * vx + o1];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          acc0[e] = fmaf(a[e], x0, acc0[e]);
-          acc1[e] = fmaf(a[e], x1, acc1[e]);
-        }
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    red[wv][(4 * q + e) * 16 + k0] = acc0[e];
-    red[wv][(4 * q + e) * 16 + k1] = acc1[e];
-  }
-  __syncthreads();
-  for (int i = t; i < 512; i += 256)
-    slab[(int64_t)blockIdx.x * 512 + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-}
-
-int conv4_c1_fwd(const float* src, int NF, int H, int W, const float* w, const float* bias, float* out,
-                 hipStream_t st) {
-  VAD_CHECK(H % 2 == 0 && W % 2 == 0, "conv4_c1_fwd: even frames");
-  const int64_t total = (int64_t)NF * (H / 2) * (W / 2);
-  hipLaunchKernelGGL(conv4_c1_fwd_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 4096)), dim3(256), 0, st,
-                     src, NF, H, W, w, bias, out);
-  VAD_LAUNCH_CHECK();
-  return 0;
-}
-
-int conv4_c1_tfwd(const float* src, int NF, int SH, int SW, const float* w, const float* bias, float* out,
-                  hipStream_t st) {
-  const int64_t total = (int64_t)NF * 4 * SH * SW;
-  hipLaunchKernelGGL(conv4_c1_tfwd_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 4096)), dim3(256), 0, st,
-                     src, NF, SH, SW, w, bias, out);
-  VAD_LAUNCH_CHECK();
-  return 0;
-}
-
-int conv4_c1_wgrad(const float* A, const float* src, int NF, int AH, int AW, float* dW, float* slab,
-                   int64_t slab_floats, hipStream_t st) {
-  VAD_CHECK(AW >= 8 && AW <= 64 && C1_TILE % AW == 0 && AH % (C1_TILE / AW) == 0,
-            "conv4_c1_wgrad: 256 / AW whole rows per tile");
-  const int64_t ntiles = (int64_t)NF * AH * AW / C1_TILE;
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>({ntiles, 512, slab_floats / 512}));
-  hipLaunchKernelGGL(conv4_c1_wgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A, src, NF, AH, AW, slab);
-  VAD_LAUNCH_CHECK();
-  return conv4_wgrad_reduce(slab, blocks, 32, 1, dW, st);
-}
-
-// =====================================================================================================
-// Conv3d(kernel 3, stride 2, padding 1) as implicit GEMMs over NDHWC volumes (a2's conv3d_2 / conv3d_3,
-// avenue_training_script2.py:20-21): no im2col / col2im columns.
-//   conv3s2_fwd    out[p][n] = act(sum_{tap, c} src[2a - 1 + kd][2b - 1 + kh][2c - 1 + kw][c] wk[n][tap C + c] + bias)
-//   conv3s2_dgrad  the input gradient as 8 parity-class GEMMs over dY: along each dim an even input index takes k = 1
-//                  (dY index = its half), an odd one k = 0 (half + 1) and k = 2 (half); scattered to (2a + pd, ...)
-//   conv3s2_wgrad  split-K correlation dY x patch3(src) into slabs, summed into torch's [Co][Ci][27] layout
-// Weight images (conv3s2_prep) of torch [Co][Ci][27]: wk [Co][27 Ci]; wc = the 8 class images [Ci][nt Co] back to back
-// (class cls = 4 pd + 2 ph + pw, nt = its tap count 1 / 2 / 4 / 8, taps d-major over the per-dim lists).
-// =====================================================================================================
-
-__global__ __launch_bounds__(256) void conv3s2_prep_kernel(const float* __restrict__ w, int Co, int Ci,
-                                                           float* __restrict__ wk, float* __restrict__ wc) {
-  const int64_t total = (int64_t)Co * Ci * 27;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
-    conv3s2_prep_elem(w, Co, Ci, wk, wc, i);
-}
-
-int conv3s2_prep(const float* w, int Co, int Ci, float* wk, float* wc, hipStream_t st) {
-  const int64_t total = (int64_t)Co * Ci * 27;
-  hipLaunchKernelGGL(conv3s2_prep_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 1024)), dim3(256), 0, st,
-                     w, Co, Ci, wk, wc);
-  VAD_LAUNCH_CHECK();
-  return 0;
-}
-
-int g_conv3s2_fwd_blocks = 512;  // knob "conv3s2_fwd_blocks": split K until the grid reaches this many blocks
-int conv3s2_fwd(const float* src, int NF, int D, int H, int W, int C, const float* wk, const float* bias, int N,
-                int relu, float* out, hipStream_t st, float* scratch, int64_t scratch_floats) {
-  VAD_CHECK(C % 4 == 0 && N >= 1, "conv3s2_fwd: C % 4 == 0");
-  const int OD = (D - 1) / 2 + 1, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  ConvGeom3 g{NF, OD, OH, OW, 2, 2, 2, D, H, W, C};
-  TapTable3 taps;
-  taps.ntaps = 27;
-  for (int t = 0; t < 27; ++t) {
-    taps.dd[t] = (int8_t)(t / 9 - 1);
-    taps.dh[t] = (int8_t)((t / 3) % 3 - 1);
-    taps.dw[t] = (int8_t)(t % 3 - 1);
-  }
-  const int M = NF * OD * OH * OW, K = 27 * C;
-  const DenseEpiArgs pe{out, N, bias, relu, 0, 0, 0, 1.f, 0, nullptr, 1.f};
-  return with_tile(pick_fwd_tile(M, N), [&](auto cfg) -> int {
-    using Cf = decltype(cfg);
-    VAD_CHECK(gather_fits((int64_t)g.imgs * g.SD * g.SH * g.SW * g.C), "conv gather: source over 2 GB");
-    typename ConvGather3KC<Cf::BM>::Params pa{src, g, taps};
-    typename DenseKC<Cf::BN>::Params pb{wk, K, N, K};
-    // (conv3d_3 at B = 32: 64 output tiles of 27 K slices each -- split K four ways, slabs summed in order by
-    // dense_splitk_reduce, which applies the bias and the ReLU)
-    const int tiles = (int)(cdiv(M, Cf::BM) * cdiv(N, Cf::BN));
-    int splits = (int)std::min<int64_t>(cdiv(g_conv3s2_fwd_blocks, tiles), cdiv(K, 4 * BK));
-    while (splits > 1 && (int64_t)splits * M * N > scratch_floats) splits /= 2;
-    if (!scratch || splits <= 1) return launch_gemm<Cf, ConvGather3KC, DenseKC, EpiDense>(pa, pb, pe, M, N, K, 1, nullptr, st);
-    EpiPartial::Params pp{scratch, N};
-    int used = 1;
-    VAD_TRY((launch_gemm<Cf, ConvGather3KC, DenseKC, EpiPartial>(pa, pb, pp, M, N, K, splits, nullptr, st, &used)));
-    const int64_t total = (int64_t)M * N;
-    hipLaunchKernelGGL(dense_splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 1024)), dim3(256),
-                       0, st, scratch, used, M, N, pe, nullptr);
-    VAD_LAUNCH_CHECK();
-    return 0;
-  });
-}
-
-struct EpiConv3Dgrad {  // scatter the rows of a parity-class grid to the NDHWC input gradient
-  static constexpr int SCRATCH = 0;
-  struct Params { float* dst; int GD, GA, GB, pd, ph, pw, DD, DH, DW, C; };
-  template <class Cfg>
-  static __device__ void apply(const Params& P, f32x16 (&acc)[Cfg::TM][Cfg::TN], int m0, int n0, int wm, int wn,
-                               int lane, int M, int N, float*) {
-    const int per = P.GD * P.GA * P.GB;
-#pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + acc_row<Cfg>(wm, i, r, lane);
-        if (row >= M) continue;
-        const int img = row / per, rem = row - img * per;
-        const int a = rem / (P.GA * P.GB), r2 = rem - a * P.GA * P.GB;
-        const int b = r2 / P.GB, c = r2 - b * P.GB;
-        const int64_t base =
-            ((((int64_t)img * P.DD + 2 * a + P.pd) * P.DH + 2 * b + P.ph) * P.DW + 2 * c + P.pw) * P.C;
-#pragma unroll
-        for (int j = 0; j < Cfg::TN; ++j) {
-          const int col = n0 + acc_col<Cfg>(wn, j, lane);
-          if (col < N) P.dst[base + col] = acc[i][j][r];
-        }
-      }
-  }
-};
-
-int conv3s2_dgrad(const float* dy, int NF, int Co, const float* wc, int Ci, float* dx, int D, int H, int W,
-                  hipStream_t st, const float* gate) {
-  VAD_CHECK(Co % 4 == 0, "conv3s2_dgrad: Co % 4 == 0");
-  const int OD = (D - 1) / 2 + 1, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  // the 8 parity classes in one launch (blockIdx.z = 7 - class: the 8-tap class first, the 1-tap class last, so the
-  // longest blocks are dispatched first; each block's K loop stops at its class's own taps x Co)
-  Conv3ClsGeom g{};
-  g.imgs = NF; g.SD = OD; g.SH = OH; g.SW = OW; g.C = Co;
-  typename DenseKCz<64>::Params pb0{};
-  EpiConv3DgradCls::Params pe{};
-  pe.dst = dx; pe.imgs = NF; pe.DD = D; pe.DH = H; pe.DW = W; pe.C = Ci; pe.gate = gate; pe.rev = 1;
-  int64_t off = 0;
-  int Mmax = 0;
-  for (int cls = 0; cls < 8; ++cls) {
-    const int pd = (cls >> 2) & 1, ph = (cls >> 1) & 1, pw = cls & 1, nt = c3_nt(cls), z = 7 - cls;
-    g.GD[z] = pe.GD[z] = std::max(0, (D - pd + 1) / 2);
-    g.GA[z] = pe.GA[z] = std::max(0, (H - ph + 1) / 2);
-    g.GB[z] = pe.GB[z] = std::max(0, (W - pw + 1) / 2);
-    Mmax = std::max(Mmax, NF * g.GD[z] * g.GA[z] * g.GB[z]);
-    TapTable3& taps = g.taps[z];
-    taps.ntaps = nt;
-    const int nh = 1 + ph, nw = 1 + pw;
-    for (int t = 0; t < nt; ++t) {
-      const int id = t / (nh * nw), ih = (t / nw) % nh, iw = t % nw;
-      // even parity: k = 1, offset 0; odd: k = 0 -> offset +1, k = 2 -> offset 0
-      taps.dd[t] = (int8_t)(pd == 0 ? 0 : (id == 0 ? 1 : 0));
-      taps.dh[t] = (int8_t)(ph == 0 ? 0 : (ih == 0 ? 1 : 0));
-      taps.dw[t] = (int8_t)(pw == 0 ? 0 : (iw == 0 ? 1 : 0));
-    }
-    pb0.off[z] = off;
-    pb0.kdim[z] = nt * Co;
-    off += (int64_t)nt * Ci * Co;
-  }
-  if (Mmax == 0) return 0;
-  const int K = 8 * Co;
-  return with_tile(pick_dgrad_tile(Mmax, Ci), [&](auto cfg) -> int {
-    using Cf = decltype(cfg);
-    VAD_CHECK(gather_fits((int64_t)g.imgs * g.SD * g.SH * g.SW * g.C), "conv gather: source over 2 GB");
-    typename ConvGather3ClsKC<Cf::BM>::Params pa{dy, g};
-    typename DenseKCz<Cf::BN>::Params pb{wc, {}, {}, Ci};
-    for (int c = 0; c < 8; ++c) {
-      pb.off[c] = pb0.off[c];
-      pb.kdim[c] = pb0.kdim[c];
-    }
-    const dim3 grid((unsigned)cdiv(Mmax, Cf::BM), (unsigned)cdiv(Ci, Cf::BN), 8u);
-    VAD_KLAUNCH((gemm_kernel<Cf, ConvGather3ClsKC<Cf::BM>, DenseKCz<Cf::BN>, EpiConv3DgradCls>), grid, dim3(256), 0, st,
-                pa, pb, pe, Mmax, Ci, K, -1, nullptr);
-    VAD_LAUNCH_CHECK();
-    return 0;
-  });
-}
-
-int conv3s2_wgrad(const float* dy, int Co, const float* src, int Ci, int NF, int D, int H, int W, float* dW,
-                  float* part, int64_t part_cap, int target_blocks, hipStream_t st, float* db) {
-  VAD_CHECK(Ci % 4 == 0 && Co % 4 == 0, "conv3s2_wgrad: channel counts % 4 == 0");
-  const int OD = (D - 1) / 2 + 1, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  // (db: the bias gradient = dY's column sums, as one more GEMM column of ones beside the 27 Ci patch columns)
-  const int M = Co, N = 27 * Ci + (db ? 1 : 0), K = NF * OD * OH * OW;
-  VAD_CHECK((int64_t)M * N <= part_cap, "conv3s2_wgrad: slab too small");
-  int used = 1;
-  VAD_TRY(with_tile(pick_wgrad_tile(M, N), [&](auto cfg) -> int {
-    using Cf = decltype(cfg);
-    const int tiles = (int)(cdiv(M, Cf::BM) * cdiv(N, Cf::BN));
-    int splits = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(target_blocks, tiles), cdiv(K, 8 * BK)));
-    while ((int64_t)splits * M * N > part_cap && splits > 1) splits /= 2;
-    VAD_CHECK(gather_fits((int64_t)K * Co), "dense gather: operand over 2 GB");
-    typename DenseKM<Cf::BM>::Params pa{dy, Co, Co, K, -1};
-    VAD_CHECK(gather_fits((int64_t)NF * D * H * W * Ci), "conv patch: source over 2 GB");
-    typename ConvPatch3KM<Cf::BN>::Params pb{src, NF, OD, OH, OW, 2, 2, 2, 1, D, H, W, Ci, 27 * Ci, db ? 1 : 0};
-    const EpiPartial::Params pe{part, N};
-    return launch_gemm<Cf, DenseKM, ConvPatch3KM, EpiPartial>(pa, pb, pe, M, N, K, splits, nullptr, st, &used);
-  }));
-  return taps_wgrad_reduce(part, used, Co, Ci, 27, dW, st, N, db);
-}
-
-// db[n] = sum over the M rows of x[m][n], fixed order, two passes: block b sums the rows of its contiguous range with
-// 256 / N row lanes per column (coalesced rows), lanes combined by a fixed tree -> part[b][n]; then one block adds the
-// block sums in order (double).  N divides 256.
-__global__ __launch_bounds__(256) void col_sum_part_kernel(const float* __restrict__ x, int64_t M, int N, int64_t rows,
-                                                           double* __restrict__ part) {
-  __shared__ double red[256];
-  const int n = threadIdx.x % N, lane = threadIdx.x / N, lanes = 256 / N;
-  const int64_t r0 = (int64_t)blockIdx.x * rows, r1 = min(M, r0 + rows);
-  double s = 0.0;
-#pragma unroll 4
-  for (int64_t m = r0 + lane; m < r1; m += lanes) s += (double)x[m * N + n];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = lanes / 2; o > 0; o >>= 1) {
-    if (lane < o) red[threadIdx.x] += red[threadIdx.x + o * N];
-    __syncthreads();
-  }
-  if (lane == 0) part[(int64_t)blockIdx.x * N + n] = red[n];
-}
-// 256 / N lanes per column each add a strided subset of the P block sums (loads independent, in flight together),
-// then the same fixed tree as the first pass
-__global__ __launch_bounds__(256) void col_sum_fin_kernel(const double* __restrict__ part, int P, int N,
-                                                          float* __restrict__ db) {
-  __shared__ double red[256];
-  const int n = threadIdx.x % N, lane = threadIdx.x / N, lanes = 256 / N;
-  double s = 0.0;
-#pragma unroll 8
-  for (int p = lane; p < P; p += lanes) s += part[(int64_t)p * N + n];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = lanes / 2; o > 0; o >>= 1) {
-    if (lane < o) red[threadIdx.x] += red[threadIdx.x + o * N];
-    __syncthreads();
-  }
-  if (lane == 0) db[n] = (float)red[n];
-}
-
-int col_sum(const float* x, int64_t M, int N, float* db, double* scratch, hipStream_t st) {
-  VAD_CHECK(N >= 1 && N <= 256 && 256 % N == 0, "col_sum: N divides 256");
-  const int64_t rows = std::max<int64_t>(256 / N, cdiv(M, 256));
-  const int P = (int)cdiv(M, rows);
-  hipLaunchKernelGGL(col_sum_part_kernel, dim3((unsigned)P), dim3(256), 0, st, x, M, N, rows, scratch);
-  VAD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(col_sum_fin_kernel, dim3(1), dim3(256), 0, st, scratch, P, N, db);
   VAD_LAUNCH_CHECK();
   return 0;
 }

@@ -144,8 +144,6 @@ __global__ __launch_bounds__(256) void bbox_tail_kernel(const float* __restrict_
   }
 }
 
-int g_bbox_im2col = 0;
-
 struct BbPlanImpl {
   int B, T, H, W;
   Conv3dGeom g1, g2;

@@ -472,18 +472,18 @@ struct CadPlanImpl {
   int streams() {
     if (!st2) {
       // the plan's events only order its own queues on this device (stream waits, never host inspection): an
-      // agent-scope release suffices, so the system-scope fence at each record is dropped (knob
-      // "cad_event_sysfence" = 1 restores it)
-      const unsigned evf = hipEventDisableTiming | (g_cad_event_sysfence ? 0u : (unsigned)hipEventDisableSystemFence);
-      // knob "cad_stream_prio": the side stream (the detector / causal-head chain, on the forward's critical path) at
-      // the device's greatest priority, the weight-gradient stream (slack beside the input gradients) at its least
+      // agent-scope release suffices, so the system-scope fence at each record is dropped
+      const unsigned evf = hipEventDisableTiming | (unsigned)hipEventDisableSystemFence;
+      // the side stream (the detector / causal-head chain, on the forward's critical path) at the device's greatest
+      // priority, the weight-gradient stream (slack beside the input gradients) at its least (A/B:
+      // profiles/r03_prio_ab.json)
       int lo = 0, hi = 0;
-      if (g_cad_stream_prio) VAD_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      VAD_HIP(hipStreamCreateWithPriority(&st2, hipStreamNonBlocking, g_cad_stream_prio ? hi : 0));
+      VAD_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+      VAD_HIP(hipStreamCreateWithPriority(&st2, hipStreamNonBlocking, hi));
       VAD_HIP(hipEventCreateWithFlags(&ev_fork, evf));
       VAD_HIP(hipEventCreateWithFlags(&ev_join, evf));
       VAD_HIP(hipEventCreateWithFlags(&ev_det, evf));
-      VAD_HIP(hipStreamCreateWithPriority(&st3, hipStreamNonBlocking, g_cad_stream_prio ? lo : 0));
+      VAD_HIP(hipStreamCreateWithPriority(&st3, hipStreamNonBlocking, lo));
       for (int b = 0; b < 2; ++b) {
         VAD_HIP(hipEventCreateWithFlags(&ev_dy[b], evf));
         VAD_HIP(hipEventCreateWithFlags(&ev_wg[b], evf));
@@ -553,7 +553,7 @@ struct CadPlanImpl {
   int ws_stem = 1, ws_dy_shared = 1, bound = 0;
   void carve_options() {
     ws_stem = stem_grad || !g_stem_fused || !stem_fused_ok(W1);
-    ws_dy_shared = !(dy_per_layer && g_cad_dy_per_layer);
+    ws_dy_shared = !dy_per_layer;
   }
   void carve(Ws& w) {
     const int64_t nf = NF;
@@ -1158,14 +1158,13 @@ struct CadPlanImpl {
     else
       TIMED("avgpool_bwd", avgpool_bwd(d_feat_det, d_pooled, B, T, HF, WF, 256, dA, st));
     VAD_TRY(streams());
-    const bool wgs = wgrad_stream != 0 && g_cad_wgrad_stream;
-    bool st3_joined = false;
+    const bool wgs = wgrad_stream != 0;
     int fused_np = 0;  // layer l's BN-backward partial sums, already written by layer l+1's input gradient
     for (int l = 7; l >= 0; --l) {
       const int64_t M = (int64_t)NF * L[l].OH * L[l].OW;
       const int C = L[l].Co;
       int np = fused_np, nb = 0;
-      const bool perl = dy_per_layer != 0 && g_cad_dy_per_layer != 0;
+      const bool perl = dy_per_layer != 0;
       float* dYl = perl ? dYL[l] : ((l & 1) ? dY2 : dY);
       VAD_CHECK(dYl != nullptr, "backward: dY buffers carved for the other dy_per_layer setting: create a new plan");
       VAD_CHECK((int64_t)bn_rows_parts((int)M, C) * 2 * C <= parts_floats, "backward: BN partial buffer too small");
@@ -1180,23 +1179,17 @@ struct CadPlanImpl {
         // layer 0 with the frozen stem: nothing follows its weight gradient on the caller's stream, so it runs there
         // (after layer 1's weight gradient has released the slab) -- no cross-queue hand-off of dY0 and no join
         // behind it before the optimizer
-        const bool on_main = wgs && l == 0 && !stem_grad && g_cad_last_wgrad_main;
+        const bool on_main = wgs && l == 0 && !stem_grad;
         hipStream_t wst = st;
         if (wgs && !on_main) {
           VAD_HIP(hipEventRecord(ev_dy[l & 1], st));
           VAD_HIP(hipStreamWaitEvent(st3, ev_dy[l & 1], 0));
           wst = st3;
         }
-        // layer 0 on the caller's stream: on a slab of its own (knob cad_l0_slab) it starts right after its BN backward,
-        // beside the end of layer 1's weight gradient (the stream join after the loop orders the optimizer after both);
-        // on the shared slab it waits for layer 1's slab reduce
-        const bool own = on_main && g_cad_l0_slab;
-        if (on_main && !own) {
-          VAD_HIP(hipStreamWaitEvent(st, ev_wg[1], 0));  // layer 1's weight gradient + slab reduce are done
-          st3_joined = true;  // (the weight-gradient stream's last work)
-        }
-        float* slab = own ? wpart0 : wpart;
-        const int64_t slab_cap = own ? wpart0_floats : wpart_floats;
+        // layer 0 on the caller's stream: on a slab of its own it starts right after its BN backward, beside the end of
+        // layer 1's weight gradient (the stream join after the loop orders the optimizer after both)
+        float* slab = on_main ? wpart0 : wpart;
+        const int64_t slab_cap = on_main ? wpart0_floats : wpart_floats;
         hipStream_t st = wst;
         int ns = 0;
         // (layer 0 with the frozen stem: little runs beside its weight gradient)
@@ -1216,7 +1209,7 @@ struct CadPlanImpl {
       }
       if (l == debug_stop_layer) break;
     }
-    if (wgs && !st3_joined) {  // every weight gradient is final before the stem backward / optimizer
+    if (wgs) {  // every weight gradient is final before the stem backward / optimizer
       VAD_HIP(hipEventRecord(ev_wgj, st3));
       VAD_HIP(hipStreamWaitEvent(st, ev_wgj, 0));
     }
@@ -1227,7 +1220,7 @@ struct CadPlanImpl {
       VAD_CHECK(y1_fresh, "stem backward: the forward ran with the stem frozen (set option stem_grad before it)");
       // the stem (cad:145-147): input gradient of layer1.0 into the pooled map, MaxPool2d backward, bn1 backward (in
       // place), conv1 weight gradient (its bias gradient comes from the bn1 finalize)
-      TIMED("stem_bwd", conv3_dgrad(L[0], (dy_per_layer && g_cad_dy_per_layer) ? dYL[0] : dY, wd[0], dA, st));
+      TIMED("stem_bwd", conv3_dgrad(L[0], dy_per_layer ? dYL[0] : dY, wd[0], dA, st));
       TIMED("stem_bwd", maxpool3s2_bwd(y1, stats[0], dA, NF, H1, W1, 32, HP, WP, stem_d, st));
       const int64_t M1 = (int64_t)NF * H1 * W1;
       int np = 0;
@@ -1608,7 +1601,7 @@ int vad_cad_debug_buffer(vad_cad_plan* plan, const char* name, int idx, void** p
   else if (n == "dA") { *ptr = c.dA; *nfloats = c.act_max; }
   else if (n == "dY") {
     const int l = c.debug_stop_layer;
-    const bool perl = c.dy_per_layer && g_cad_dy_per_layer && l >= 0 && l < 8;
+    const bool perl = c.dy_per_layer && l >= 0 && l < 8;
     *ptr = perl ? c.dYL[l] : ((l & 1) ? c.dY2 : c.dY);
     *nfloats = perl ? (int64_t)c.NF * c.L[l].OH * c.L[l].OW * c.L[l].Co : c.act_max;
   }

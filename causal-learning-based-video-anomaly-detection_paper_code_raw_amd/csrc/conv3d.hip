@@ -268,8 +268,6 @@ __global__ __launch_bounds__(256) void maxpool3d_bwd_win_kernel(const float* __r
   }
 }
 
-int g_maxpool_bwd_win = 1;  // knob "maxpool3d_bwd_win": one thread per window (0: one per input element)
-
 int maxpool3d_bwd(const float* y, const float* stats, int relu, const Vol5& v, int kd, int kh, int kw,
                   const float* dout, float* dA, hipStream_t st) {
   const int64_t total = v.numel();

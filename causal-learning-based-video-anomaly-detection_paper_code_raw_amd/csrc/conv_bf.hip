@@ -894,12 +894,10 @@ __global__ __launch_bounds__(256, 2) void bfc_dgrad_s2_kernel(const BfcArgs p) {
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
-int g_bfc = 1;             // knob "conv_bfc": config-4 forwards / stride-1 input gradients on these kernels
-int g_bfc_blocks = 512;    // knob "conv_bfc_blocks": target grid (persistent blocks over the tiles)
-int g_bfc_s2_ni2 = 1;      // knob "conv_bfc_s2_ni2": stride-2 input gradients of class grids <= 8 wide on 2-frame tiles
+constexpr int BFC_BLOCKS = 512;  // target grid (persistent blocks over the tiles)
 
 bool bfc_supported(const Conv3Layer& L, bool fwd) {
-  if (!g_bfc || !g_conv_bf16 || !g_act_bf16) return false;
+  if (!g_conv_bf16 || !g_act_bf16) return false;
   if (L.stride != 1 && L.stride != 2) return false;
   if (!fwd && L.stride == 2)  // the parity-class kernel: dX exactly 2x the dY grid (padding 1)
     return L.Co % 16 == 0 && L.Ci % 32 == 0 && L.OH == (L.IH - 1) / 2 + 1 && L.OW == (L.IW - 1) / 2 + 1;
@@ -916,7 +914,7 @@ static int bfc_launch(BfcArgs a, int64_t max_blocks, hipStream_t st, int* nparts
   a.tiles_w = (int)cdiv(a.OW, TW);
   a.ntiles = (int)(cdiv(a.NF, NI) * a.tiles_h * a.tiles_w);
   const int ny = a.N / (32 * NCT);
-  const int64_t target = std::max<int64_t>(1, std::min<int64_t>(max_blocks, cdiv(g_bfc_blocks, ny)));
+  const int64_t target = std::max<int64_t>(1, std::min<int64_t>(max_blocks, cdiv(BFC_BLOCKS, ny)));
   a.tpb = (int)cdiv(a.ntiles, target);
   const int gx = (int)cdiv(a.ntiles, a.tpb);
   if (a.C == CB) VAD_KLAUNCH((bfc_conv_kernel<S, NI, TH, TW, CB, NCT, FWD, true>), dim3(gx, ny), dim3(256), 0, st, a);
@@ -994,13 +992,13 @@ int bfc_dgrad(const Conv3Layer& L, const __bf16* dY, const __bf16* wdb, __bf16* 
   if (L.stride == 2) {
     // class grids 8 wide or less (the 8 x 8 dY maps of config 4's last stride-2 layer): two frames' 8 x 8 tiles per
     // block tile instead of a half-empty 8 x 16 one
-    const int ni = (L.IW + 1) / 2 <= 8 && g_bfc_s2_ni2 ? 2 : 1;
+    const int ni = (L.IW + 1) / 2 <= 8 ? 2 : 1;
     const int TH = 8, TW = 16 / ni;
     a.tiles_h = (int)cdiv((L.IH + 1) / 2, TH);
     a.tiles_w = (int)cdiv((L.IW + 1) / 2, TW);
     a.ntiles = (int)cdiv(L.NF, ni) * a.tiles_h * a.tiles_w;
     const int ny = L.Ci / 32;
-    const int64_t target = std::max<int64_t>(1, std::min<int64_t>(mb, cdiv(g_bfc_blocks, ny)));
+    const int64_t target = std::max<int64_t>(1, std::min<int64_t>(mb, cdiv(BFC_BLOCKS, ny)));
     a.tpb = (int)cdiv(a.ntiles, target);
     const int gx = (int)cdiv(a.ntiles, a.tpb);
     if (ni == 2) {
@@ -1018,7 +1016,7 @@ int bfc_dgrad(const Conv3Layer& L, const __bf16* dY, const __bf16* wdb, __bf16* 
 }
 
 bool bfc_wgrad_supported(const Conv3Layer& L) {
-  return g_bfc && g_conv_bf16 && g_act_bf16 && (L.stride == 1 || L.stride == 2) && L.Ci % 32 == 0 && L.Co % 32 == 0;
+  return g_conv_bf16 && g_act_bf16 && (L.stride == 1 || L.stride == 2) && L.Ci % 32 == 0 && L.Co % 32 == 0;
 }
 
 template <int S, int NI, int TH, int TW, int NCO>
@@ -1036,7 +1034,7 @@ static int bfw_launch(BfwArgs a, int target_blocks, int64_t partial_cap, hipStre
   return 0;
 }
 
-int g_bfw_blocks = 384;  // knob "conv_bfw_blocks": target grid of the bf16 weight gradients (sweep: 384 best)
+constexpr int BFW_BLOCKS = 384;  // target grid of the bf16 weight gradients (sweep: 384 best)
 
 int bfc_wgrad(const Conv3Layer& L, const __bf16* dY, const __bf16* src, const float* src_stats, float* slab,
               int* nsplit, int64_t partial_cap, hipStream_t st) {
@@ -1051,7 +1049,7 @@ int bfc_wgrad(const Conv3Layer& L, const __bf16* dY, const __bf16* src, const fl
   a.shift = src_stats ? src_stats + 3 * L.Ci : nullptr;
   a.slab = slab;
   a.NF = L.NF; a.IH = L.IH; a.IW = L.IW; a.Ci = L.Ci; a.OH = L.OH; a.OW = L.OW; a.Co = L.Co;
-  const int tb = g_bfw_blocks;
+  const int tb = BFW_BLOCKS;
   const bool c64 = L.Co % 64 == 0;
   if (L.stride == 2) {
     VAD_CHECK(L.IH >= 2 * L.OH - 1 && L.IW >= 2 * L.OW - 1, "bfc_wgrad: stride-2 geometry");

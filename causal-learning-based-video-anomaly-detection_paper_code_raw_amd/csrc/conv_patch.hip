@@ -466,8 +466,6 @@ static int launch_patch(PatchArgs a, hipStream_t st, int* nparts) {
   return 0;
 }
 
-int g_patch_persist = 1;  // tuning knob "conv_patch_persist"
-
 // tile geometry per output size (128 pixels per block): 0 -> 2 images x 8x8, 1 -> 8x16, 2 -> 4x32
 static int patch_geom(int OH, int OW) { return (OH <= 8 && OW <= 8) ? 0 : (OW <= 16 ? 1 : 2); }
 

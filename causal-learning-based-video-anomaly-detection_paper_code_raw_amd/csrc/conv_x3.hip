@@ -453,7 +453,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv3x3_x3_kernel(const X3Arg
   }
 }
 
-// Software-pipelined stride-1 variant (knob "conv_split_pipe"): 32 output channels per block, two LDS patch images
+// Software-pipelined stride-1 variant (the 32-channel forwards): 32 output channels per block, two LDS patch images
 // (and two weight-slice images when the slice is restaged per item), ONE barrier per item.  While the waves multiply
 // item k out of image k & 1, they stage item k+1 -- loaded into registers one item earlier -- into the other image,
 // the staging pieces (BN+ReLU on load, the three-way split, the LDS stores) placed between the taps' MFMAs so the
@@ -739,7 +739,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
   }
 }
 
-int g_x3_dgrad_blocks = 512;  // knob "conv_dgrad_blocks"
+constexpr int X3_DGRAD_BLOCKS = 512;  // target grid of the input gradients (as the forwards': 2 blocks per CU)
 
 template <int S, int NI, int TH, int TW, int NT, int PC, bool FWD, int NP, int WCH = 1, int NW = 4>
 static int launch_np(X3Args a, int max_blocks, hipStream_t st, int* nparts) {
@@ -751,9 +751,8 @@ static int launch_np(X3Args a, int max_blocks, hipStream_t st, int* nparts) {
   a.tiles_w = (int)cdiv(a.OW, TW);
   a.ntiles = (int)(cdiv(a.NF, NI) * a.tiles_h * a.tiles_w);
   const int ny = (int)cdiv(a.N, 32 * NT);
-  // 2 resident blocks per CU over 256 CUs (input gradients: knob "conv_dgrad_blocks", they share the GPU with the
-  // weight gradients)
-  const int target = std::max(1, std::min(max_blocks, (FWD ? 512 : g_x3_dgrad_blocks) * 4 / NW / ny));
+  // 2 resident blocks per CU over 256 CUs (the input gradients share the GPU with the weight gradients)
+  const int target = std::max(1, std::min(max_blocks, (FWD ? 512 : X3_DGRAD_BLOCKS) * 4 / NW / ny));
   a.tpb = (int)cdiv(a.ntiles, target);
   const int gx = (int)cdiv(a.ntiles, a.tpb);
   if constexpr (NP == 1) {
@@ -770,18 +769,11 @@ static int launch_np(X3Args a, int max_blocks, hipStream_t st, int* nparts) {
   return 0;
 }
 
-int g_conv_split = 1;  // tuning knob "conv_split": 1 = split-bf16 patch kernels where supported, 0 = f32 MFMA
-thread_local int g_conv_bf16 = 0;  // bf16-operand convs (one plane, one product; set per plan, see ConvPrecision)
-thread_local int g_act_bf16 = 0;   // bf16 activation storage (set per plan, see ActStorage)
-int g_x3_nt = 0;       // tuning knob "conv_split_nt": 0 = auto, 1 / 2 = force 32 / 64 output channels per block
-
-
-int g_x3_wres = 1;  // knob "conv_split_wres": 32-channel stride-1 layers keep all split weights resident in LDS
-
+// 32-channel stride-1 layers keep all split weights resident in LDS (WCH = 2); other widths restage them per chunk
 template <int S, int NI, int TH, int TW, int NT, int PC, bool FWD, int NW = 4>
 static int launch_x3(X3Args a, int max_blocks, hipStream_t st, int* nparts) {
   if constexpr (S == 1 && NT == 1) {
-    if (g_x3_wres && a.C == 2 * PC) {
+    if (a.C == 2 * PC) {
       if (g_conv_bf16) return launch_np<S, NI, TH, TW, NT, PC, FWD, 1, 2, NW>(a, max_blocks, st, nparts);
       return launch_np<S, NI, TH, TW, NT, PC, FWD, 3, 2, NW>(a, max_blocks, st, nparts);
     }
@@ -790,14 +782,13 @@ static int launch_x3(X3Args a, int max_blocks, hipStream_t st, int* nparts) {
   return launch_np<S, NI, TH, TW, NT, PC, FWD, 3, 1, NW>(a, max_blocks, st, nparts);
 }
 
-// knob "conv_split_pipe": stride-1 layers on the software-pipelined kernel (conv3x3_x3p_kernel); bit 0 forwards, bit 1
-// input gradients (these share the CUs with the weight gradients, which a 132 KB block leaves no LDS for)
-int g_x3_pipe = 1;
-
-template <int NI, int TH, int TW, bool FWD, int NP, int WCH>
+// stride-1 forwards on the software-pipelined kernel (conv3x3_x3p_kernel).  Not the input gradients: these share the
+// CUs with the weight gradients, which a 132 KB block leaves no LDS for.  fp32 numerics only (three split planes): of
+// the kernel template's arms only FWD = true, NP = 3, fp32 activations are instantiated
+template <int NI, int TH, int TW, int WCH>
 static int launch_pipe(X3Args a, int max_blocks, hipStream_t st, int* nparts) {
-  constexpr int PC = 16, NW = 8;
-  VAD_CHECK(!g_act_bf16 || NP == 1, "conv3x3_x3p: bf16 activations need the bf16-operand kernels (conv_bf16)");
+  constexpr int PC = 16, NW = 8, NP = 3;
+  VAD_CHECK(!g_act_bf16 && !g_conv_bf16, "conv3x3_x3p: fp32 operands and activations only");
   VAD_CHECK(a.C % PC == 0 && a.C <= 256 && (WCH == 1 ? a.C > PC : a.C == WCH * PC), "conv3x3_x3p: channel count");
   VAD_CHECK((int64_t)a.NF * a.IH * a.IW * a.C < ((int64_t)1 << 31), "conv3x3_x3p: 32-bit staging offsets");
   a.tiles_h = (int)cdiv(a.OH, TH);
@@ -805,52 +796,41 @@ static int launch_pipe(X3Args a, int max_blocks, hipStream_t st, int* nparts) {
   a.ntiles = (int)(cdiv(a.NF, NI) * a.tiles_h * a.tiles_w);
   const int ny = (int)cdiv(a.N, 32);
   // one 512-thread block per CU (two patch images + weights: 98-132 KB of LDS)
-  const int target = std::max(1, std::min(max_blocks, (FWD ? 256 : g_x3_dgrad_blocks / 2) / ny));
+  const int target = std::max(1, std::min(max_blocks, 256 / ny));
   a.tpb = (int)cdiv(a.ntiles, target);
   const int gx = (int)cdiv(a.ntiles, a.tpb);
-  if (NP == 1 && g_act_bf16)
-    VAD_KLAUNCH((conv3x3_x3p_kernel<NI, TH, TW, PC, FWD, NP, WCH, NW, NP == 1>), dim3(gx, ny), dim3(64 * NW), 0, st, a);
-  else
-    VAD_KLAUNCH((conv3x3_x3p_kernel<NI, TH, TW, PC, FWD, NP, WCH, NW>), dim3(gx, ny), dim3(64 * NW), 0, st, a);
+  VAD_KLAUNCH((conv3x3_x3p_kernel<NI, TH, TW, PC, true, NP, WCH, NW>), dim3(gx, ny), dim3(64 * NW), 0, st, a);
   VAD_LAUNCH_CHECK();
   if (nparts) *nparts = gx;
   return 0;
 }
 
-template <int NI, int TH, int TW, bool FWD>
+template <int NI, int TH, int TW>
 static int dispatch_pipe_np(const X3Args& a, int max_blocks, hipStream_t st, int* nparts) {
-  const bool wres = g_x3_wres && a.C == 32;
-  if (g_conv_bf16)
-    return wres ? launch_pipe<NI, TH, TW, FWD, 1, 2>(a, max_blocks, st, nparts)
-                : launch_pipe<NI, TH, TW, FWD, 1, 1>(a, max_blocks, st, nparts);
-  return wres ? launch_pipe<NI, TH, TW, FWD, 3, 2>(a, max_blocks, st, nparts)
-              : launch_pipe<NI, TH, TW, FWD, 3, 1>(a, max_blocks, st, nparts);
+  // 32 channels: all split weights resident in LDS
+  return a.C == 32 ? launch_pipe<NI, TH, TW, 2>(a, max_blocks, st, nparts)
+                   : launch_pipe<NI, TH, TW, 1>(a, max_blocks, st, nparts);
 }
 
-template <bool FWD>
 static int dispatch_pipe(const X3Args& a, int max_blocks, hipStream_t st, int* nparts) {
-  if (a.OH <= 8 && a.OW <= 8) return dispatch_pipe_np<4, 8, 8, FWD>(a, max_blocks, st, nparts);
-  if (a.OW <= 16) return dispatch_pipe_np<2, 8, 16, FWD>(a, max_blocks, st, nparts);
-  return dispatch_pipe_np<1, 8, 32, FWD>(a, max_blocks, st, nparts);
+  if (a.OH <= 8 && a.OW <= 8) return dispatch_pipe_np<4, 8, 8>(a, max_blocks, st, nparts);
+  if (a.OW <= 16) return dispatch_pipe_np<2, 8, 16>(a, max_blocks, st, nparts);
+  return dispatch_pipe_np<1, 8, 32>(a, max_blocks, st, nparts);
 }
 
-int g_x3_big = 1;  // knob "conv_split_big": stride-1 layers on 256-pixel tiles, 512-thread blocks (NW = 8)
-int g_x3_s2big = 1;  // knob "conv_split_s2big": fp32 stride-2 forwards on 256-pixel tiles, 8 waves, 32 channels
-
-
+// stride 1: 256-pixel tiles, 512-thread blocks (NW = 8); stride 2: 128-pixel tiles of 4 waves
 template <int S, bool FWD, int NT>
 static int dispatch_x3_nt(const X3Args& a, int max_blocks, hipStream_t st, int* nparts) {
   const int OH = a.OH, OW = a.OW;
   if constexpr (S == 1) {
-    if (g_x3_big) {
-      if (OH <= 8 && OW <= 8) return launch_x3<S, 4, 8, 8, NT, 16, FWD, 8>(a, max_blocks, st, nparts);
-      if (OW <= 16) return launch_x3<S, 2, 8, 16, NT, 16, FWD, 8>(a, max_blocks, st, nparts);
-      return launch_x3<S, 1, 8, 32, NT, 16, FWD, 8>(a, max_blocks, st, nparts);
-    }
+    if (OH <= 8 && OW <= 8) return launch_x3<S, 4, 8, 8, NT, 16, FWD, 8>(a, max_blocks, st, nparts);
+    if (OW <= 16) return launch_x3<S, 2, 8, 16, NT, 16, FWD, 8>(a, max_blocks, st, nparts);
+    return launch_x3<S, 1, 8, 32, NT, 16, FWD, 8>(a, max_blocks, st, nparts);
+  } else {
+    if (OH <= 8 && OW <= 8) return launch_x3<S, 2, 8, 8, NT, 16, FWD>(a, max_blocks, st, nparts);
+    if (OW <= 16) return launch_x3<S, 1, 8, 16, NT, 16, FWD>(a, max_blocks, st, nparts);
+    return launch_x3<S, 1, 4, 32, NT, 16, FWD>(a, max_blocks, st, nparts);
   }
-  if (OH <= 8 && OW <= 8) return launch_x3<S, 2, 8, 8, NT, 16, FWD>(a, max_blocks, st, nparts);
-  if (OW <= 16) return launch_x3<S, 1, 8, 16, NT, 16, FWD>(a, max_blocks, st, nparts);
-  return launch_x3<S, 1, 4, 32, NT, 16, FWD>(a, max_blocks, st, nparts);
 }
 
 template <int S, bool FWD>
@@ -859,24 +839,20 @@ static int dispatch_x3(const X3Args& a, int max_blocks, hipStream_t st, int* npa
     // fp32 numerics (three split planes): a 128-pixel stride-2 tile needs a 4.5x larger patch than its output, so the
     // 4-wave block's LDS (patch + 64-channel weight slice, 121 KB) allows one block -- one wave per SIMD -- per CU.
     // 256-pixel tiles of 8 waves over 32 output channels fit 152-158 KB: two waves per SIMD
-    if (g_x3_s2big && !g_conv_bf16) {
+    if (!g_conv_bf16) {
       if (a.OH <= 8 && a.OW <= 8) return launch_x3<2, 4, 8, 8, 1, 16, FWD, 8>(a, max_blocks, st, nparts);
       if (a.OW <= 16) return launch_x3<2, 2, 8, 16, 1, 16, FWD, 8>(a, max_blocks, st, nparts);
       return launch_x3<2, 1, 8, 32, 1, 16, FWD, 8>(a, max_blocks, st, nparts);
     }
   }
-  int nt = g_x3_nt;
-  if (nt == 0) {
-    // 64 channels per block halves the fragment reads per MFMA; keep 32 when that would leave the chip underfull
-    const int64_t tiles = conv3_patch_blocks(a.NF, a.OH, a.OW);
-    // (stride 2: the 4x larger input patch per tile makes sharing it over 64 channels pay even on a small grid)
-    nt = (a.N % 64 == 0 && (S == 2 || tiles * (a.N / 64) >= 512)) ? 2 : 1;
-  }
-  if constexpr (S == 1) {
+  // 64 channels per block halves the fragment reads per MFMA; keep 32 when that would leave the chip underfull
+  const int64_t tiles = conv3_patch_blocks(a.NF, a.OH, a.OW);
+  // (stride 2: the 4x larger input patch per tile makes sharing it over 64 channels pay even on a small grid)
+  const int nt = (a.N % 64 == 0 && (S == 2 || tiles * (a.N / 64) >= 512)) ? 2 : 1;
+  if constexpr (S == 1 && FWD) {
     // 32-channel blocks: the pipelined kernel (measured: L0/L1 -1..-3 us, L7 -5 us; on the layers that take 64
     // channels per block it would lose the patch sharing, +10 us each: profiles/r03_pipe_ab.json)
-    if ((g_x3_pipe & (FWD ? 1 : 2)) && nt == 1 && a.C <= 256 && a.C > 16 && g_x3_big && !g_conv_bf16)
-      return dispatch_pipe<FWD>(a, max_blocks, st, nparts);
+    if (nt == 1 && a.C <= 256 && a.C > 16 && !g_conv_bf16) return dispatch_pipe(a, max_blocks, st, nparts);
   }
   return nt == 2 ? dispatch_x3_nt<S, FWD, 2>(a, max_blocks, st, nparts)
                  : dispatch_x3_nt<S, FWD, 1>(a, max_blocks, st, nparts);
@@ -1237,15 +1213,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_dgrad_s2x3_kernel(const X3Args
   }
 }
 
-int g_dgrad_s2_x3 = 1;  // tuning knob "conv_dgrad_s2_x3": stride-2 input gradients on the split-bf16 kernel
-
 bool conv3_x3_dgrad_s2_supported(const Conv3Layer& L) {
   return g_conv_split && g_dgrad_s2_x3 && L.stride == 2 && L.Co % 16 == 0 && L.Ci % 32 == 0 &&
          L.OH == (L.IH - 1) / 2 + 1 && L.OW == (L.IW - 1) / 2 + 1;
 }
-
-int g_dgrad_s2_w3 = 1;
-int g_dgrad_s2_nt = 1;  // knob "conv_dgrad_s2_nt": 1 = 32 input channels per block (default: config-2 layer 4 92 -> 75 us, profiles/r04_s2_nt_ab.json), 0 = 64 where the grid allows
 
 bool conv3_dgrad_w3_wanted(const Conv3Layer& L) {
   return g_dgrad_s2_w3 && !g_conv_bf16 && conv3_x3_dgrad_s2_supported(L);
@@ -1272,24 +1243,20 @@ int conv3_x3_dgrad_s2(const Conv3Layer& L, const float* dY, const float* wd, flo
   a.tiles_h = (int)cdiv((L.IH + 1) / 2, 8);
   a.tiles_w = (int)cdiv((L.IW + 1) / 2, 8);
   const int tiles = L.NF * a.tiles_h * a.tiles_w;
-  // 64 input channels per block where that still gives >= 2 blocks per CU, else 32
-  const bool nt2 = g_dgrad_s2_nt != 1 && L.Ci % 64 == 0 && (int64_t)tiles * (L.Ci / 64) >= 512;
-  dim3 grid((unsigned)tiles, (unsigned)(L.Ci / (nt2 ? 64 : 32)));
+  // 32 input channels per block (against 64 where the grid allows: config-2 layer 4 92 -> 75 us,
+  // profiles/r04_s2_nt_ab.json)
+  dim3 grid((unsigned)tiles, (unsigned)(L.Ci / 32));
   VAD_CHECK(!g_act_bf16 || g_conv_bf16, "conv3_x3_dgrad_s2: bf16 activations need conv_bf16");
   if (f) *f->nparts = tiles;
   if (g_conv_bf16 && g_act_bf16) {
-    if (nt2) VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<2, 16, 1, true>), grid, dim3(256), 0, st, a);
-    else VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<1, 16, 1, true>), grid, dim3(256), 0, st, a);
+    VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<1, 16, 1, true>), grid, dim3(256), 0, st, a);
   } else if (g_conv_bf16) {
-    if (nt2) VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<2, 16, 1>), grid, dim3(256), 0, st, a);
-    else VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<1, 16, 1>), grid, dim3(256), 0, st, a);
+    VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<1, 16, 1>), grid, dim3(256), 0, st, a);
   } else if (w3) {
     a.w3 = w3;
-    if (nt2) VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<2, 16, 3, false, true>), grid, dim3(256), 0, st, a);
-    else VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<1, 16, 3, false, true>), grid, dim3(256), 0, st, a);
+    VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<1, 16, 3, false, true>), grid, dim3(256), 0, st, a);
   } else {
-    if (nt2) VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<2, 16, 3>), grid, dim3(256), 0, st, a);
-    else VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<1, 16, 3>), grid, dim3(256), 0, st, a);
+    VAD_KLAUNCH((conv3x3_dgrad_s2x3_kernel<1, 16, 3>), grid, dim3(256), 0, st, a);
   }
   VAD_LAUNCH_CHECK();
   return 0;
@@ -1815,26 +1782,22 @@ static int launch_wgrad_x3nt(WgX3Args a, int target_blocks, int64_t partial_cap,
   return 0;
 }
 
-template <int S, int TH, int TW>
-static int launch_wgrad_x3nt_co(WgX3Args a, int nt, int target_blocks, int64_t partial_cap, hipStream_t st,
-                                int* nsplit) {
-  if (nt == 4 && a.Co % 128 == 0) return launch_wgrad_x3nt<S, TH, TW, 4>(a, target_blocks, partial_cap, st, nsplit);
-  return launch_wgrad_x3nt<S, TH, TW, 2>(a, target_blocks, partial_cap, st, nsplit);
+// stride 2: four 32-channel co tiles per block where Co allows, else two
+template <int TH, int TW>
+static int launch_wgrad_x3nt_s2(WgX3Args a, int target_blocks, int64_t partial_cap, hipStream_t st, int* nsplit) {
+  if (a.Co % 128 == 0) return launch_wgrad_x3nt<2, TH, TW, 4>(a, target_blocks, partial_cap, st, nsplit);
+  return launch_wgrad_x3nt<2, TH, TW, 2>(a, target_blocks, partial_cap, st, nsplit);
 }
 
-int g_wgrad_split = 1;     // tuning knob "conv_wgrad_split": stride-1 weight gradients on the split-bf16 kernel
-int g_wgrad_split_s2 = 1;  // tuning knob "conv_wgrad_split_s2": stride-2 weight gradients on the split-bf16 kernel
-int g_wgrad_s2_blocks = 384;  // tuning knob "conv_wgrad_s2_blocks": their target grid size (sweep: profiles/r02_wgrad_grid_sweep.json)
-int g_wgrad_s1_nt = 2;  // tuning knob "conv_wgrad_s1_nt": stride-1 frames <= 16 wide on the multi-co-tile kernel (2|4)
-int g_wgrad_s1_nt_wide = 0;  // knob "conv_wgrad_s1_nt_wide": wider stride-1 frames too (2x32 tiles)
-int g_wgrad_s1_nt_blocks = 384;  // knob "conv_wgrad_s1_nt_blocks"
+constexpr int WGRAD_S2_BLOCKS = 384;  // target grid of the stride-2 weight gradients (sweep: profiles/r02_wgrad_grid_sweep.json)
+constexpr int WGRAD_S1_NT_BLOCKS = 384;  // and of the stride-1 ones on the multi-co-tile kernel
 
 bool conv3_wgrad_x3_supported(const Conv3Layer& L) {
   if (!g_conv_split || L.Ci % 32 != 0 || L.Co % 32 != 0) return false;
   if (L.stride == 2) return g_wgrad_split_s2 != 0 && L.Co % 64 == 0;
   // (8x8 frames: 64-pixel tiles carry too little MFMA work per staged patch; the f32 patch kernel is faster there)
   return L.stride == 1 && g_wgrad_split &&
-         (L.OH > 8 || L.OW > 8 || g_wgrad_split == 2 || g_conv_bf16 || (g_wgrad_s1_nt && L.Co % 64 == 0));
+         (L.OH > 8 || L.OW > 8 || g_wgrad_split == 2 || g_conv_bf16 || L.Co % 64 == 0);
 }
 
 int conv3_wgrad_x3(const Conv3Layer& L, const float* dY, const float* src, const float* src_stats, float* slab,
@@ -1850,16 +1813,14 @@ int conv3_wgrad_x3(const Conv3Layer& L, const float* dY, const float* src, const
   a.NF = L.NF; a.IH = L.IH; a.IW = L.IW; a.Ci = L.Ci; a.OH = L.OH; a.OW = L.OW; a.Co = L.Co;
   if (L.stride == 2) {
     VAD_CHECK(L.IH >= 2 * L.OH - 1 && L.IW >= 2 * L.OW - 1, "conv3_wgrad_x3: stride-2 geometry");
-    target_blocks = g_wgrad_s2_blocks;
-    if (L.OW > 16) return launch_wgrad_x3nt_co<2, 1, 32>(a, 4, target_blocks, partial_cap, st, nsplit);
-    if (L.OW > 8) return launch_wgrad_x3nt_co<2, 2, 16>(a, 4, target_blocks, partial_cap, st, nsplit);
-    return launch_wgrad_x3nt_co<2, 4, 8>(a, 4, target_blocks, partial_cap, st, nsplit);
+    if (L.OW > 16) return launch_wgrad_x3nt_s2<1, 32>(a, WGRAD_S2_BLOCKS, partial_cap, st, nsplit);
+    if (L.OW > 8) return launch_wgrad_x3nt_s2<2, 16>(a, WGRAD_S2_BLOCKS, partial_cap, st, nsplit);
+    return launch_wgrad_x3nt_s2<4, 8>(a, WGRAD_S2_BLOCKS, partial_cap, st, nsplit);
   }
-  if (g_wgrad_s1_nt && L.Co % 64 == 0 && (L.OW <= 16 || g_wgrad_s1_nt_wide)) {
-    if (L.OW > 16) return launch_wgrad_x3nt_co<1, 2, 32>(a, g_wgrad_s1_nt, g_wgrad_s1_nt_blocks, partial_cap, st, nsplit);
-    if (L.OW <= 8 && L.OH <= 8)
-      return launch_wgrad_x3nt_co<1, 8, 8>(a, g_wgrad_s1_nt, g_wgrad_s1_nt_blocks, partial_cap, st, nsplit);
-    return launch_wgrad_x3nt_co<1, 4, 16>(a, g_wgrad_s1_nt, g_wgrad_s1_nt_blocks, partial_cap, st, nsplit);
+  // stride-1 frames <= 16 wide: the multi-co-tile kernel, two 32-channel tiles per block
+  if (L.Co % 64 == 0 && L.OW <= 16) {
+    if (L.OW <= 8 && L.OH <= 8) return launch_wgrad_x3nt<1, 8, 8, 2>(a, WGRAD_S1_NT_BLOCKS, partial_cap, st, nsplit);
+    return launch_wgrad_x3nt<1, 4, 16, 2>(a, WGRAD_S1_NT_BLOCKS, partial_cap, st, nsplit);
   }
   if (L.OH <= 8 && L.OW <= 8) return launch_wgrad_x3<1, 8, 8>(a, target_blocks, partial_cap, st, nsplit);
   if (L.OW <= 16) return launch_wgrad_x3<1, 8, 16>(a, target_blocks, partial_cap, st, nsplit);

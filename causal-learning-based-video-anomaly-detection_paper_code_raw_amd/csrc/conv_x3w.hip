@@ -292,9 +292,6 @@ __global__ __launch_bounds__(256, 2) void x3_wgrad_tr_kernel(const TrwArgs p) {
       for (int r = 0; r < 4; ++r) out[(int64_t)(cob + 16 * u + r) * 9 * p.Ci + t * p.Ci + cic] = acc[t][u][r];
 }
 
-int g_wgrad_tr = 1;           // knob "conv_wgrad_tr": fp32 weight gradients on x3_wgrad_tr_kernel
-int g_wgrad_tr_blocks = 384;  // knob "conv_wgrad_tr_blocks": its target grid (1.5 blocks per CU: they share the CUs with the input gradients)
-
 bool x3_wgrad_tr_supported(const Conv3Layer& L) {
   const int64_t lim = (int64_t)1 << 31;
   return g_wgrad_tr && g_conv_split && !g_conv_bf16 && !g_act_bf16 && (L.stride == 1 || L.stride == 2) &&
@@ -302,9 +299,6 @@ bool x3_wgrad_tr_supported(const Conv3Layer& L) {
          (int64_t)L.NF * L.OH * L.OW * L.Co * 4 < lim - 64 && (int64_t)L.NF * L.IH * L.IW * L.Ci * 4 < lim - 64 &&
          L.OH < 256 && L.OW < 256;
 }
-
-int g_wgrad_tr_pft = 0;  // knob "conv_wgrad_tr_pft": the next tap's input fragments read before this tap's MFMAs (off:
-                         // config-2 step 1.696 ms off vs 1.72-1.74 on, profiles/r05_prefetch_ab.json)
 
 template <int S, int NI, int TH, int TW, int NCO>
 static int trw_launch(TrwArgs a, int target_blocks, int64_t partial_cap, hipStream_t st, int* nsplit) {

@@ -1,6 +1,7 @@
 // Fused MLP chains (detector_net / direct_classifier) and the generic row-reduction weight gradient.
 #pragma once
 #include "common.h"
+#include "tuning.h"
 #include "weight_images.h"
 
 namespace vad {
@@ -45,8 +46,6 @@ struct MlpTailBwdArgs {
   const int* skip;     // nullable device flag: 0 -> no-op
 };
 
-extern int g_mlp_tail_wide;  // knob "mlp_tail_wide"
-extern int g_mlp_tail_rb;    // knob "mlp_tail_rb"
 int mlp_tail_fwd(const MlpTailArgs& a, hipStream_t st);
 // its host checks alone (layer shapes, rows per block): for a caller that queues work of its own in front of it
 int mlp_tail_fwd_check(const MlpTailArgs& a);

@@ -563,10 +563,6 @@ int dir_combine(const DirCombineArgs& a, hipStream_t st) {
 
 static int mlp_rb(int M) { return M >= 64 ? 4 : 8; }
 
-int g_mlp_tail_rb = 0;  // knob "mlp_tail_rb": rows per block of the detector's layers 1-4 (0: auto)
-int g_mlp_tail_wide = 1;  // knob "mlp_tail_wide": 1024-thread blocks for the detector's layers 1-4 (4 x the K-slices
-                          // and split-K loads in flight of 256 threads; profiles/r03_mlp_tail_sweep.txt)
-
 int mlp_tail_fwd_check(const MlpTailArgs& a) {
   for (int i = 1; i < 5; ++i)
     VAD_CHECK(a.L[i].N <= MLP_MAXW && a.L[i].N % 4 == 0 && a.L[i].N / 4 <= 256 && a.L[i].K <= MLP_MAXW &&

@@ -46,6 +46,8 @@ extern "C" int vad_conv3x3_wgrad(const float* x_nhwc, const float* dy_nhwc, int 
 }
 
 extern "C" int vad_set_tuning(const char* key, int value) { return vad::set_tuning(key, value); }
+extern "C" int vad_get_tuning(const char* key, int* value) { return vad::get_tuning(key, value); }
+extern "C" const char* vad_tuning_name(int i) { return vad::tuning_name(i); }
 
 // The BN backward apply pass alone (measurement / tests): dY = k (dZ - mean dZ - xhat mean(dZ xhat)), dZ = dA masked by
 // the ReLU of s y + t; stats = the layer's [7 C] BN state; bf16: dA / y / dY stored as bf16 (config 4).

@@ -240,8 +240,6 @@ __global__ __launch_bounds__(256, 4) void stem_fused_kernel(const float* __restr
 
 }  // namespace
 
-int g_stem_fused = 1;  // tuning knob "stem_fused": the frozen stem's forward without the conv1 activation
-
 static int stem_pitch(int OW) { return (int)cdiv(2 * OW + 6, 8) * 8; }
 static size_t stem_lds(int OW) { return (size_t)3 * (2 * (2 * ST_PB + 1) + 6) * stem_pitch(OW) * sizeof(__bf16); }
 

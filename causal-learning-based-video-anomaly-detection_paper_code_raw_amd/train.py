@@ -52,7 +52,7 @@ class CadTrainer:
         zero on every rank -- are left out of the head bucket.  One small collective and a host wait per step instead
         of 13.3 MB on the wire: for interconnect-bound setups (the default sums it and never waits).
         prio_stream: run each step on a stream of the device's greatest priority (ordered after and before the
-        caller's stream), so with the plan's low-priority weight-gradient stream (knob cad_stream_prio) the dispatcher
+        caller's stream), so with the plan's low-priority weight-gradient stream the dispatcher
         prefers the critical path's workgroups."""
         self.model = model
         if compute_dtype is not None:
@@ -115,7 +115,7 @@ class CadTrainer:
         beside the previous step's queued tail (CadEngine.input_ready)."""
         if self.prio_stream is not None and self.eng.grads.is_cuda:
             # the step's critical path on a stream of the device's greatest priority (the plan's weight-gradient stream
-            # runs at its least with knob cad_stream_prio), ordered after / before the caller's stream
+            # runs at its least), ordered after / before the caller's stream
             caller = torch.cuda.current_stream(self.eng.device)
             self.prio_stream.wait_stream(caller)
             with torch.cuda.stream(self.prio_stream):

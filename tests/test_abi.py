@@ -28,6 +28,45 @@ def test_library_exports_every_declared_symbol():
     assert L.vad_abi_version() == 1
 
 
+# the tuning keys the test suite sets: retiring one of them would strand a test
+_KEYS_TESTS_SET = [
+    "conv_patch", "conv_patch_persist", "conv_split", "conv_wgrad_patch", "conv_wgrad_split", "conv_wgrad_split_s2",
+    "conv_wgrad_tr", "conv_wgrad_tr_pft", "conv_dgrad_s2_x3", "conv_dgrad_s2_w3", "conv_bf16", "act_bf16", "stem_fused",
+    "mlp_tail_rb", "mlp_tail_wide", "cad_stem_early", "cad_dir_affine", "cad_opt_images",
+    "conv3d_direct", "maxpool3d_bwd_win", "bbox_im2col", "ae_direct", "ae_wgrad_stream", "conv4_cls_batch_min",
+    "a2_direct", "a2_head_clip",
+]
+
+
+def test_tuning_table():
+    """The knob table (csrc/tuning.h) through vad_tuning_name / vad_get_tuning / vad_set_tuning: unique keys, every key
+    reads and writes its own variable, unknown keys are refused by both entry points."""
+    from vad_amd import _native
+    L = _native.lib()
+    keys = []
+    while L.vad_tuning_name(len(keys)) is not None:
+        keys.append(L.vad_tuning_name(len(keys)))
+    assert L.vad_tuning_name(len(keys) + 1) is None and L.vad_tuning_name(-1) is None
+    assert len(keys) >= len(_KEYS_TESTS_SET) and len(set(keys)) == len(keys)
+    get = lambda k: (_native.check(L.vad_get_tuning(k, ctypes.byref(v))), v.value)[1]
+    v = ctypes.c_int()
+    entry = {k: get(k) for k in keys}
+    try:
+        for i, k in enumerate(keys):  # a value of its own per key: two keys on one variable would read back alike
+            _native.check(L.vad_set_tuning(k, entry[k] + 100 + i))
+        assert {k: get(k) for k in keys} == {k: entry[k] + 100 + i for i, k in enumerate(keys)}
+    finally:
+        for k in keys:
+            L.vad_set_tuning(k, entry[k])
+    assert {k: get(k) for k in keys} == entry
+    assert L.vad_set_tuning(b"no_such_knob", 1) != 0
+    assert b"unknown tuning key no_such_knob" in L.vad_last_error()
+    assert L.vad_get_tuning(b"no_such_knob", ctypes.byref(v)) != 0
+    assert b"unknown tuning key no_such_knob" in L.vad_last_error()
+    missing = [k for k in _KEYS_TESTS_SET if k.encode() not in keys]
+    assert not missing, missing
+
+
 def test_slot_table_matches_module():
     from vad_amd import _native
     from vad_amd.cad import CausalAnomalyDetector
