@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
+from ._flat import FlatEngine, FlatPlan
 
 
 class CompactFeatureExtractor(nn.Module):
@@ -63,7 +64,6 @@ class CausalAnomalyDetector(nn.Module):
         if e is None or e.device != x.device:
             e = A2Engine(self, x.device)
             self._engine = e
-        e.sync_from_module()
         e.use_shape(tuple(x.shape))
         return e
 
@@ -115,81 +115,42 @@ class _A2LossFunction(torch.autograd.Function):
         return (ds.view(-1, 1) * g, dadj * g, None, None, None, None)
 
 
-class _A2Plan:
-    def __init__(self, e, shape):
-        lib = nat.lib()
-        B, C, T, H, W = shape
-        plan = ctypes.c_void_p()
-        nat.check(lib.vad_a2_create(B, T, H, W, ctypes.byref(plan)))
-        self.plan = plan
+class _A2Plan(FlatPlan):
+    def __init__(self, e, B, C, T, H, W):
+        super().__init__(e, B, C, T, H, W)
         self.B = B
-        self.ws = torch.empty(lib.vad_a2_workspace_bytes(plan) + 256, dtype=torch.uint8, device=e.device)
-        base = (self.ws.data_ptr() + 255) // 256 * 256
-        nat.check(lib.vad_a2_bind(plan, ctypes.c_void_p(base), nat.ptr(e.params), nat.ptr(e.grads),
-                                  nat.ptr(e.exp_avg), nat.ptr(e.exp_avg_sq), nat.ptr(e.steps)))
         f = dict(dtype=torch.float32, device=e.device)
         self.scores, self.adj, self.feats = torch.zeros(B, **f), torch.zeros(B, 16, 16, **f), torch.zeros(B, 16, **f)
         self.d_s, self.d_adj = torch.zeros(B, **f), torch.zeros(B, 16, 16, **f)
         self.borrow = False
 
-    def __del__(self):
-        try:
-            if getattr(self, "plan", None):
-                nat.lib().vad_a2_destroy(self.plan)
-        except Exception:
-            pass
+    @staticmethod
+    def create_args(B, C, T, H, W):
+        return B, T, H, W
 
 
-class A2Engine:
+class A2Engine(FlatEngine):
     """Flat device buffers (params / grads / AdamW state, named_parameters order) shared by per-shape plans."""
+    PLAN = _A2Plan
 
     def __init__(self, model, device):
-        lib = nat.lib()
-        self.device, self.model, self.seed = device, model, 1234
-        self.slots = [(lib.vad_a2_slot_name(i).decode(), lib.vad_a2_slot_offset(i), lib.vad_a2_slot_numel(i))
-                      for i in range(lib.vad_a2_num_slots())]
-        names = [n for n, _ in model.named_parameters()]
-        if names != [s[0] for s in self.slots]:
-            raise NotImplementedError("the HIP a2 plan supports the reference dims (feature_dim=64, causal_dim=16, "
-                                      "hidden_dim=128) only")
-        n = lib.vad_a2_param_floats()
-        f = dict(dtype=torch.float32, device=device)
-        self.params, self.grads = torch.zeros(n, **f), torch.zeros(n, **f)
-        self.exp_avg, self.exp_avg_sq = torch.zeros(n, **f), torch.zeros(n, **f)
-        self.steps = torch.zeros(len(self.slots), dtype=torch.int32, device=device)
-        self.losses = torch.zeros(10, **f)
-        sd = dict(model.named_parameters())
-        self.param_views = [self.params[o:o + k].view_as(sd[nm]) for nm, o, k in self.slots]
-        self._bound = False
-        self.plans, self.cur, self.last_keys = {}, None, (0, 0, 0)
+        super().__init__(model, device, "a2", replace_params=True, opt_state="eager",
+                         bind_names=("params", "grads", "exp_avg", "exp_avg_sq", "steps"),
+                         name_mismatch=(NotImplementedError, "the HIP a2 plan supports the reference dims "
+                                        "(feature_dim=64, causal_dim=16, hidden_dim=128) only"))
+        self.seed, self.last_keys = 1234, (0, 0, 0)
+        self.losses = torch.zeros(10, dtype=torch.float32, device=device)
 
     def use_shape(self, shape):
-        if shape not in self.plans:
-            self.plans[shape] = _A2Plan(self, shape)
-        self.cur = self.plans[shape]
-
-    def sync_from_module(self):
-        if self._bound:
-            return
-        m = self.model
-        with torch.no_grad():
-            sd = dict(m.named_parameters())
-            for (name, o, k), view in zip(self.slots, self.param_views):
-                view.copy_(sd[name].detach().to(self.device))
-                mod_name, attr = name.rsplit(".", 1)
-                setattr(m.get_submodule(mod_name), attr, nn.Parameter(view, requires_grad=sd[name].requires_grad))
-        self._bound = True
-
-    def stream(self):
-        return nat.stream_of(self.device)
+        self.cur = self.plan(*shape)
 
     def forward(self, x, training, seed, step, clip0, with_loss, borrow_input=False):
         """borrow_input: x stays unchanged until the backward (the fused train step): conv3d_1 reads it in place."""
         p = self.cur
         if p.borrow != bool(borrow_input):
-            nat.check(nat.lib().vad_a2_set_option(p.plan, b"borrow_input", int(bool(borrow_input))))
+            nat.check(nat.lib().vad_a2_set_option(p.h, b"borrow_input", int(bool(borrow_input))))
             p.borrow = bool(borrow_input)
-        nat.check(nat.lib().vad_a2_forward(p.plan, nat.ptr(x), int(training), ctypes.c_uint64(seed),
+        nat.check(nat.lib().vad_a2_forward(p.h, nat.ptr(x), int(training), ctypes.c_uint64(seed),
                                            ctypes.c_uint64(step), ctypes.c_int64(clip0), int(with_loss),
                                            nat.ptr(p.scores), nat.ptr(p.adj), nat.ptr(p.feats),
                                            nat.ptr(self.losses) if with_loss else None, self.stream()))
@@ -200,28 +161,25 @@ class A2Engine:
         p = self.cur
         ptr = buf.data_ptr() if buf is not None else 0
         if getattr(p, "host_ptr", 0) != ptr:
-            nat.check(nat.lib().vad_a2_set_option(p.plan, b"host_losses", ctypes.c_int64(ptr)))
+            nat.check(nat.lib().vad_a2_set_option(p.h, b"host_losses", ctypes.c_int64(ptr)))
             p.host_ptr = ptr
 
     def loss(self, seed, step, clip0):
-        nat.check(nat.lib().vad_a2_loss(self.cur.plan, ctypes.c_uint64(seed), ctypes.c_uint64(step),
+        nat.check(nat.lib().vad_a2_loss(self.cur.h, ctypes.c_uint64(seed), ctypes.c_uint64(step),
                                         ctypes.c_int64(clip0), nat.ptr(self.losses), self.stream()))
 
     def loss_grads(self):
         p = self.cur
-        nat.check(nat.lib().vad_a2_loss_grads(p.plan, nat.ptr(p.d_s), nat.ptr(p.d_adj), self.stream()))
+        nat.check(nat.lib().vad_a2_loss_grads(p.h, nat.ptr(p.d_s), nat.ptr(p.d_adj), self.stream()))
         return p.d_s.clone(), p.d_adj.clone()
 
     def backward(self, d_s=None, d_adj=None, d_f=None):
-        nat.check(nat.lib().vad_a2_backward(self.cur.plan, nat.ptr(d_s) if d_s is not None else None,
+        nat.check(nat.lib().vad_a2_backward(self.cur.h, nat.ptr(d_s) if d_s is not None else None,
                                             nat.ptr(d_adj) if d_adj is not None else None,
                                             nat.ptr(d_f) if d_f is not None else None, self.stream()))
 
-    def grad_clones(self):
-        return [self.grads[o:o + k].view_as(v).clone() for (_, o, k), v in zip(self.slots, self.param_views)]
-
     def optimizer_step(self, lr, weight_decay, max_norm, betas=(0.9, 0.999), eps=1e-8):
-        nat.check(nat.lib().vad_a2_optimizer_step(self.cur.plan, ctypes.c_float(lr), ctypes.c_float(betas[0]),
+        nat.check(nat.lib().vad_a2_optimizer_step(self.cur.h, ctypes.c_float(lr), ctypes.c_float(betas[0]),
                                                   ctypes.c_float(betas[1]), ctypes.c_float(eps),
                                                   ctypes.c_float(weight_decay), ctypes.c_float(max_norm),
                                                   self.stream()))

@@ -12,7 +12,6 @@ clip_grad_norm_(0.1), Adam with coupled L2).  There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
@@ -21,7 +20,7 @@ import torch.nn as nn
 
 from . import _native as nat
 from .a2 import _ParamGroups, _Plateau
-from .engine import _set_buffer
+from ._flat import FlatEngine, _set_buffer
 
 LATENT, HW = 64, 64
 
@@ -151,102 +150,34 @@ class _AeFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_recon, d_seq, d_ff, d_score):
         ctx.e.backward(False, d_recon, d_seq, d_ff)
-        return (None, None, None, *ctx.e.grad_views())
+        return (None, None, None, *ctx.e.grad_clones())
 
 
-class _AePlan:
-    """One C plan + workspace per (B, T), bound to the engine's shared flat buffers."""
-
-    def __init__(self, e, B, T):
-        L = nat.lib()
-        h = ctypes.c_void_p()
-        nat.check(L.vad_ae_create(B, T, ctypes.byref(h)))
-        self.h = h
-        self.ws = torch.empty(L.vad_ae_workspace_bytes(h) + 256, dtype=torch.uint8, device=e.device)
-        self.bind(e)
-
-    def bind(self, e):
-        base = (self.ws.data_ptr() + 255) // 256 * 256
-        nat.check(nat.lib().vad_ae_bind(self.h, base, e.params.data_ptr(), e.grads.data_ptr(), e.bufs.data_ptr(),
-                                        e.nbt.data_ptr(), e.memory.data_ptr(), e.mptr.data_ptr(), nat.ptr(e.exp_avg),
-                                        nat.ptr(e.exp_avg_sq), nat.ptr(e.steps)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                nat.lib().vad_ae_destroy(self.h)
-        except Exception:
-            pass
-
-
-class AeEngine:
+class AeEngine(FlatEngine):
     """Flat device buffers of one VideoAutoEncoder -- params / grads / BN running stats / counters / memory ring /
     Adam state; the module's parameters and buffers are views into them -- shared by per-(B, T) plans."""
 
     def __init__(self, model):
-        L = nat.lib()
         p0 = next(model.parameters())
         nat.require_hip(p0)
         if model.encoder[0].in_channels != 1 or model.temporal_encoder.hidden_size != LATENT:
             raise NotImplementedError("the HIP plan implements VideoAutoEncoder(input_channels=1, latent_dim=64), "
                                       "the reference's configuration (cad1:687)")
-        self.model, self.device = model, p0.device
-        self.slots = [(L.vad_ae_slot_name(i).decode(), L.vad_ae_slot_offset(i), L.vad_ae_slot_numel(i))
-                      for i in range(L.vad_ae_num_slots())]
-        named = list(model.named_parameters())
-        if [k for k, _ in named] != [s[0] for s in self.slots]:
-            raise RuntimeError("model parameters do not match the libvadhip slot table")
+        super().__init__(model, p0.device, "ae", replace_params=False, opt_state="lazy",
+                         bind_names=("params", "grads", "bufs", "nbt", "memory", "mptr", "exp_avg", "exp_avg_sq",
+                                     "steps"))
         f = dict(dtype=torch.float32, device=self.device)
-        self.params = torch.zeros(L.vad_ae_param_floats(), **f)
-        self.grads = torch.zeros_like(self.params)
-        self.bufs = torch.zeros(L.vad_ae_buf_floats(), **f)
-        named_bufs = dict(model.named_buffers())
-        nbt_names = [k for k in named_bufs if k.endswith("num_batches_tracked")]
-        self.nbt = torch.zeros(len(nbt_names), dtype=torch.int64, device=self.device)
         with torch.no_grad():
-            for (k, p), (_, off, nel) in zip(named, self.slots):
-                if p.numel() != nel:
-                    raise RuntimeError(f"parameter {k}: {p.numel()} elements, library expects {nel}")
-                view = self.params[off:off + nel].view_as(p)
-                view.copy_(p.data)
-                p.data = view
-            for i in range(L.vad_ae_num_bufs()):
-                k, off, nel = L.vad_ae_buf_name(i).decode(), L.vad_ae_buf_offset(i), L.vad_ae_buf_numel(i)
-                view = self.bufs[off:off + nel].view_as(named_bufs[k])
-                view.copy_(named_bufs[k])
-                _set_buffer(model, k, view)
-            for i, k in enumerate(nbt_names):
-                self.nbt[i].copy_(named_bufs[k].reshape(()))
-                _set_buffer(model, k, self.nbt[i])
-            self.memory = named_bufs["normal_memory"].detach().to(**f).clone().contiguous()
-            self.mptr = named_bufs["memory_ptr"].detach().to(device=self.device, dtype=torch.int64).clone()
+            self.memory = model.normal_memory.detach().to(**f).clone().contiguous()
+            self.mptr = model.memory_ptr.detach().to(device=self.device, dtype=torch.int64).clone()
             _set_buffer(model, "normal_memory", self.memory)
             _set_buffer(model, "memory_ptr", self.mptr)
-        self.exp_avg = self.exp_avg_sq = self.steps = None
         self.losses = torch.zeros(4, **f)  # mse, grad norm, clipped, status
-        self.plans = {}
-        self.cur = None
 
     def is_bound(self) -> bool:
         m = self.model
         return (next(m.parameters()).data_ptr() == self.params.data_ptr()
                 and m.normal_memory.data_ptr() == self.memory.data_ptr())
-
-    def plan(self, B, T) -> _AePlan:
-        if (B, T) not in self.plans:
-            self.plans[(B, T)] = _AePlan(self, B, T)
-        return self.plans[(B, T)]
-
-    def init_optimizer_state(self):
-        if self.exp_avg is None:
-            self.exp_avg = torch.zeros_like(self.params)
-            self.exp_avg_sq = torch.zeros_like(self.params)
-            self.steps = torch.zeros(len(self.slots), dtype=torch.int32, device=self.device)
-            for p in self.plans.values():
-                p.bind(self)
-
-    def stream(self):
-        return nat.stream_of(self.device)
 
     def forward(self, x, stages=3, training=True, loss_mode=0, seq_in=None, T=None, outputs=True):
         """One plan forward (stages 1 encode / 2 decode / 3 both; loss_mode 0 none / 1 eval MSE / 2 train_model
@@ -285,10 +216,6 @@ class AeEngine:
         self.init_optimizer_state()
         nat.check(nat.lib().vad_ae_optimizer_step(self.cur.h, lr, betas[0], betas[1], eps, weight_decay, max_norm,
                                                   grad_scale, self.stream()))
-
-    def grad_views(self):
-        return [self.grads[off:off + n].view_as(p).clone()
-                for (_, off, n), (_, p) in zip(self.slots, self.model.named_parameters())]
 
     def update_memory(self, features):
         f = features.detach().to(device=self.device, dtype=torch.float32).reshape(-1, LATENT).contiguous()

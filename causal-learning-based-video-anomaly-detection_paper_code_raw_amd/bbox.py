@@ -9,7 +9,6 @@ person detectors and drawing code (cv2 / yolov5) are out of scope.
 """
 from __future__ import annotations
 
-import ctypes
 from collections import defaultdict
 from pathlib import Path
 
@@ -18,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
+from ._flat import FlatEngine, FlatPlan
 
 
 class CausalAnomalyDetector(nn.Module):
@@ -45,64 +45,30 @@ class CausalAnomalyDetector(nn.Module):
         e = self._engine
         if e is None or e.device != x.device:
             e = self._engine = BboxEngine(self, x.device)
-        e.sync_from_module()
         s, adj, f = e.forward(x.float().contiguous())
         return s.squeeze(), adj, f
 
 
-class _BboxPlan:
-    def __init__(self, e, shape):
-        lib = nat.lib()
-        B, C, T, H, W = shape
-        plan = ctypes.c_void_p()
-        nat.check(lib.vad_bbox_create(B, T, H, W, ctypes.byref(plan)))
-        self.plan = plan
-        self.ws = torch.empty(lib.vad_bbox_workspace_bytes(plan) + 256, dtype=torch.uint8, device=e.device)
-        base = (self.ws.data_ptr() + 255) // 256 * 256
-        nat.check(lib.vad_bbox_bind(plan, ctypes.c_void_p(base), nat.ptr(e.params)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "plan", None):
-                nat.lib().vad_bbox_destroy(self.plan)
-        except Exception:
-            pass
+class _BboxPlan(FlatPlan):
+    @staticmethod
+    def create_args(B, C, T, H, W):
+        return B, T, H, W
 
 
-class BboxEngine:
+class BboxEngine(FlatEngine):
+    PLAN = _BboxPlan
+
     def __init__(self, model, device):
-        lib = nat.lib()
-        self.device, self.model = device, model
-        self.slots = [(lib.vad_bbox_slot_name(i).decode(), lib.vad_bbox_slot_offset(i), lib.vad_bbox_slot_numel(i))
-                      for i in range(lib.vad_bbox_num_slots())]
-        if [n for n, _ in model.named_parameters()] != [s[0] for s in self.slots]:
-            raise NotImplementedError("the HIP bbox plan supports the reference layout (input_channels=3) only")
-        self.params = torch.zeros(lib.vad_bbox_param_floats(), dtype=torch.float32, device=device)
-        self._bound = False
-        self.plans = {}
-
-    def sync_from_module(self):
-        if self._bound:
-            return
-        m = self.model
-        with torch.no_grad():
-            sd = dict(m.named_parameters())
-            for name, off, n in self.slots:
-                view = self.params[off:off + n].view_as(sd[name])
-                view.copy_(sd[name].detach().to(self.device))
-                mod_name, attr = name.rsplit(".", 1)
-                setattr(m.get_submodule(mod_name), attr, nn.Parameter(view, requires_grad=sd[name].requires_grad))
-        self._bound = True
+        super().__init__(model, device, "bbox", replace_params=True, opt_state=None, bind_names=("params",),
+                         name_mismatch=(NotImplementedError,
+                                        "the HIP bbox plan supports the reference layout (input_channels=3) only"))
 
     def forward(self, x):
-        shape = tuple(x.shape)
-        if shape not in self.plans:
-            self.plans[shape] = _BboxPlan(self, shape)
-        p = self.plans[shape]
-        B = shape[0]
+        p = self.plan(*x.shape)
+        B = x.shape[0]
         f = dict(dtype=torch.float32, device=self.device)
         s, adj, feats = torch.empty(B, **f), torch.empty(B, 16, 16, **f), torch.empty(B, 1024, **f)
-        nat.check(nat.lib().vad_bbox_forward(p.plan, nat.ptr(x), nat.ptr(s), nat.ptr(adj), nat.ptr(feats),
+        nat.check(nat.lib().vad_bbox_forward(p.h, nat.ptr(x), nat.ptr(s), nat.ptr(adj), nat.ptr(feats),
                                              nat.stream_of(self.device)))
         return s.view(B, 1), adj, feats
 

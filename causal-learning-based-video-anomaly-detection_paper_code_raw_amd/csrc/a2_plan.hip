@@ -27,42 +27,26 @@ constexpr int A2_NSLOT = 20;
 constexpr int A2_CO[3] = {16, 32, 64};
 constexpr int A2_MAXB = 256;
 
-struct A2Slot {
-  const char* name;
-  int64_t numel;
-};
-static const A2Slot A2_SLOTS[A2_NSLOT] = {
-    {"feature_extractor.conv3d_1.weight", 16 * 3 * 27}, {"feature_extractor.conv3d_1.bias", 16},
-    {"feature_extractor.conv3d_2.weight", 32 * 16 * 27}, {"feature_extractor.conv3d_2.bias", 32},
-    {"feature_extractor.conv3d_3.weight", 64 * 32 * 27}, {"feature_extractor.conv3d_3.bias", 64},
-    {"feature_extractor.fc.weight", 16 * 4096},          {"feature_extractor.fc.bias", 16},
-    {"causal_discovery.causal_net.0.weight", 32 * 16},   {"causal_discovery.causal_net.0.bias", 32},
-    {"causal_discovery.causal_net.2.weight", 256 * 32},  {"causal_discovery.causal_net.2.bias", 256},
-    {"graph_encoder.0.weight", 128 * 256},               {"graph_encoder.0.bias", 128},
-    {"graph_encoder.3.weight", 64 * 128},                {"graph_encoder.3.bias", 64},
-    {"anomaly_predictor.0.weight", 32 * 80},             {"anomaly_predictor.0.bias", 32},
-    {"anomaly_predictor.2.weight", 32},                  {"anomaly_predictor.2.bias", 1},
-};
+// model.named_parameters() order (a2:15-101)
+static const FlatLayout& a2_layout() {
+  static const FlatLayout L{
+      {"feature_extractor.conv3d_1.weight", 16 * 3 * 27}, {"feature_extractor.conv3d_1.bias", 16},
+      {"feature_extractor.conv3d_2.weight", 32 * 16 * 27}, {"feature_extractor.conv3d_2.bias", 32},
+      {"feature_extractor.conv3d_3.weight", 64 * 32 * 27}, {"feature_extractor.conv3d_3.bias", 64},
+      {"feature_extractor.fc.weight", 16 * 4096},          {"feature_extractor.fc.bias", 16},
+      {"causal_discovery.causal_net.0.weight", 32 * 16},   {"causal_discovery.causal_net.0.bias", 32},
+      {"causal_discovery.causal_net.2.weight", 256 * 32},  {"causal_discovery.causal_net.2.bias", 256},
+      {"graph_encoder.0.weight", 128 * 256},               {"graph_encoder.0.bias", 128},
+      {"graph_encoder.3.weight", 64 * 128},                {"graph_encoder.3.bias", 64},
+      {"anomaly_predictor.0.weight", 32 * 80},             {"anomaly_predictor.0.bias", 32},
+      {"anomaly_predictor.2.weight", 32},                  {"anomaly_predictor.2.bias", 1},
+  };
+  return L;
+}
 enum {
   S_C1W, S_C1B, S_C2W, S_C2B, S_C3W, S_C3B, S_FCW, S_FCB, S_CN0W, S_CN0B, S_CN2W, S_CN2B,
   S_GE0W, S_GE0B, S_GE3W, S_GE3B, S_AP0W, S_AP0B, S_AP2W, S_AP2B
 };
-
-struct A2Offsets {
-  int64_t off[A2_NSLOT];
-  int64_t total;
-  A2Offsets() {
-    total = 0;
-    for (int i = 0; i < A2_NSLOT; ++i) {
-      off[i] = total;
-      total += (A2_SLOTS[i].numel + 255) / 256 * 256;
-    }
-  }
-};
-static const A2Offsets& a2_offsets() {
-  static const A2Offsets o;
-  return o;
-}
 
 // ------------------------------------------------------------------ head
 // The head is a chain of small Linear layers over B rows (a2:27-101); each layer is one launch with one thread per
@@ -786,8 +770,8 @@ struct A2PlanImpl {
       in = g[s].out();
     }
   }
-  float* P(int s) const { return params + a2_offsets().off[s]; }
-  float* G(int s) const { return grads + a2_offsets().off[s]; }
+  float* P(int s) const { return params + a2_layout().offsets[s]; }
+  float* G(int s) const { return grads + a2_layout().offsets[s]; }
 
   void carve(Ws& w) {
     int64_t max_y = 0, max_dcols = 1;
@@ -1031,12 +1015,10 @@ struct A2PlanImpl {
 
   int optimizer(float lr, float b1, float b2, float eps, float wd, float max_norm, hipStream_t st,
                 float* user_losses = nullptr) {
-    const AdamSlots t = adam_slots(A2_NSLOT, [](int i) { return a2_offsets().off[i]; },
-                                   [](int i) { return A2_SLOTS[i].numel; });
     // AdamW, clipped on every step, no finiteness gate and no status: only the norm, losses[8], is written
     const AdamStep a{lr, b1, b2, eps, wd, true, -1.f, max_norm, 1.f, losses + 9, losses + 8,
                      user_losses ? user_losses + 8 : nullptr, nullptr, nullptr};
-    return adam_clip_step(t, params, grads, m, v, a2_offsets().total, steps, aws, a, st);
+    return adam_clip_step(a2_layout().adam_slots(), params, grads, m, v, a2_layout().param_floats, steps, aws, a, st);
   }
 };
 
@@ -1055,11 +1037,7 @@ struct vad_a2_plan {
 
 extern "C" {
 
-int vad_a2_num_slots(void) { return A2_NSLOT; }
-const char* vad_a2_slot_name(int i) { return (i >= 0 && i < A2_NSLOT) ? A2_SLOTS[i].name : nullptr; }
-int64_t vad_a2_slot_numel(int i) { return (i >= 0 && i < A2_NSLOT) ? A2_SLOTS[i].numel : -1; }
-int64_t vad_a2_slot_offset(int i) { return (i >= 0 && i < A2_NSLOT) ? a2_offsets().off[i] : -1; }
-int64_t vad_a2_param_floats(void) { return a2_offsets().total; }
+VAD_FLAT_SLOT_ABI(a2, (void), (int i), &a2_layout())
 
 int vad_a2_create(int B, int T, int H, int W, vad_a2_plan** out) {
   VAD_CHECK(out != nullptr, "vad_a2_create: out is null");
@@ -1086,7 +1064,7 @@ int vad_a2_bind(vad_a2_plan* plan, void* workspace, float* params, float* grads,
   ws.dry = false;
   c.carve(ws);
   c.params = params; c.grads = grads; c.m = exp_avg; c.v = exp_avg_sq; c.steps = steps;
-  VAD_HIP(hipMemcpy(c.off_dev, a2_offsets().off, sizeof(int64_t) * A2_NSLOT, hipMemcpyHostToDevice));
+  VAD_HIP(hipMemcpy(c.off_dev, a2_layout().offsets.data(), sizeof(int64_t) * A2_NSLOT, hipMemcpyHostToDevice));
   return 0;
 }
 

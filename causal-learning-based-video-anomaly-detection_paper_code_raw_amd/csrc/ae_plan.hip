@@ -59,60 +59,42 @@ constexpr int AE_WGRAD_BLOCKS = 1024;
 constexpr int ENC_CI[4] = {1, 32, 64, 128}, ENC_CO[4] = {32, 64, 128, 128}, ENC_IN[4] = {64, 32, 16, 8};
 constexpr int DEC_CI[4] = {128, 128, 64, 32}, DEC_CO[4] = {128, 64, 32, 1}, DEC_IN[4] = {4, 8, 16, 32};
 
-struct AeSlot {
-  std::string name;
-  int64_t numel, offset;
-};
-
 // model.named_parameters() and BN running-stat order (cad1:129-188)
-struct AeLayout {
-  std::vector<AeSlot> slots, bufs;
-  int64_t param_floats = 0, buf_floats = 0;
+struct AeLayout : FlatLayout {
   int enc_w[4], enc_b[4], ebn_w[4], ebn_b[4], efc_w, efc_b;
   int dfc_w, dfc_b, dec_w[4], dec_b[4], dbn_w[3], dbn_b[3];
   int wih, whh, bih, bhh;
   int erm[4], erv[4], drm[3], drv[3];
   AeLayout() {
-    auto add = [](std::vector<AeSlot>& v, const std::string& n, int64_t k) {
-      v.push_back({n, k, 0});
-      return (int)v.size() - 1;
-    };
     for (int l = 0; l < 4; ++l) {
       const std::string c = "encoder." + std::to_string(3 * l), b = "encoder." + std::to_string(3 * l + 1);
-      enc_w[l] = add(slots, c + ".weight", (int64_t)ENC_CO[l] * ENC_CI[l] * 16);
-      enc_b[l] = add(slots, c + ".bias", ENC_CO[l]);
-      ebn_w[l] = add(slots, b + ".weight", ENC_CO[l]);
-      ebn_b[l] = add(slots, b + ".bias", ENC_CO[l]);
-      erm[l] = add(bufs, b + ".running_mean", ENC_CO[l]);
-      erv[l] = add(bufs, b + ".running_var", ENC_CO[l]);
+      enc_w[l] = add(c + ".weight", (int64_t)ENC_CO[l] * ENC_CI[l] * 16);
+      enc_b[l] = add(c + ".bias", ENC_CO[l]);
+      ebn_w[l] = add(b + ".weight", ENC_CO[l]);
+      ebn_b[l] = add(b + ".bias", ENC_CO[l]);
+      erm[l] = add_buf(b + ".running_mean", ENC_CO[l]);
+      erv[l] = add_buf(b + ".running_var", ENC_CO[l]);
     }
-    efc_w = add(slots, "encoder.13.weight", (int64_t)AE_LAT * AE_FLAT);
-    efc_b = add(slots, "encoder.13.bias", AE_LAT);
-    dfc_w = add(slots, "decoder.0.weight", (int64_t)AE_FLAT * AE_LAT);
-    dfc_b = add(slots, "decoder.0.bias", AE_FLAT);
+    efc_w = add("encoder.13.weight", (int64_t)AE_LAT * AE_FLAT);
+    efc_b = add("encoder.13.bias", AE_LAT);
+    dfc_w = add("decoder.0.weight", (int64_t)AE_FLAT * AE_LAT);
+    dfc_b = add("decoder.0.bias", AE_FLAT);
     for (int j = 0; j < 4; ++j) {
       const std::string c = "decoder." + std::to_string(3 * j + 3), b = "decoder." + std::to_string(3 * j + 4);
-      dec_w[j] = add(slots, c + ".weight", (int64_t)DEC_CI[j] * DEC_CO[j] * 16);
-      dec_b[j] = add(slots, c + ".bias", DEC_CO[j]);
+      dec_w[j] = add(c + ".weight", (int64_t)DEC_CI[j] * DEC_CO[j] * 16);
+      dec_b[j] = add(c + ".bias", DEC_CO[j]);
       if (j < 3) {
-        dbn_w[j] = add(slots, b + ".weight", DEC_CO[j]);
-        dbn_b[j] = add(slots, b + ".bias", DEC_CO[j]);
-        drm[j] = add(bufs, b + ".running_mean", DEC_CO[j]);
-        drv[j] = add(bufs, b + ".running_var", DEC_CO[j]);
+        dbn_w[j] = add(b + ".weight", DEC_CO[j]);
+        dbn_b[j] = add(b + ".bias", DEC_CO[j]);
+        drm[j] = add_buf(b + ".running_mean", DEC_CO[j]);
+        drv[j] = add_buf(b + ".running_var", DEC_CO[j]);
       }
     }
-    wih = add(slots, "temporal_encoder.weight_ih_l0", (int64_t)AE_GATES * AE_LAT);
-    whh = add(slots, "temporal_encoder.weight_hh_l0", (int64_t)AE_GATES * AE_LAT);
-    bih = add(slots, "temporal_encoder.bias_ih_l0", AE_GATES);
-    bhh = add(slots, "temporal_encoder.bias_hh_l0", AE_GATES);
-    for (auto& s : slots) {
-      s.offset = param_floats;
-      param_floats += (s.numel + 255) / 256 * 256;
-    }
-    for (auto& b : bufs) {
-      b.offset = buf_floats;
-      buf_floats += (b.numel + 255) / 256 * 256;
-    }
+    wih = add("temporal_encoder.weight_ih_l0", (int64_t)AE_GATES * AE_LAT);
+    whh = add("temporal_encoder.weight_hh_l0", (int64_t)AE_GATES * AE_LAT);
+    bih = add("temporal_encoder.bias_ih_l0", AE_GATES);
+    bhh = add("temporal_encoder.bias_hh_l0", AE_GATES);
+    finish();
   }
 };
 static const AeLayout& ae_layout() {
@@ -1178,13 +1160,11 @@ struct AePlanImpl {
 
   int optimizer(float lr, float b1, float b2, float eps, float wd, float max_norm, float grad_scale, hipStream_t st) {
     const AeLayout& L = ae_layout();
-    const AdamSlots t = adam_slots((int)L.slots.size(), [&](int i) { return L.slots[i].offset; },
-                                   [&](int i) { return L.slots[i].numel; });
     // coupled decay; clip_grad_norm_(max_norm) on every step (cad1:424): clip_above < 0; losses[1] norm, [2] clipped,
     // [3] the status word
     const AdamStep a{lr, b1, b2, eps, wd, false, -1.f, max_norm, grad_scale, losses + 3, losses + 1, nullptr,
                      losses + 2, losses + 3};
-    return adam_clip_step(t, params, grads, m, v, L.param_floats, steps, aws, a, st);
+    return adam_clip_step(L.adam_slots(), params, grads, m, v, L.param_floats, steps, aws, a, st);
   }
 };
 
@@ -1200,20 +1180,8 @@ struct vad_ae_plan {
 
 extern "C" {
 
-int vad_ae_num_slots(void) { return (int)ae_layout().slots.size(); }
-const char* vad_ae_slot_name(int i) {
-  return (i >= 0 && i < vad_ae_num_slots()) ? ae_layout().slots[i].name.c_str() : nullptr;
-}
-int64_t vad_ae_slot_numel(int i) { return (i >= 0 && i < vad_ae_num_slots()) ? ae_layout().slots[i].numel : -1; }
-int64_t vad_ae_slot_offset(int i) { return (i >= 0 && i < vad_ae_num_slots()) ? ae_layout().slots[i].offset : -1; }
-int64_t vad_ae_param_floats(void) { return ae_layout().param_floats; }
-int vad_ae_num_bufs(void) { return (int)ae_layout().bufs.size(); }
-const char* vad_ae_buf_name(int i) {
-  return (i >= 0 && i < vad_ae_num_bufs()) ? ae_layout().bufs[i].name.c_str() : nullptr;
-}
-int64_t vad_ae_buf_numel(int i) { return (i >= 0 && i < vad_ae_num_bufs()) ? ae_layout().bufs[i].numel : -1; }
-int64_t vad_ae_buf_offset(int i) { return (i >= 0 && i < vad_ae_num_bufs()) ? ae_layout().bufs[i].offset : -1; }
-int64_t vad_ae_buf_floats(void) { return ae_layout().buf_floats; }
+VAD_FLAT_SLOT_ABI(ae, (void), (int i), &ae_layout())
+VAD_FLAT_BUF_ABI(ae, (void), (int i), &ae_layout())
 
 int vad_ae_create(int B, int T, vad_ae_plan** out) {
   VAD_CHECK(out != nullptr, "vad_ae_create: out is null");

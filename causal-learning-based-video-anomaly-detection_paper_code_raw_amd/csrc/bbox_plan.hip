@@ -15,34 +15,17 @@
 
 namespace vad {
 
-constexpr int BB_NSLOT = 12;
-struct BbSlot {
-  const char* name;
-  int64_t numel;
-};
 // model.named_parameters() order (bbox:53-84)
-static const BbSlot BB_SLOTS[BB_NSLOT] = {
-    {"encoder.0.weight", 32 * 3 * 27},     {"encoder.0.bias", 32},
-    {"encoder.3.weight", 64 * 32 * 27},    {"encoder.3.bias", 64},
-    {"causal_net.0.weight", 256 * 1024},   {"causal_net.0.bias", 256},
-    {"causal_net.2.weight", 256 * 256},    {"causal_net.2.bias", 256},
-    {"classifier.0.weight", 128 * 1024},   {"classifier.0.bias", 128},
-    {"classifier.3.weight", 128},          {"classifier.3.bias", 1},
-};
-
-struct BbOffsets {
-  int64_t off[BB_NSLOT];
-  int64_t total = 0;
-  BbOffsets() {
-    for (int i = 0; i < BB_NSLOT; ++i) {
-      off[i] = total;
-      total += (BB_SLOTS[i].numel + 255) / 256 * 256;
-    }
-  }
-};
-static const BbOffsets& bb_offsets() {
-  static const BbOffsets o;
-  return o;
+static const FlatLayout& bb_layout() {
+  static const FlatLayout L{
+      {"encoder.0.weight", 32 * 3 * 27},     {"encoder.0.bias", 32},
+      {"encoder.3.weight", 64 * 32 * 27},    {"encoder.3.bias", 64},
+      {"causal_net.0.weight", 256 * 1024},   {"causal_net.0.bias", 256},
+      {"causal_net.2.weight", 256 * 256},    {"causal_net.2.bias", 256},
+      {"classifier.0.weight", 128 * 1024},   {"classifier.0.bias", 128},
+      {"classifier.3.weight", 128},          {"classifier.3.bias", 1},
+  };
+  return L;
 }
 
 // encoder[0:3] (bbox:58-60): Conv3d(3->32, k3, p1) + bias -> ReLU -> MaxPool3d(2), fused, exact fp32 on the VALU.
@@ -159,7 +142,7 @@ struct BbPlanImpl {
     pool_vol = {B, 32, o1.D / 2, o1.H / 2, o1.W / 2};
     g2 = conv3d_geom(pool_vol, 64, 3, 1, 1, 1, 1);
   }
-  const float* P(int i) const { return params + bb_offsets().off[i]; }
+  const float* P(int i) const { return params + bb_layout().offsets[i]; }
 
   void carve(Ws& w) {
     cols1 = w.take<float>(g1.rows() * g1.K());
@@ -224,11 +207,7 @@ struct vad_bbox_plan {
 
 extern "C" {
 
-int vad_bbox_num_slots(void) { return BB_NSLOT; }
-const char* vad_bbox_slot_name(int i) { return (i >= 0 && i < BB_NSLOT) ? BB_SLOTS[i].name : nullptr; }
-int64_t vad_bbox_slot_numel(int i) { return (i >= 0 && i < BB_NSLOT) ? BB_SLOTS[i].numel : -1; }
-int64_t vad_bbox_slot_offset(int i) { return (i >= 0 && i < BB_NSLOT) ? bb_offsets().off[i] : -1; }
-int64_t vad_bbox_param_floats(void) { return bb_offsets().total; }
+VAD_FLAT_SLOT_ABI(bbox, (void), (int i), &bb_layout())
 
 int vad_bbox_create(int B, int T, int H, int W, vad_bbox_plan** out) {
   VAD_CHECK(out != nullptr, "vad_bbox_create: out is null");

@@ -16,25 +16,7 @@ namespace vad {
 
 // ------------------------------------------------------------------ parameter slot table (state_dict order)
 enum Group { G_FROZEN = 0, G_ALWAYS = 1, G_DET = 2, G_STRUCT = 3, G_NEVER = 4 };
-struct Slot {
-  std::string name;
-  int64_t numel;
-  int group;
-  int64_t offset;
-};
-struct BufSlot {
-  std::string name;
-  int64_t numel;
-  int64_t offset;
-};
-
-constexpr int64_t ALIGN = 256;
-static int64_t align_up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
-
-struct CadLayout {
-  std::vector<Slot> slots;
-  std::vector<BufSlot> bufs;
-  int64_t param_floats = 0, buf_floats = 0;
+struct CadLayout : FlatLayout {
   // indices
   int conv1_w, conv1_b, bn1_w, bn1_b;
   int conv_w[8], conv_b[8], bn_w[8], bn_b[8];
@@ -42,20 +24,12 @@ struct CadLayout {
   int head0;  // first head slot (tracker.reid_net.0.weight)
   int rm[9], rv[9];
   CadLayout() {
-    auto add = [&](const std::string& n, int64_t k, int g) {
-      slots.push_back({n, k, g, 0});
-      return (int)slots.size() - 1;
-    };
-    auto addb = [&](const std::string& n, int64_t k) {
-      bufs.push_back({n, k, 0});
-      return (int)bufs.size() - 1;
-    };
     conv1_w = add("backbone.conv1.weight", 32 * 49, G_FROZEN);
     conv1_b = add("backbone.conv1.bias", 32, G_FROZEN);
     bn1_w = add("backbone.bn1.weight", 32, G_FROZEN);
     bn1_b = add("backbone.bn1.bias", 32, G_FROZEN);
-    rm[0] = addb("backbone.bn1.running_mean", 32);
-    rv[0] = addb("backbone.bn1.running_var", 32);
+    rm[0] = add_buf("backbone.bn1.running_mean", 32);
+    rv[0] = add_buf("backbone.bn1.running_var", 32);
     const int cin[8] = {32, 32, 32, 64, 64, 128, 128, 256};
     const int cout[8] = {32, 32, 64, 64, 128, 128, 256, 256};
     for (int l = 0; l < 8; ++l) {
@@ -65,8 +39,8 @@ struct CadLayout {
       conv_b[l] = add(c + ".bias", cout[l], G_ALWAYS);
       bn_w[l] = add(b + ".weight", cout[l], G_ALWAYS);
       bn_b[l] = add(b + ".bias", cout[l], G_ALWAYS);
-      rm[l + 1] = addb(b + ".running_mean", cout[l]);
-      rv[l + 1] = addb(b + ".running_var", cout[l]);
+      rm[l + 1] = add_buf(b + ".running_mean", cout[l]);
+      rv[l + 1] = add_buf(b + ".running_var", cout[l]);
     }
     const int dims[6] = {6144, 512, 256, 128, 64, 20};
     const int didx[5] = {0, 3, 6, 8, 10};
@@ -113,18 +87,7 @@ struct CadLayout {
                      (int64_t)(i == 4 ? 2 : dims[i + 1]) * dims[i], G_ALWAYS);
       dir_b[i] = add("direct_classifier." + std::to_string(didx[i]) + ".bias", i == 4 ? 2 : dims[i + 1], G_ALWAYS);
     }
-    int64_t o = 0;
-    for (auto& s : slots) {
-      s.offset = o;
-      o = align_up(o + s.numel);
-    }
-    param_floats = o;
-    o = 0;
-    for (auto& b : bufs) {
-      b.offset = o;
-      o = align_up(o + b.numel);
-    }
-    buf_floats = o;
+    finish();
   }
 };
 
@@ -685,13 +648,13 @@ struct CadPlanImpl {
     img_tab.det = mlp_transpose_args();
     for (int i = 0; i < 160; ++i) img_tab.slot_img[i] = -1;
     for (int l = 0; l < pt.n; ++l) {
-      const Slot& s = LY.slots[LY.conv_w[l]];
+      const FlatSlot& s = LY.slots[LY.conv_w[l]];
       img_tab.slot_img[LY.conv_w[l]] = (int8_t)l;
       img_tab.off[l] = s.offset;
       img_tab.numel[l] = s.numel;
     }
     for (int j = 0; j < img_tab.det.n; ++j) {  // entry j: detector layer j + 1
-      const Slot& s = LY.slots[LY.det_w[j + 1]];
+      const FlatSlot& s = LY.slots[LY.det_w[j + 1]];
       img_tab.slot_img[LY.det_w[j + 1]] = (int8_t)(8 + j);
       img_tab.off[8 + j] = s.offset;
       img_tab.numel[8 + j] = s.numel;
@@ -1356,21 +1319,12 @@ int vad_synth_frames(uint64_t seed, uint64_t step, int64_t frame0, int64_t nfram
   return 0;
 }
 
-int vad_cad_num_slots(void) { return (int)layout().slots.size(); }
-const char* vad_cad_slot_name(int i) {
-  return (i >= 0 && i < vad_cad_num_slots()) ? layout().slots[i].name.c_str() : nullptr;
+VAD_FLAT_SLOT_ABI(cad, (void), (int i), &layout())
+VAD_FLAT_BUF_ABI(cad, (void), (int i), &layout())
+int vad_cad_slot_group(int i) {
+  const FlatSlot* s = flat_at(&layout(), &FlatLayout::slots, i);
+  return s ? s->group : -1;
 }
-int64_t vad_cad_slot_numel(int i) { return (i >= 0 && i < vad_cad_num_slots()) ? layout().slots[i].numel : -1; }
-int64_t vad_cad_slot_offset(int i) { return (i >= 0 && i < vad_cad_num_slots()) ? layout().slots[i].offset : -1; }
-int vad_cad_slot_group(int i) { return (i >= 0 && i < vad_cad_num_slots()) ? layout().slots[i].group : -1; }
-int64_t vad_cad_param_floats(void) { return layout().param_floats; }
-int vad_cad_num_bufs(void) { return (int)layout().bufs.size(); }
-const char* vad_cad_buf_name(int i) {
-  return (i >= 0 && i < vad_cad_num_bufs()) ? layout().bufs[i].name.c_str() : nullptr;
-}
-int64_t vad_cad_buf_numel(int i) { return (i >= 0 && i < vad_cad_num_bufs()) ? layout().bufs[i].numel : -1; }
-int64_t vad_cad_buf_offset(int i) { return (i >= 0 && i < vad_cad_num_bufs()) ? layout().bufs[i].offset : -1; }
-int64_t vad_cad_buf_floats(void) { return layout().buf_floats; }
 int vad_cad_num_bn(void) { return 9; }
 
 int vad_cad_create(int B, int T, int H, int W, vad_cad_plan** out) {

@@ -28,45 +28,27 @@ constexpr int MC_POOL[3][3] = {{1, 2, 2}, {2, 2, 2}, {2, 2, 2}};
 constexpr int MC_FC[4] = {32, 16, 8, 1};
 constexpr int MC_MAXB = 1024;
 
-struct McSlot {
-  std::string name;
-  int64_t numel, offset;
-};
-
-struct McLayout {
-  std::vector<McSlot> slots, bufs;
-  int64_t param_floats = 0, buf_floats = 0;
+struct McLayout : FlatLayout {
   int conv_w[3], conv_b[3], bn_w[3], bn_b[3], fc_w[3], fc_b[3], rm[3], rv[3];
   explicit McLayout(int C) {
-    auto add = [&](std::vector<McSlot>& v, const std::string& n, int64_t k) {
-      v.push_back({n, k, 0});
-      return (int)v.size() - 1;
-    };
     int ci = C;
     for (int s = 0; s < 3; ++s) {
       const std::string c = "features." + std::to_string(4 * s), b = "features." + std::to_string(4 * s + 1);
-      conv_w[s] = add(slots, c + ".weight", (int64_t)MC_CO[s] * ci * 27);
-      conv_b[s] = add(slots, c + ".bias", MC_CO[s]);
-      bn_w[s] = add(slots, b + ".weight", MC_CO[s]);
-      bn_b[s] = add(slots, b + ".bias", MC_CO[s]);
-      rm[s] = add(bufs, b + ".running_mean", MC_CO[s]);
-      rv[s] = add(bufs, b + ".running_var", MC_CO[s]);
+      conv_w[s] = add(c + ".weight", (int64_t)MC_CO[s] * ci * 27);
+      conv_b[s] = add(c + ".bias", MC_CO[s]);
+      bn_w[s] = add(b + ".weight", MC_CO[s]);
+      bn_b[s] = add(b + ".bias", MC_CO[s]);
+      rm[s] = add_buf(b + ".running_mean", MC_CO[s]);
+      rv[s] = add_buf(b + ".running_var", MC_CO[s]);
       ci = MC_CO[s];
     }
     const int fidx[3] = {1, 4, 6};
     for (int i = 0; i < 3; ++i) {
       const std::string f = "classifier." + std::to_string(fidx[i]);
-      fc_w[i] = add(slots, f + ".weight", (int64_t)MC_FC[i + 1] * MC_FC[i]);
-      fc_b[i] = add(slots, f + ".bias", MC_FC[i + 1]);
+      fc_w[i] = add(f + ".weight", (int64_t)MC_FC[i + 1] * MC_FC[i]);
+      fc_b[i] = add(f + ".bias", MC_FC[i + 1]);
     }
-    for (auto& s : slots) {
-      s.offset = param_floats;
-      param_floats += (s.numel + 255) / 256 * 256;
-    }
-    for (auto& b : bufs) {
-      b.offset = buf_floats;
-      buf_floats += (b.numel + 255) / 256 * 256;
-    }
+    finish();
   }
 };
 
@@ -414,12 +396,10 @@ struct McPlanImpl {
   }
 
   int optimizer(float lr, float b1, float b2, float eps, float wd, float clip_above, float max_norm, hipStream_t st) {
-    const AdamSlots t = adam_slots((int)LY.slots.size(), [&](int i) { return LY.slots[i].offset; },
-                                   [&](int i) { return LY.slots[i].numel; });
     // coupled decay; the clip only above clip_above (mc:304-306); losses[1] norm, [2] clipped, [3] the status word
     const AdamStep a{lr, b1, b2, eps, wd, false, clip_above, max_norm, 1.f, losses + 3, losses + 1, nullptr,
                      losses + 2, losses + 3};
-    return adam_clip_step(t, params, grads, m, v, LY.param_floats, steps, aws, a, st);
+    return adam_clip_step(LY.adam_slots(), params, grads, m, v, LY.param_floats, steps, aws, a, st);
   }
 };
 
@@ -455,28 +435,8 @@ int vad_mc_create(int B, int C, int T, int H, int W, vad_mc_plan** out) {
 
 void vad_mc_destroy(vad_mc_plan* plan) { delete plan; }
 
-int vad_mc_num_slots(const vad_mc_plan* p) { return p ? (int)p->impl.LY.slots.size() : -1; }
-const char* vad_mc_slot_name(const vad_mc_plan* p, int i) {
-  return (p && i >= 0 && i < vad_mc_num_slots(p)) ? p->impl.LY.slots[i].name.c_str() : nullptr;
-}
-int64_t vad_mc_slot_numel(const vad_mc_plan* p, int i) {
-  return (p && i >= 0 && i < vad_mc_num_slots(p)) ? p->impl.LY.slots[i].numel : -1;
-}
-int64_t vad_mc_slot_offset(const vad_mc_plan* p, int i) {
-  return (p && i >= 0 && i < vad_mc_num_slots(p)) ? p->impl.LY.slots[i].offset : -1;
-}
-int64_t vad_mc_param_floats(const vad_mc_plan* p) { return p ? p->impl.LY.param_floats : -1; }
-int vad_mc_num_bufs(const vad_mc_plan* p) { return p ? (int)p->impl.LY.bufs.size() : -1; }
-const char* vad_mc_buf_name(const vad_mc_plan* p, int i) {
-  return (p && i >= 0 && i < vad_mc_num_bufs(p)) ? p->impl.LY.bufs[i].name.c_str() : nullptr;
-}
-int64_t vad_mc_buf_numel(const vad_mc_plan* p, int i) {
-  return (p && i >= 0 && i < vad_mc_num_bufs(p)) ? p->impl.LY.bufs[i].numel : -1;
-}
-int64_t vad_mc_buf_offset(const vad_mc_plan* p, int i) {
-  return (p && i >= 0 && i < vad_mc_num_bufs(p)) ? p->impl.LY.bufs[i].offset : -1;
-}
-int64_t vad_mc_buf_floats(const vad_mc_plan* p) { return p ? p->impl.LY.buf_floats : -1; }
+VAD_FLAT_SLOT_ABI(mc, (const vad_mc_plan* p), (const vad_mc_plan* p, int i), p ? &p->impl.LY : nullptr)
+VAD_FLAT_BUF_ABI(mc, (const vad_mc_plan* p), (const vad_mc_plan* p, int i), p ? &p->impl.LY : nullptr)
 int64_t vad_mc_workspace_bytes(const vad_mc_plan* p) { return p ? p->impl.ws_bytes : -1; }
 
 int vad_mc_bind(vad_mc_plan* plan, void* workspace, float* params, float* grads, float* bufs, int64_t* nbt,

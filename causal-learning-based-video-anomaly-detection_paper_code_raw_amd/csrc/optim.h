@@ -9,25 +9,8 @@
 
 namespace vad {
 
-constexpr int ADAM_MAX_SLOTS = 64;
 constexpr int ADAM_SQ_CHUNKS = 64;  // blocks per slot of the squared-norm pass (fixed-order partials)
-
-struct AdamSlots {
-  int n;
-  int64_t off[ADAM_MAX_SLOTS], numel[ADAM_MAX_SLOTS];
-};
-
-// the table of a plan's n slots: off(i), numel(i) in floats (n above the cap is refused by adam_clip_step)
-template <class Off, class Numel>
-AdamSlots adam_slots(int n, Off off, Numel numel) {
-  AdamSlots t{};
-  t.n = n;
-  for (int i = 0; i < n && i < ADAM_MAX_SLOTS; ++i) {
-    t.off[i] = off(i);
-    t.numel[i] = numel(i);
-  }
-  return t;
-}
+// (AdamSlots, the slot table of a step, comes from the plan's FlatLayout::adam_slots(): plan_util.h)
 
 struct AdamWs {
   double* sq;   // [ADAM_MAX_SLOTS][ADAM_SQ_CHUNKS]

@@ -17,34 +17,29 @@ import ctypes
 import torch
 
 from . import _native as nat
+from ._flat import FlatEngine, FlatPlan
 
 GROUP_FROZEN, GROUP_ALWAYS, GROUP_DET, GROUP_STRUCT, GROUP_NEVER = range(5)
 
 
-class _Plan:
+class _Plan(FlatPlan):
     def __init__(self, engine, B, T, H, W):
-        L = nat.lib()
-        h = ctypes.c_void_p()
-        nat.check(L.vad_cad_create(B, T, H, W, ctypes.byref(h)))
-        self.h = h
-        nat.check(L.vad_cad_set_option(h, b"conv_bf16", 1 if engine.compute_dtype == torch.bfloat16 else 0))
-        # (the workspace is carved for the options set before the size query: the training stem's buffers only when
-        # the stem trains -- CadEngine.plan builds a new plan when that changes)
-        self.stem_grad = engine.stem_trains()
-        self.ws_stem = self.stem_grad
-        nat.check(L.vad_cad_set_option(h, b"stem_grad", 1 if self.stem_grad else 0))
+        super().__init__(engine, B, T, H, W)
         self.shape = (B, T, H, W)
-        nbytes = L.vad_cad_workspace_bytes(h)
-        self.ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=engine.device)
-        base = (self.ws.data_ptr() + 255) // 256 * 256
-        e = engine
-        nat.check(L.vad_cad_bind(h, base, e.params.data_ptr(), e.grads.data_ptr(), e.bufs.data_ptr(),
-                                 e.nbt.data_ptr(), nat.ptr(e.exp_avg), nat.ptr(e.exp_avg_sq), nat.ptr(e.steps)))
         self._sync_cb = None
         self.apply_bn_sync(engine)
         # CadEngine._weights_version() at which this plan's weight images were last known to hold the parameters
         # (None: not known, the next forward relayouts)
         self.img_ver = None
+
+    def configure(self, engine, *key):
+        L = nat.lib()
+        nat.check(L.vad_cad_set_option(self.h, b"conv_bf16", 1 if engine.compute_dtype == torch.bfloat16 else 0))
+        # (the workspace is carved for the options set before the size query: the training stem's buffers only when
+        # the stem trains -- CadEngine.plan builds a new plan when that changes)
+        self.stem_grad = engine.stem_trains()
+        self.ws_stem = self.stem_grad
+        nat.check(L.vad_cad_set_option(self.h, b"stem_grad", 1 if self.stem_grad else 0))
 
     def apply_bn_sync(self, engine):
         """Install (or clear) the SyncBatchNorm callback: an all-reduce of the plan's [2C] double sums buffer over
@@ -72,67 +67,19 @@ class _Plan:
         self._sync_cb = nat.BN_SYNC_FN(_cb)  # kept alive as long as the plan
         nat.check(L.vad_cad_set_bn_sync(self.h, self._sync_cb, None, world))
 
-    def rebind(self, engine):
-        e = engine
-        base = (self.ws.data_ptr() + 255) // 256 * 256
-        nat.check(nat.lib().vad_cad_bind(self.h, base, e.params.data_ptr(), e.grads.data_ptr(), e.bufs.data_ptr(),
-                                         e.nbt.data_ptr(), nat.ptr(e.exp_avg), nat.ptr(e.exp_avg_sq),
-                                         nat.ptr(e.steps)))
 
-    def __del__(self):
-        try:
-            if self.h:
-                nat.lib().vad_cad_destroy(self.h)
-        except Exception:
-            pass
+class CadEngine(FlatEngine):
+    PLAN = _Plan
 
-
-class CadEngine:
     def __init__(self, model: torch.nn.Module):
-        L = nat.lib()
-        self.model = model
         p0 = next(model.parameters())
         nat.require_hip(p0)
-        self.device = p0.device
-        n = L.vad_cad_num_slots()
-        self.slot_names = [L.vad_cad_slot_name(i).decode() for i in range(n)]
-        self.slot_numel = [L.vad_cad_slot_numel(i) for i in range(n)]
-        self.slot_offset = [L.vad_cad_slot_offset(i) for i in range(n)]
-        self.slot_group = [L.vad_cad_slot_group(i) for i in range(n)]
-        self.param_floats = L.vad_cad_param_floats()
-        named = list(model.named_parameters())
-        if [k for k, _ in named] != self.slot_names:
-            raise RuntimeError("model parameters do not match the libvadhip slot table")
-        for (k, p), nel in zip(named, self.slot_numel):
-            if p.numel() != nel:
-                raise RuntimeError(f"parameter {k}: {p.numel()} elements, library expects {nel}")
-        dev = self.device
-        self.params = torch.zeros(self.param_floats, dtype=torch.float32, device=dev)
-        self.grads = torch.zeros(self.param_floats + 256, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            for (k, p), off in zip(named, self.slot_offset):
-                view = self.params[off:off + p.numel()].view_as(p)
-                view.copy_(p.data)
-                p.data = view
-        nb = L.vad_cad_num_bufs()
-        self.buf_names = [L.vad_cad_buf_name(i).decode() for i in range(nb)]
-        self.buf_offset = [L.vad_cad_buf_offset(i) for i in range(nb)]
-        self.bufs = torch.zeros(L.vad_cad_buf_floats(), dtype=torch.float32, device=dev)
-        named_bufs = dict(model.named_buffers())
-        with torch.no_grad():
-            for k, off in zip(self.buf_names, self.buf_offset):
-                b = named_bufs[k]
-                view = self.bufs[off:off + b.numel()].view_as(b)
-                view.copy_(b)
-                _set_buffer(model, k, view)
-        nbt_names = [k for k in named_bufs if k.endswith("num_batches_tracked")]
-        if len(nbt_names) != L.vad_cad_num_bn():
+        self._compute_dtype = torch.float32
+        super().__init__(model, p0.device, "cad", replace_params=False, opt_state="lazy", grad_tail=256,
+                         bind_names=("params", "grads", "bufs", "nbt", "exp_avg", "exp_avg_sq", "steps"))
+        if len(self.nbt) != nat.lib().vad_cad_num_bn():
             raise RuntimeError("unexpected number of BatchNorm layers")
-        self.nbt = torch.zeros(len(nbt_names), dtype=torch.int64, device=dev)
-        with torch.no_grad():
-            for i, k in enumerate(nbt_names):
-                self.nbt[i].copy_(named_bufs[k].reshape(()))
-                _set_buffer(model, k, self.nbt[i])
+        named = list(model.named_parameters())
         # (the stem's Parameter objects, for the per-call requires_grad check: building the named-parameter dict
         # costs ~0.3 ms of host time, twice per step, on the step's critical path where the GPU runs short kernels)
         self._stem_params = [p for k, p in named if k in self.STEM]
@@ -142,10 +89,10 @@ class CadEngine:
             k.startswith("detector.detector_net.") and k.endswith(".weight") and not k.endswith(".0.weight"))]
         if len(self._image_params) != 12:
             raise RuntimeError("unexpected number of conv / detector weights with derived images")
-        self.exp_avg = self.exp_avg_sq = self.steps = None
+        # length of the backbone's leading run of slots in the flat buffers (named_parameters order)
+        self.backbone_floats = next(o for n, o in zip(self.slot_names, self.slot_offset)
+                                    if not n.startswith("backbone."))
         self.bn_sync = None  # (process_group, world) in SyncBatchNorm mode
-        self._compute_dtype = torch.float32
-        self.plans = {}
         self.generation = 0
         self._last = None
         self._loss_buf = None
@@ -178,18 +125,6 @@ class CadEngine:
             self.bn_sync = None
         for p in self.plans.values():
             p.apply_bn_sync(self)
-
-    def is_bound(self) -> bool:
-        p = next(self.model.parameters())
-        return p.data_ptr() == self.params.data_ptr() and p.device == self.device
-
-    def init_optimizer_state(self):
-        if self.exp_avg is None:
-            self.exp_avg = torch.zeros_like(self.params)
-            self.exp_avg_sq = torch.zeros_like(self.params)
-            self.steps = torch.zeros(len(self.slot_names), dtype=torch.int32, device=self.device)
-            for p in self.plans.values():
-                p.rebind(self)
 
     def plan(self, B, T, H, W) -> _Plan:
         key = (B, T, H, W)
@@ -333,11 +268,6 @@ class CadEngine:
             pl.stem_grad = on
         self.stem_grad_on = on
 
-    @property
-    def backbone_floats(self) -> int:
-        """Length of the backbone's leading run of slots in the flat buffers (named_parameters order)."""
-        return next(o for n, o in zip(self.slot_names, self.slot_offset) if not n.startswith("backbone."))
-
     def profile(self, enable: bool, only_prefix: str = "", reset: bool = True):
         """HIP-event timing of the plan's labelled launches (all plans of this engine).  enable=False pauses (the
         records are kept); enable=True clears them first unless reset=False."""
@@ -383,14 +313,6 @@ class CadEngine:
                 q.img_ver = None
         nat.check(nat.lib().vad_cad_optimizer_step(pl.h, lr, betas[0], betas[1], eps, weight_decay, max_norm,
                                                    grad_scale, nat.ptr(total_norm), nat.stream_of(self.device)))
-
-
-def _set_buffer(model, dotted, tensor):
-    mod = model
-    parts = dotted.split(".")
-    for p in parts[:-1]:
-        mod = getattr(mod, p)
-    mod._buffers[parts[-1]] = tensor
 
 
 def engine_for(model) -> CadEngine:

@@ -2,9 +2,10 @@
 
 Same class names, constructor signatures, submodule names (state_dict keys ``features.N.*``, ``classifier.N.*``),
 initialisation order (mc:76-88: so a given torch seed draws the reference's weights) and forward return
-``(B, 1)`` sigmoid scores (mc:90-102).  The compute goes through ``libvadhip.so`` (``vad_mc_*``): 3-D convs as
-im2col + f32 MFMA GEMMs, train-mode BatchNorm3d, fused BN+ReLU+MaxPool3d, the classifier, BCE, and the
-StableTrainer update (NaN/Inf skip, conditional clip, Adam with coupled L2) in device kernels.
+``(B, 1)`` sigmoid scores (mc:90-102).  The compute goes through ``libvadhip.so`` (``vad_mc_*``): 3-D convs on the
+direct kernels (knob ``conv3d_direct``; 0: im2col + f32 MFMA GEMMs), train-mode BatchNorm3d, fused BN+ReLU+MaxPool3d,
+the classifier, BCE, and the StableTrainer update (NaN/Inf skip, conditional clip, Adam with coupled L2) in device
+kernels.
 """
 from __future__ import annotations
 
@@ -15,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
+from ._flat import FlatEngine
 
 
 class SimpleVideoAnomalyDetector(nn.Module):
@@ -59,7 +61,6 @@ class SimpleVideoAnomalyDetector(nn.Module):
         if e is None or e.device != x.device:
             e = McEngine(self, x.device)
             self._engine = e
-        e.sync_from_module()
         e.use_shape(tuple(x.shape))
         return e
 
@@ -91,100 +92,28 @@ class _McFunction(torch.autograd.Function):
     def backward(ctx, d_scores):
         e = ctx.e
         e.backward_from_scores(d_scores.reshape(-1).contiguous().float())
-        grads = e.grad_views_for_autograd()
-        return (None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, *e.grad_clones())
 
 
-class _McPlan:
-    """One C plan + workspace per input shape, bound to the engine's shared flat buffers."""
-
-    def __init__(self, e: "McEngine", shape):
-        lib = nat.lib()
-        plan = ctypes.c_void_p()
-        nat.check(lib.vad_mc_create(*shape, ctypes.byref(plan)))
-        self.plan = plan
-        self.ws = torch.empty(lib.vad_mc_workspace_bytes(plan) + 256, dtype=torch.uint8, device=e.device)
-        base = (self.ws.data_ptr() + 255) // 256 * 256
-        nat.check(lib.vad_mc_bind(plan, ctypes.c_void_p(base), nat.ptr(e.params), nat.ptr(e.grads), nat.ptr(e.bufs),
-                                  nat.ptr(e.nbt), nat.ptr(e.exp_avg), nat.ptr(e.exp_avg_sq), nat.ptr(e.steps)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "plan", None):
-                nat.lib().vad_mc_destroy(self.plan)
-        except Exception:
-            pass
-
-
-class McEngine:
-    """Flat device buffers (params / grads / BN buffers / Adam state, state_dict order) shared by per-shape plans."""
+class McEngine(FlatEngine):
+    """Flat device buffers (params / grads / BN buffers / Adam state, state_dict order) shared by per-shape plans
+    (keyed by the input's (B, C, T, H, W))."""
 
     def __init__(self, model: SimpleVideoAnomalyDetector, device):
-        lib = nat.lib()
-        self.device, self.model, self.seed = device, model, 1234
-        C = model.features[0].in_channels
-        probe = ctypes.c_void_p()
-        nat.check(lib.vad_mc_create(1, C, 8, 8, 8, ctypes.byref(probe)))  # the slot table depends on C only
-        try:
-            self.slots = [(lib.vad_mc_slot_name(probe, i).decode(), lib.vad_mc_slot_offset(probe, i),
-                           lib.vad_mc_slot_numel(probe, i)) for i in range(lib.vad_mc_num_slots(probe))]
-            self.bufs_meta = [(lib.vad_mc_buf_name(probe, i).decode(), lib.vad_mc_buf_offset(probe, i),
-                               lib.vad_mc_buf_numel(probe, i)) for i in range(lib.vad_mc_num_bufs(probe))]
-            nparam, nbuf = lib.vad_mc_param_floats(probe), lib.vad_mc_buf_floats(probe)
-        finally:
-            lib.vad_mc_destroy(probe)
-        f = dict(dtype=torch.float32, device=device)
-        self.params = torch.zeros(nparam, **f)
-        self.grads = torch.zeros(nparam + 256, **f)
-        self.bufs = torch.zeros(nbuf, **f)
-        self.nbt = torch.zeros(3, dtype=torch.int64, device=device)
-        self.exp_avg = torch.zeros_like(self.params)
-        self.exp_avg_sq = torch.zeros_like(self.params)
-        self.steps = torch.zeros(len(self.slots), dtype=torch.int32, device=device)
-        self.losses = torch.zeros(4, **f)  # bce, grad_norm, clipped, status
+        super().__init__(model, device, "mc", replace_params=True, opt_state="eager", grad_tail=256,
+                         bind_names=("params", "grads", "bufs", "nbt", "exp_avg", "exp_avg_sq", "steps"))
+        self.seed = 1234
+        self.losses = torch.zeros(4, dtype=torch.float32, device=device)  # bce, grad_norm, clipped, status
         self.flags = torch.zeros(4, dtype=torch.int32, device=device)
-        sd = dict(model.named_parameters())
-        self.param_views = [self.params[off:off + n].view_as(sd[name]) for name, off, n in self.slots]
-        self._bound = False
-        self.plans = {}
-        self.cur = None
         self.scores = None
 
     def use_shape(self, shape):
-        if shape not in self.plans:
-            self.plans[shape] = _McPlan(self, shape)
-        self.cur = self.plans[shape]
+        self.cur = self.plan(*shape)
         if self.scores is None or self.scores.numel() != shape[0]:
             self.scores = torch.zeros(shape[0], dtype=torch.float32, device=self.device)
 
-    def stream(self):
-        return nat.stream_of(self.device)
-
-    def sync_from_module(self):
-        """Point the module's parameters / BN buffers at the flat device buffers (copied once)."""
-        if self._bound:
-            return
-        m = self.model
-        with torch.no_grad():
-            sd = dict(m.named_parameters())
-            for (name, off, n), view in zip(self.slots, self.param_views):
-                view.copy_(sd[name].detach().to(self.device))
-                mod_name, attr = name.rsplit(".", 1)
-                setattr(m.get_submodule(mod_name), attr, nn.Parameter(view, requires_grad=sd[name].requires_grad))
-            mods = dict(m.named_modules())
-            for name, off, n in self.bufs_meta:
-                mod_name, attr = name.rsplit(".", 1)
-                mod = mods[mod_name]
-                view = self.bufs[off:off + n].view_as(getattr(mod, attr))
-                view.copy_(getattr(mod, attr).to(self.device))
-                mod._buffers[attr] = view
-            for i, b in enumerate(("features.1", "features.5", "features.9")):
-                self.nbt[i] = int(mods[b].num_batches_tracked)
-                mods[b]._buffers["num_batches_tracked"] = self.nbt[i:i + 1].view(())
-        self._bound = True
-
     def forward(self, x, training, seed, step, clip0, labels=None):
-        nat.check(nat.lib().vad_mc_forward(self.cur.plan, nat.ptr(x), int(training), ctypes.c_uint64(seed),
+        nat.check(nat.lib().vad_mc_forward(self.cur.h, nat.ptr(x), int(training), ctypes.c_uint64(seed),
                                            ctypes.c_uint64(step), ctypes.c_int64(clip0),
                                            nat.ptr(labels) if labels is not None else None, nat.ptr(self.scores),
                                            nat.ptr(self.losses), nat.ptr(self.flags), self.stream()))
@@ -192,16 +121,13 @@ class McEngine:
 
     def backward(self):
         """Backward of the BCE loss of the last forward (StableTrainer path)."""
-        nat.check(nat.lib().vad_mc_backward(self.cur.plan, None, self.stream()))
+        nat.check(nat.lib().vad_mc_backward(self.cur.h, None, self.stream()))
 
     def backward_from_scores(self, d_scores):
-        nat.check(nat.lib().vad_mc_backward(self.cur.plan, nat.ptr(d_scores), self.stream()))
-
-    def grad_views_for_autograd(self):
-        return [self.grads[off:off + n].view_as(v).clone() for (name, off, n), v in zip(self.slots, self.param_views)]
+        nat.check(nat.lib().vad_mc_backward(self.cur.h, nat.ptr(d_scores), self.stream()))
 
     def optimizer_step(self, lr, wd=1e-5, b1=0.9, b2=0.999, eps=1e-8, clip_above=10.0, max_norm=1.0):
-        nat.check(nat.lib().vad_mc_optimizer_step(self.cur.plan, ctypes.c_float(lr), ctypes.c_float(b1),
+        nat.check(nat.lib().vad_mc_optimizer_step(self.cur.h, ctypes.c_float(lr), ctypes.c_float(b1),
                                                   ctypes.c_float(b2), ctypes.c_float(eps), ctypes.c_float(wd),
                                                   ctypes.c_float(clip_above), ctypes.c_float(max_norm),
                                                   self.stream()))

@@ -38,8 +38,8 @@ def test_a2_step_matches_reference(case):
         assert v == pytest.approx(float(g[f"loss/{k}"]), rel=1e-4, abs=1e-6), k
     assert float(e.losses[8]) == pytest.approx(float(g["grad_total_norm"]), rel=1e-3)
     sd = dict(vad.model.named_parameters())
-    for name, off, n in e.slots:
-        gf = e.grads[off:off + n].cpu().numpy()
+    for name, gf in e.grad_dict().items():
+        gf, n = gf.cpu().numpy(), gf.numel()
         ref = float(g[f"grad_norm/{name}"])
         assert float(np.linalg.norm(gf.astype(np.float64))) == pytest.approx(ref, rel=2e-3, abs=1e-12), name
         np.testing.assert_allclose(gf[g[f"idx/{name}"]], g[f"grad/{name}"], rtol=2e-3,
@@ -98,7 +98,7 @@ def test_a2_direct_and_im2col_paths_agree():
             vad = _vad(case)
             avg, _ = vad.train_epoch_improved([(x, ao.synth_labels(0, 6))])
             e = vad.model._engine
-            res.append((avg, {n: e.grads[off:off + k].cpu().double() for n, off, k in e.slots}))
+            res.append((avg, {n: g.cpu().double() for n, g in e.grad_dict().items()}))
         finally:
             nat.check(nat.lib().vad_set_tuning(b"a2_direct", 1))
     assert res[0][0] == pytest.approx(res[1][0], rel=1e-6)

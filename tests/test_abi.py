@@ -5,6 +5,7 @@ import os
 import re
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import rng
@@ -67,47 +68,84 @@ def test_tuning_table():
     assert not missing, missing
 
 
-def test_slot_table_matches_module():
-    from vad_amd import _native
+def _cad_model():
     from vad_amd.cad import CausalAnomalyDetector
-    L = _native.lib()
-    torch.manual_seed(0)
-    m = CausalAnomalyDetector()
-    named = list(m.named_parameters())
-    assert L.vad_cad_num_slots() == len(named)
-    off_prev = -1
-    for i, (k, p) in enumerate(named):
-        assert L.vad_cad_slot_name(i).decode() == k
-        assert L.vad_cad_slot_numel(i) == p.numel()
-        off = L.vad_cad_slot_offset(i)
-        assert off % 256 == 0 and off > off_prev
-        off_prev = off
-    assert L.vad_cad_param_floats() >= off_prev + named[-1][1].numel()
-    bufs = [k for k in m.state_dict() if "running" in k]
-    assert [L.vad_cad_buf_name(i).decode() for i in range(L.vad_cad_num_bufs())] == bufs
-    groups = {L.vad_cad_slot_name(i).decode(): L.vad_cad_slot_group(i) for i in range(len(named))}
-    assert groups["backbone.conv1.weight"] == 0 and groups["structure_learner.structure_params"] == 4
-    assert groups["detector.detector_net.0.weight"] == 2 and groups["structure_learner.node_encoder.weight"] == 3
+    return CausalAnomalyDetector()
 
 
-def test_ae_slot_table_matches_module():
-    """cad1 VideoAutoEncoder: library slots = named_parameters(), buffers = the BN running stats in state_dict order."""
-    from vad_amd import _native
+def _mc_model(C):
+    from vad_amd.mc import SimpleVideoAnomalyDetector
+    return SimpleVideoAnomalyDetector(input_channels=C)
+
+
+def _a2_model():
+    from vad_amd.a2 import CausalAnomalyDetector
+    return CausalAnomalyDetector()
+
+
+def _bbox_model():
+    from vad_amd.bbox import CausalAnomalyDetector
+    return CausalAnomalyDetector()
+
+
+def _ae_model():
     from vad_amd.ae import VideoAutoEncoder
+    return VideoAutoEncoder()
+
+
+# id -> (C prefix, model, has a buffer table, mc's input channels: its accessors take a plan)
+_LAYOUTS = {"cad": ("cad", _cad_model, True, None), "mc_c1": ("mc", lambda: _mc_model(1), True, 1),
+            "mc_c3": ("mc", lambda: _mc_model(3), True, 3), "a2": ("a2", _a2_model, False, None),
+            "bbox": ("bbox", _bbox_model, False, None), "ae": ("ae", _ae_model, True, None)}
+
+
+@pytest.mark.parametrize("name", list(_LAYOUTS))
+def test_slot_table_matches_module(name):
+    """Every model's library tables against its module: slots = named_parameters(), buffers = the BN running stats in
+    state_dict order, both laid out by the one rule (running sum, each slot rounded up to 256 floats)."""
+    from vad_amd import _native
     L = _native.lib()
+    pfx, make, has_bufs, C = _LAYOUTS[name]
     torch.manual_seed(0)
-    m = VideoAutoEncoder()
-    named = list(m.named_parameters())
-    assert L.vad_ae_num_slots() == len(named)
-    for i, (k, p) in enumerate(named):
-        assert L.vad_ae_slot_name(i).decode() == k
-        assert L.vad_ae_slot_numel(i) == p.numel()
-        assert L.vad_ae_slot_offset(i) % 256 == 0
-    assert [L.vad_ae_buf_name(i).decode() for i in range(L.vad_ae_num_bufs())] == \
-        [k for k in m.state_dict() if "running" in k]
-    h = ctypes.c_void_p()
-    assert L.vad_ae_create(501, 8, ctypes.byref(h)) != 0  # update_memory writes B rows of the 500-row ring
-    assert b"unsupported shape" in L.vad_last_error()
+    m = make()
+    pre = ()
+    if C is not None:
+        h = ctypes.c_void_p()
+        assert L.vad_mc_create(1, C, 4, 8, 8, ctypes.byref(h)) == 0  # the smallest legal shape; runs on the host
+        pre = (h,)
+
+    def check(kind, total, want):
+        fn = lambda s: getattr(L, f"vad_{pfx}_{s}")  # noqa: E731
+        n = fn(f"num_{kind}s")(*pre)
+        assert n == len(want)
+        off = 0
+        for i, (k, numel) in enumerate(want):
+            assert fn(f"{kind}_name")(*pre, i).decode() == k
+            assert fn(f"{kind}_numel")(*pre, i) == numel
+            assert fn(f"{kind}_offset")(*pre, i) == off, k
+            off += (numel + 255) // 256 * 256
+        assert fn(total)(*pre) == off
+        for i in (-1, n):
+            assert fn(f"{kind}_name")(*pre, i) is None
+            assert fn(f"{kind}_numel")(*pre, i) == -1 and fn(f"{kind}_offset")(*pre, i) == -1
+
+    try:
+        named = [(k, p.numel()) for k, p in m.named_parameters()]
+        check("slot", "param_floats", named)
+        if has_bufs:
+            check("buf", "buf_floats", [(k, v.numel()) for k, v in m.state_dict().items() if "running_" in k])
+    finally:
+        if pre:
+            L.vad_mc_destroy(pre[0])
+    if name == "cad":
+        assert L.vad_cad_slot_group(-1) == -1 and L.vad_cad_slot_group(len(named)) == -1
+        groups = {L.vad_cad_slot_name(i).decode(): L.vad_cad_slot_group(i) for i in range(len(named))}
+        assert groups["backbone.conv1.weight"] == 0 and groups["structure_learner.structure_params"] == 4
+        assert groups["detector.detector_net.0.weight"] == 2 and groups["structure_learner.node_encoder.weight"] == 3
+    if name == "ae":
+        h = ctypes.c_void_p()
+        assert L.vad_ae_create(501, 8, ctypes.byref(h)) != 0  # update_memory writes B rows of the 500-row ring
+        assert b"unsupported shape" in L.vad_last_error()
 
 
 def test_error_codes_and_text():

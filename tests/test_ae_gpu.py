@@ -52,11 +52,10 @@ def test_ae_train_steps_match_reference(case):
         losses.append(float(l[0]))
         norms.append(float(l[1]))
         if first is None:
-            first = e.grads.cpu().numpy().copy()
+            first = {name: gf.cpu().numpy() for name, gf in e.grad_dict().items()}
     np.testing.assert_allclose(losses, g["train/step_loss"], rtol=1e-4)
     np.testing.assert_allclose(norms, g["train/norms"], rtol=2e-3)
-    for name, off, n in e.slots:
-        gf = first[off:off + n]
+    for name, gf in first.items():
         if name in PRE_BN_BIASES:
             wn = float(g[f"grad_norm/{name[:-4]}weight"])
             assert float(np.abs(gf).max()) <= 1e-4 * wn + 1e-9, name  # exactly-zero true grad: noise level

@@ -49,8 +49,7 @@ def _d64(d):
 
 
 def _device_slots(e):
-    g = e.grads.cpu().numpy().astype(np.float64)
-    return {name: g[off:off + n] for name, off, n in e.slots}
+    return {name: g.cpu().numpy().astype(np.float64) for name, g in e.grad_dict().items()}
 
 
 def _check(dev, ref, pre_bn, label, bound=None):

@@ -51,8 +51,8 @@ def _mc_step_case(case):
     assert int(losses[2]) == int(g["clipped"])
     assert int(losses[3]) == 2
     sd = model.state_dict()
-    for name, off, n in e.slots:
-        gf = e.grads[off:off + n].cpu().numpy()
+    for name, gf in e.grad_dict().items():
+        gf = gf.cpu().numpy()
         ref = float(g[f"grad_norm/{name}"])
         if name in PRE_BN_BIASES:
             # the conv bias feeding a train-mode BatchNorm has an exactly-zero true gradient (BN removes the
