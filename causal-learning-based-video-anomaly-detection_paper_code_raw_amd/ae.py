@@ -131,6 +131,16 @@ class VideoAutoEncoder(nn.Module):
         """cad1:262-301."""
         return self.engine().memory_score(sequence_feature)
 
+    def score_video(self, frames, window=16, stride=1, *, chunk=256, return_reconstructions=False):
+        """Eval-mode scores of every window of one video, each frame encoded once (ae_video.py).  frames
+        (N, 1, 64, 64) or (1, N, 1, 64, 64); window w = frames w*stride .. w*stride + window - 1 ->
+        {'anomaly_scores' (Wn,) = 0.7 * 'recon_errors' + 0.3 * 'memory_scores', 'sequence_features' (Wn, 64),
+        'frame_features' (N, 64), 'window_starts' (Wn,) int64 on the CPU, and with return_reconstructions
+        'reconstructed' (Wn, 1, 64, 64): the one frame the decoder gives per window}; what the clip path
+        (calculate_anomaly_scores, cad1:542-552) gives for that clip.  Changes nothing in the model."""
+        from .ae_video import score_video
+        return score_video(self, frames, window, stride, chunk=chunk, return_reconstructions=return_reconstructions)
+
     def forward(self, frames):
         x = _clip_input(frames)
         e = self.engine()

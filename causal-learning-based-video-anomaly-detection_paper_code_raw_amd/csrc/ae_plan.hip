@@ -27,6 +27,10 @@
 // GEMMs with K = 16 for the 1-channel layer -- the round-4 path, kept as the cross-check of the direct kernels:
 // tests/test_ae_gpu.py::test_ae_direct_and_im2col_paths_agree)
 //   update    non-finite-grad skip + clip_grad_norm_(0.1) + Adam with coupled L2 (optim.h)
+//   scoring   a whole video in sliding windows, eval mode (vad_ae_frames_forward / vad_ae_windows_forward): the
+//             encoder and the LSTM input projection once per frame into a frame cache, then per window the
+//             recurrence over cached rows (the LSTM kernel's WIN instantiation), ring score, one decoder call and
+//             the error against the window's T frames
 // Status word (losses[3]): 0 = skipped before backward (train-loop mode: a non-finite input, cad1:385-387 -- the BN
 // running stats, counters and the memory ring stay untouched, as the reference's `continue` before the forward -- or
 // a non-finite loss), 1 = non-finite grads, no step, 2 = stepped.
@@ -58,6 +62,12 @@ constexpr int AE_NBN = 7;
 constexpr int AE_WGRAD_BLOCKS = 1024;
 constexpr int ENC_CI[4] = {1, 32, 64, 128}, ENC_CO[4] = {32, 64, 128, 128}, ENC_IN[4] = {64, 32, 16, 8};
 constexpr int DEC_CI[4] = {128, 128, 64, 32}, DEC_CO[4] = {128, 64, 32, 1}, DEC_IN[4] = {4, 8, 16, 32};
+
+// Frame cache of the sliding-window scoring (include/vad.h): arrays over the video's frames, each 64-float aligned
+struct AeFrameCache {
+  int64_t lat, gx, total;  // offsets in floats: lat [N][64] (tanh latents), gx [N][256] (W_ih lat + b_ih)
+  explicit AeFrameCache(int64_t n) : lat(0), gx(n * AE_LAT), total(n * (AE_LAT + AE_GATES)) {}
+};
 
 // model.named_parameters() and BN running-stat order (cad1:129-188)
 struct AeLayout : FlatLayout {
@@ -525,12 +535,19 @@ __global__ __launch_bounds__(256) void ae_add_kernel(float* __restrict__ a, cons
 
 // ------------------------------------------------------------------ LSTM(64, 64) (cad1:182-188, 236-240)
 // One block per clip: thread j owns gate row j of W_hh (64 registers), h is broadcast from LDS.  torch gate order
-// i, f, g, o; gx = x W_ih^T + b_ih for all frames (one GEMM).  Keeps post-activation gates, c_t and h_{t-1}.
-__global__ __launch_bounds__(256) void ae_lstm_fwd_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
-                                                          const float* __restrict__ bhh, int B, int T,
-                                                          float* __restrict__ gates, float* __restrict__ cs,
-                                                          float* __restrict__ hprev, float* __restrict__ seq,
-                                                          float* __restrict__ seq_out) {
+// i, f, g, o; gx = x W_ih^T + b_ih for all frames (one GEMM).  The clip form (WIN = false) reads row t*B + b of the
+// plan's gx and keeps post-activation gates, c_t and h_{t-1} for BPTT.  The windowed form (WIN = true, eval scoring of
+// a video) reads the frame cache's gx row first + b*stride + t -- one coalesced 1 KB load per step, whose address
+// does not depend on h, so the rows of the next AE_PF steps are fetched into registers ahead of the dependent chain --
+// and stores nothing but the sequence feature.  Both forms run the same floating-point instructions per step.
+constexpr int AE_PF = 4;
+
+template <bool WIN>
+__device__ __forceinline__ void ae_lstm_fwd_body(const float* __restrict__ gx, const float* __restrict__ whh,
+                                                 const float* __restrict__ bhh, int B, int T, int stride,
+                                                 int64_t first, float* __restrict__ gates, float* __restrict__ cs,
+                                                 float* __restrict__ hprev, float* __restrict__ seq,
+                                                 float* __restrict__ seq_out) {
   __shared__ float h[AE_LAT], act[AE_GATES];
   const int b = blockIdx.x, j = threadIdx.x;
   float w[AE_LAT];
@@ -546,29 +563,68 @@ __global__ __launch_bounds__(256) void ae_lstm_fwd_kernel(const float* __restric
   float c = 0.f;
   if (j < AE_LAT) h[j] = 0.f;
   __syncthreads();
-  for (int t = 0; t < T; ++t) {
-    const int64_t n = (int64_t)t * B + b;
+  // one step on the input projection g of row n (n: the clip form's row of the BPTT state)
+  auto step = [&](float g, int64_t n) {
     float acc = bj;
 #pragma unroll
     for (int k = 0; k < AE_LAT; ++k) acc = fmaf(w[k], h[k], acc);
-    const float pre = gx[n * AE_GATES + j] + acc;
+    const float pre = g + acc;
     const float a = (j >= 2 * AE_LAT && j < 3 * AE_LAT) ? tanhf(pre) : 1.f / (1.f + expf(-pre));
     act[j] = a;
-    gates[n * AE_GATES + j] = a;
-    if (j < AE_LAT) hprev[n * AE_LAT + j] = h[j];
+    if constexpr (!WIN) {
+      gates[n * AE_GATES + j] = a;
+      if (j < AE_LAT) hprev[n * AE_LAT + j] = h[j];
+    }
     __syncthreads();
     if (j < AE_LAT) {
       c = act[AE_LAT + j] * c + act[j] * act[2 * AE_LAT + j];
-      cs[n * AE_LAT + j] = c;
+      if constexpr (!WIN) cs[n * AE_LAT + j] = c;
       h[j] = act[3 * AE_LAT + j] * tanhf(c);
     }
     __syncthreads();
+  };
+  if constexpr (WIN) {
+    const float* row = gx + (first + (int64_t)b * stride) * AE_GATES + j;  // frame (w0 + b) * stride + t, t = 0
+    float pf[AE_PF];
+#pragma unroll
+    for (int i = 0; i < AE_PF; ++i) pf[i] = i < T ? row[(int64_t)i * AE_GATES] : 0.f;
+    for (int t0 = 0; t0 < T; t0 += AE_PF) {
+#pragma unroll
+      for (int i = 0; i < AE_PF; ++i) {
+        const int t = t0 + i;
+        if (t < T) {  // (block-uniform)
+          const float g = pf[i];
+          pf[i] = t + AE_PF < T ? row[(int64_t)(t + AE_PF) * AE_GATES] : 0.f;
+          step(g, 0);
+        }
+      }
+    }
+  } else {
+    for (int t = 0; t < T; ++t) {
+      const int64_t n = (int64_t)t * B + b;
+      step(gx[n * AE_GATES + j], n);
+    }
   }
   if (j < AE_LAT) {
     const float v = nan0(h[j]);  // check_and_fix_nan(sequence_feature), cad1:240
-    seq[b * AE_LAT + j] = v;
+    if constexpr (!WIN) seq[b * AE_LAT + j] = v;
     if (seq_out) seq_out[b * AE_LAT + j] = v;
   }
+}
+
+__global__ __launch_bounds__(256) void ae_lstm_fwd_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
+                                                          const float* __restrict__ bhh, int B, int T,
+                                                          float* __restrict__ gates, float* __restrict__ cs,
+                                                          float* __restrict__ hprev, float* __restrict__ seq,
+                                                          float* __restrict__ seq_out) {
+  ae_lstm_fwd_body<false>(gx, whh, bhh, B, T, 0, 0, gates, cs, hprev, seq, seq_out);
+}
+
+// window i of the launch = frames first + i*stride .. + T - 1 of the cache's gx; seq_out [gridDim.x][64]
+__global__ __launch_bounds__(256) void ae_lstm_win_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
+                                                          const float* __restrict__ bhh, int T, int stride,
+                                                          int64_t first, float* __restrict__ seq_out) {
+  ae_lstm_fwd_body<true>(gx, whh, bhh, 0, T, stride, first, nullptr, nullptr, nullptr, nullptr, seq_out);
 }
 
 // BPTT, one block per clip in reverse time: thread (q, k) holds column k of W_hh rows [64q, 64q + 64) for
@@ -675,6 +731,52 @@ __global__ __launch_bounds__(256) void ae_loss_finalize_kernel(const float* __re
     losses[2] = 0.f;
     losses[3] = ok ? 2.f : 0.f;
   }
+}
+
+// The windowed form (eval scoring of a video): one block per (window i of the launch, 256-pixel chunk); the window's
+// one reconstruction r against its T frames first + i*stride + t of the caller's video, NaN -> 0 on both sides, in
+// ae_loss_kernel's order (fmaf(d, d, sq) over t ascending, the same LDS tree).  recon (nullable) [windows][4096]: r
+// once per window.
+__global__ __launch_bounds__(256) void ae_win_loss_kernel(const float* __restrict__ y3,
+                                                          const float* __restrict__ frames, int T, int stride,
+                                                          int64_t first, float* __restrict__ recon,
+                                                          float* __restrict__ part) {
+  __shared__ float red[256];
+  const int b = blockIdx.x / AE_CHUNKS, p = (blockIdx.x % AE_CHUNKS) * 256 + threadIdx.x;
+  const float r0 = 1.f / (1.f + expf(-y3[(int64_t)b * AE_PIX + p]));
+  const float r = r0 != r0 ? 0.f : r0;
+  const float* x = frames + (first + (int64_t)b * stride) * AE_PIX + p;
+  float sq = 0.f;
+  // (the loads of an unrolled group issue before its arithmetic; the adds stay in t order)
+#pragma unroll 4
+  for (int t = 0; t < T; ++t) {
+    const float d = r - nan0(x[(int64_t)t * AE_PIX]);
+    sq = fmaf(d, d, sq);
+  }
+  if (recon) recon[(int64_t)b * AE_PIX + p] = r;
+  red[threadIdx.x] = sq;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+// one thread per window: its chunk partials summed in double (as ae_loss_finalize_kernel), the per-window error and
+// the blend of calculate_anomaly_scores (cad1:548-552)
+__global__ __launch_bounds__(256) void ae_win_finalize_kernel(const float* __restrict__ part, int nw, int T,
+                                                              const float* __restrict__ mem_score,
+                                                              float* __restrict__ recon_err,
+                                                              float* __restrict__ score) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= nw) return;
+  double s = 0.0;
+  for (int c = 0; c < AE_CHUNKS; ++c) s += (double)part[b * AE_CHUNKS + c];
+  const float err = (float)(s / ((double)T * AE_PIX));
+  recon_err[b] = err;
+  // (two rounded products and a rounded sum, as the clip path's tensor expression 0.7 * err + 0.3 * ms: no fma)
+  score[b] = __fadd_rn(__fmul_rn(0.7f, err), __fmul_rn(0.3f, mem_score[b]));
 }
 
 // module backward: d logits = r (1 - r) * sum_t d_recon[b][t] (the T stacked copies); 0 where r was NaN
@@ -937,51 +1039,91 @@ struct AePlanImpl {
     return 0;
   }
 
+  // the per-frame part of the forward on the plan's NF frames: encoder convs + BN + LeakyReLU, Linear + tanh into
+  // lat_dst [NF][64] (and ff), the LSTM input projection into gx_dst [NF][256]; with_dec: the decoder's weight images
+  // go out with the encoder's
+  int encode(const float* x, bool with_dec, const int* skip, float* lat_dst, float* gx_dst, float* ff,
+             hipStream_t st) {
+    const AeLayout& L = ae_layout();
+    bool prep_wait = false;
+    const DenseAct none{};
+    hipLaunchKernelGGL(ae_frames_kernel, grid_for((int64_t)NF * AE_PIX / 4), dim3(256), 0, st, x, B, T, xf, bad);
+    VAD_LAUNCH_CHECK();
+    if (direct) {  // the weight images on the side stream, beside the first layer (waited for before layer 1)
+      hipStream_t ps = st;
+      VAD_TRY(fork(st, &ps));
+      for (int l = 1; l < 4; ++l) VAD_TRY(conv4_prep(P(L.enc_w[l]), ENC_CO[l], ENC_CI[l], ewk[l], ewc[l], ps));
+      if (with_dec)
+        for (int j = 0; j < 3; ++j) VAD_TRY(conv4_prep(P(L.dec_w[j]), DEC_CI[j], DEC_CO[j], dwk[j], dwc[j], ps));
+      if (ps != st) {
+        VAD_HIP(hipEventRecord(ev_join, ps));
+        prep_wait = true;
+      }
+    }
+    for (int l = 0; l < 4; ++l) {
+      const int64_t M = ge[l].rows();
+      if (direct && l == 0) {
+        VAD_TRY(conv4_c1_fwd(xf, NF, AE_HW, AE_HW, P(L.enc_w[0]), P(L.enc_b[0]), ey[0], st));
+      } else if (direct) {
+        if (prep_wait) VAD_HIP(hipStreamWaitEvent(st, ev_join, 0));
+        prep_wait = false;
+        VAD_TRY(conv4_fwd(ea[l - 1], NF, ENC_IN[l], ENC_IN[l], ENC_CI[l], ewk[l], P(L.enc_b[l]), ENC_CO[l], ey[l],
+                          st, scratch, scratch_floats));
+      } else {
+        VAD_TRY(im2col3d(l == 0 ? xf : ea[l - 1], ndhwc_strides(ge[l].in), ge[l], nullptr, nullptr, 0, ecols[l],
+                         st));
+        VAD_TRY(dense_fwd(ecols[l], (int)M, ge[l].K(), P(L.enc_w[l]), P(L.enc_b[l]), ENC_CO[l], ey[l], none,
+                          scratch, scratch_floats, st));
+      }
+      VAD_TRY(bn_fwd(ey[l], enc_bn(l), L.ebn_w[l], L.ebn_b[l], L.erm[l], L.erv[l], 1, skip, est[l], ea[l],
+                     l == 3 ? 16 : 0, st));
+    }
+    VAD_TRY(dense_fwd(ea[3], NF, AE_FLAT, P(L.efc_w), P(L.efc_b), AE_LAT, z, none, scratch, scratch_floats, st));
+    hipLaunchKernelGGL(ae_latent_kernel, grid_for((int64_t)NF * AE_LAT), dim3(256), 0, st, z, B, T, lat_dst, ff);
+    VAD_LAUNCH_CHECK();
+    VAD_TRY(dense_fwd(lat_dst, NF, AE_LAT, P(L.wih), P(L.bih), AE_GATES, gx_dst, none, scratch, scratch_floats, st));
+    return 0;
+  }
+
+  // the decoder on nb <= B sequence features s [nb][64], once per clip: logits of the reconstruction in dy[3]
+  // [nb][4096]; prepped: the weight images are already queued (encode(with_dec))
+  int decode(const float* s, int nb, bool prepped, const int* skip, hipStream_t st) {
+    const AeLayout& L = ae_layout();
+    const DenseAct none{};
+    VAD_TRY(dense_fwd(s, nb, AE_LAT, P(L.dfc_w), P(L.dfc_b), AE_FLAT, u, none, scratch, scratch_floats, st));
+    hipLaunchKernelGGL(ae_dec_in_kernel, grid_for((int64_t)nb * AE_FLAT), dim3(256), 0, st, u, nb, dx[0]);
+    VAD_LAUNCH_CHECK();
+    if (direct && !prepped)
+      for (int j = 0; j < 3; ++j) VAD_TRY(conv4_prep(P(L.dec_w[j]), DEC_CI[j], DEC_CO[j], dwk[j], dwc[j], st));
+    for (int j = 0; j < 4; ++j) {
+      const Conv3dGeom g = nb == B ? gd[j] : ae_geom(nb, DEC_CO[j], 2 * DEC_IN[j], DEC_CI[j]);
+      if (direct && j == 3) {  // ConvTranspose2d(32, 1): 128 MACs per output pixel on the VALU
+        VAD_TRY(conv4_c1_tfwd(dx[3], nb, DEC_IN[3], DEC_IN[3], P(L.dec_w[3]), P(L.dec_b[3]), dy[3], st));
+      } else if (direct) {  // ConvTranspose2d j: four parity-class GEMMs, bias in the epilogue
+        VAD_TRY(conv4_cls(dx[j], nb, DEC_IN[j], DEC_IN[j], DEC_CI[j], dwc[j], P(L.dec_b[j]), DEC_CO[j], dy[j], st,
+                          scratch, scratch_floats));
+      } else {
+        // columns = X_j Wt (the transposed conv's GEMM), col2im + bias
+        VAD_TRY(dense_dgrad(dx[j], (int)g.rows(), DEC_CI[j], P(L.dec_w[j]), g.K(), bcols, nullptr, 1.f, nullptr, st));
+        VAD_TRY(col2im3d(bcols, g, dy[j], st, P(L.dec_b[j])));
+      }
+      if (j < 3)
+        VAD_TRY(bn_fwd(dy[j], gbn(1, g.in.voxels(), DEC_CO[j]), L.dbn_w[j], L.dbn_b[j], L.drm[j], L.drv[j], T, skip,
+                       dst[j], dx[j + 1], 0, st));
+    }
+    return 0;
+  }
+
   int forward(const float* x, const float* seq_in, int stages, float* recon, float* seq_out, float* ff,
               float* scores, float* recon_err, hipStream_t st) {
     const AeLayout& L = ae_layout();
     const bool enc = stages & 1, dec = stages & 2;
     const int* skip = loss_mode == 2 ? bad : nullptr;
-    bool dec_prepped = false, prep_wait = false;
+    const bool dec_prepped = enc && dec && direct;
     const DenseAct none{};
     VAD_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
     if (enc) {
-      hipLaunchKernelGGL(ae_frames_kernel, grid_for((int64_t)NF * AE_PIX / 4), dim3(256), 0, st, x, B, T, xf, bad);
-      VAD_LAUNCH_CHECK();
-      if (direct) {  // the weight images on the side stream, beside the first layer (waited for before layer 1)
-        hipStream_t ps = st;
-        VAD_TRY(fork(st, &ps));
-        for (int l = 1; l < 4; ++l) VAD_TRY(conv4_prep(P(L.enc_w[l]), ENC_CO[l], ENC_CI[l], ewk[l], ewc[l], ps));
-        if (dec)
-          for (int j = 0; j < 3; ++j) VAD_TRY(conv4_prep(P(L.dec_w[j]), DEC_CI[j], DEC_CO[j], dwk[j], dwc[j], ps));
-        dec_prepped = dec;
-        if (ps != st) {
-          VAD_HIP(hipEventRecord(ev_join, ps));
-          prep_wait = true;
-        }
-      }
-      for (int l = 0; l < 4; ++l) {
-        const int64_t M = ge[l].rows();
-        if (direct && l == 0) {
-          VAD_TRY(conv4_c1_fwd(xf, NF, AE_HW, AE_HW, P(L.enc_w[0]), P(L.enc_b[0]), ey[0], st));
-        } else if (direct) {
-          if (prep_wait) VAD_HIP(hipStreamWaitEvent(st, ev_join, 0));
-          prep_wait = false;
-          VAD_TRY(conv4_fwd(ea[l - 1], NF, ENC_IN[l], ENC_IN[l], ENC_CI[l], ewk[l], P(L.enc_b[l]), ENC_CO[l], ey[l],
-                            st, scratch, scratch_floats));
-        } else {
-          VAD_TRY(im2col3d(l == 0 ? xf : ea[l - 1], ndhwc_strides(ge[l].in), ge[l], nullptr, nullptr, 0, ecols[l],
-                           st));
-          VAD_TRY(dense_fwd(ecols[l], (int)M, ge[l].K(), P(L.enc_w[l]), P(L.enc_b[l]), ENC_CO[l], ey[l], none,
-                            scratch, scratch_floats, st));
-        }
-        VAD_TRY(bn_fwd(ey[l], enc_bn(l), L.ebn_w[l], L.ebn_b[l], L.erm[l], L.erv[l], 1, skip, est[l], ea[l],
-                       l == 3 ? 16 : 0, st));
-      }
-      VAD_TRY(dense_fwd(ea[3], NF, AE_FLAT, P(L.efc_w), P(L.efc_b), AE_LAT, z, none, scratch, scratch_floats, st));
-      hipLaunchKernelGGL(ae_latent_kernel, grid_for((int64_t)NF * AE_LAT), dim3(256), 0, st, z, B, T, lat, ff);
-      VAD_LAUNCH_CHECK();
-      VAD_TRY(dense_fwd(lat, NF, AE_LAT, P(L.wih), P(L.bih), AE_GATES, gx, none, scratch, scratch_floats, st));
+      VAD_TRY(encode(x, dec, skip, lat, gx, ff, st));
       hipLaunchKernelGGL(ae_lstm_fwd_kernel, dim3(B), dim3(AE_GATES), 0, st, gx, P(L.whh), P(L.bhh), B, T, gates,
                          cs, hprev, seq, seq_out);
       VAD_LAUNCH_CHECK();
@@ -995,27 +1137,7 @@ struct AePlanImpl {
       VAD_LAUNCH_CHECK();
     }
     if (dec) {
-      VAD_TRY(dense_fwd(seq, B, AE_LAT, P(L.dfc_w), P(L.dfc_b), AE_FLAT, u, none, scratch, scratch_floats, st));
-      hipLaunchKernelGGL(ae_dec_in_kernel, grid_for((int64_t)B * AE_FLAT), dim3(256), 0, st, u, B, dx[0]);
-      VAD_LAUNCH_CHECK();
-      if (direct && !dec_prepped)
-        for (int j = 0; j < 3; ++j) VAD_TRY(conv4_prep(P(L.dec_w[j]), DEC_CI[j], DEC_CO[j], dwk[j], dwc[j], st));
-      for (int j = 0; j < 4; ++j) {
-        if (direct && j == 3) {  // ConvTranspose2d(32, 1): 128 MACs per output pixel on the VALU
-          VAD_TRY(conv4_c1_tfwd(dx[3], B, DEC_IN[3], DEC_IN[3], P(L.dec_w[3]), P(L.dec_b[3]), dy[3], st));
-        } else if (direct) {  // ConvTranspose2d j: four parity-class GEMMs, bias in the epilogue
-          VAD_TRY(conv4_cls(dx[j], B, DEC_IN[j], DEC_IN[j], DEC_CI[j], dwc[j], P(L.dec_b[j]), DEC_CO[j], dy[j], st,
-                            scratch, scratch_floats));
-        } else {
-          // columns = X_j Wt (the transposed conv's GEMM), col2im + bias
-          VAD_TRY(dense_dgrad(dx[j], (int)gd[j].rows(), DEC_CI[j], P(L.dec_w[j]), gd[j].K(), bcols, nullptr, 1.f,
-                              nullptr, st));
-          VAD_TRY(col2im3d(bcols, gd[j], dy[j], st, P(L.dec_b[j])));
-        }
-        if (j < 3)
-          VAD_TRY(bn_fwd(dy[j], dec_bn(j), L.dbn_w[j], L.dbn_b[j], L.drm[j], L.drv[j], T, skip, dst[j], dx[j + 1], 0,
-                         st));
-      }
+      VAD_TRY(decode(seq, B, dec_prepped, skip, st));
       const bool lossy = loss_mode != 0 && enc;
       hipLaunchKernelGGL(ae_loss_kernel, dim3(B * AE_CHUNKS), dim3(256), 0, st, dy[3], lossy ? xf : nullptr, B, T,
                          (float)(2.0 / ((double)B * T * AE_PIX)), recon,
@@ -1034,6 +1156,43 @@ struct AePlanImpl {
       VAD_LAUNCH_CHECK();
     }
     have_fwd = stages == 3;
+    return 0;
+  }
+
+  // Sliding-window scoring, per-frame stage (a (B = F, T = 1) plan: row order t*B + b = frame order): the eval
+  // encoder on F frames, latents and input projections straight into rows f0 .. f0 + F - 1 of the cache
+  int frames_forward(const float* frames_chunk, float* cache, int64_t nframes, int64_t f0, hipStream_t st) {
+    const AeFrameCache C(nframes);
+    training = 0;
+    loss_mode = 0;
+    have_fwd = 0;  // the encoder activations of an earlier forward are gone
+    return encode(frames_chunk, false, nullptr, cache + C.lat + f0 * AE_LAT, cache + C.gx + f0 * AE_GATES, nullptr,
+                  st);
+  }
+
+  // per-window stage for windows w0 .. w0 + nw - 1 (nw <= B): recurrence over the cached rows, ring score, one decoder
+  // call per window, its error against the window's T frames, the blend
+  int windows_forward(const float* cache, const float* frames, int64_t nframes, int T_, int stride, int64_t w0,
+                      int nw, float* seq_out, float* recon_err, float* mem_score, float* score, float* recon,
+                      hipStream_t st) {
+    const AeLayout& L = ae_layout();
+    const AeFrameCache C(nframes);
+    const int64_t first = w0 * stride;
+    training = 0;
+    loss_mode = 0;
+    have_fwd = 0;  // the decoder activations of an earlier forward are gone
+    hipLaunchKernelGGL(ae_lstm_win_kernel, dim3(nw), dim3(AE_GATES), 0, st, cache + C.gx, P(L.whh), P(L.bhh), T_,
+                       stride, first, seq_out);
+    VAD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ae_memory_score_kernel, dim3(nw), dim3(256), 0, st, memory, mptr, seq_out, mem_score);
+    VAD_LAUNCH_CHECK();
+    VAD_TRY(decode(seq_out, nw, false, nullptr, st));
+    hipLaunchKernelGGL(ae_win_loss_kernel, dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3], frames, T_, stride, first,
+                       recon, lpart);
+    VAD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ae_win_finalize_kernel, dim3((unsigned)cdiv(nw, 256)), dim3(256), 0, st, lpart, nw, T_,
+                       mem_score, recon_err, score);
+    VAD_LAUNCH_CHECK();
     return 0;
   }
 
@@ -1258,6 +1417,59 @@ int vad_ae_optimizer_step(vad_ae_plan* plan, float lr, float beta1, float beta2,
   if (plan->user_losses)
     VAD_HIP(hipMemcpyAsync(plan->user_losses, c.losses, 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
   return 0;
+}
+
+int64_t vad_ae_frame_cache_floats(int64_t nframes) {
+  if (nframes < 1 || nframes > (1ll << 40)) {
+    vad::set_error("vad_ae_frame_cache_floats: nframes must be >= 1");
+    return -1;
+  }
+  return AeFrameCache(nframes).total;
+}
+
+int64_t vad_ae_frame_cache_offset(int64_t nframes, int field) {
+  if (nframes < 1 || nframes > (1ll << 40) || field < 0 || field > 1) {
+    vad::set_error("vad_ae_frame_cache_offset: nframes must be >= 1 and field in 0..1");
+    return -1;
+  }
+  const AeFrameCache C(nframes);
+  return field == 0 ? C.lat : C.gx;
+}
+
+int vad_ae_frames_forward(vad_ae_plan* plan, const float* frames_chunk, int64_t nframes, float* cache, int64_t f0,
+                          void* stream) {
+  VAD_CHECK(plan != nullptr, "vad_ae_frames_forward: null plan");
+  AePlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_ae_frames_forward: plan not bound");
+  VAD_CHECK(c.T == 1, "vad_ae_frames_forward: needs a plan created as (B = frames per chunk, T = 1)");
+  VAD_CHECK(frames_chunk && (reinterpret_cast<uintptr_t>(frames_chunk) & 15) == 0,
+            "vad_ae_frames_forward: frames_chunk must be a 16-byte aligned device pointer");
+  VAD_CHECK(cache && (reinterpret_cast<uintptr_t>(cache) & 15) == 0,
+            "vad_ae_frames_forward: cache must be a 16-byte aligned device pointer");
+  VAD_CHECK(nframes >= 1 && nframes <= (1ll << 40), "vad_ae_frames_forward: nframes must be >= 1");
+  VAD_CHECK(f0 >= 0 && f0 + c.B <= nframes,
+            "vad_ae_frames_forward: f0 .. f0 + F - 1 (F = the plan's B) reach outside the nframes of the cache");
+  return c.frames_forward(frames_chunk, cache, nframes, f0, (hipStream_t)stream);
+}
+
+int vad_ae_windows_forward(vad_ae_plan* plan, const float* cache, const float* frames, int64_t nframes, int T,
+                           int stride, int64_t w0, int nw, float* seq, float* recon_err, float* mem_score,
+                           float* score, float* recon, void* stream) {
+  VAD_CHECK(plan != nullptr, "vad_ae_windows_forward: null plan");
+  AePlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_ae_windows_forward: plan not bound");
+  VAD_CHECK(cache && frames && (reinterpret_cast<uintptr_t>(cache) & 15) == 0,
+            "vad_ae_windows_forward: cache (16-byte aligned) and frames must be device pointers");
+  VAD_CHECK(seq && recon_err && mem_score && score && (reinterpret_cast<uintptr_t>(seq) & 15) == 0,
+            "vad_ae_windows_forward: seq (16-byte aligned), recon_err, mem_score and score must not be null");
+  VAD_CHECK(nframes >= 1 && nframes <= (1ll << 40), "vad_ae_windows_forward: nframes must be >= 1");
+  VAD_CHECK(T >= 1 && T <= nframes, "vad_ae_windows_forward: T must be in 1..nframes");
+  VAD_CHECK(stride >= 1, "vad_ae_windows_forward: stride must be >= 1");
+  VAD_CHECK(nw >= 1 && nw <= c.B, "vad_ae_windows_forward: nw must be in 1..B of the plan (its per-clip buffers)");
+  VAD_CHECK(w0 >= 0 && w0 <= (nframes - T) / stride && nw - 1 <= (nframes - T) / stride - w0,
+            "vad_ae_windows_forward: w0 .. w0 + nw - 1 reach outside the video");
+  return c.windows_forward(cache, frames, nframes, T, stride, w0, nw, seq, recon_err, mem_score, score, recon,
+                           (hipStream_t)stream);
 }
 
 int vad_ae_debug_buffer(vad_ae_plan* plan, const char* name, int idx, void** ptr, int64_t* nfloats) {

@@ -416,6 +416,36 @@ int vad_ae_backward(vad_ae_plan* plan, int use_loss, const float* d_recon, const
  * grad_scale multiplies the grads first (1/world after a data-parallel sum) */
 int vad_ae_optimizer_step(vad_ae_plan* plan, float lr, float beta1, float beta2, float eps, float weight_decay,
                           float max_norm, float grad_scale, void* stream);
+/* Sliding-window scoring of a video (eval mode, forward only).  Replaces calculate_anomaly_scores' loop over clips
+ * (cad1:542-552) on the clips the reference enumerates at stride T/4 (cad1:72), which encodes every frame once per
+ * clip that holds it: with running BatchNorm statistics the encoder, Linear + tanh and the LSTM input projection
+ * depend on the frame alone, so they run once per frame into a caller-owned frame cache, and windows then read frames
+ * start + t of the cache.
+ * The cache of a video of nframes frames holds two fields, each [nframes][...] and 64-float aligned: 0 lat [64] (the
+ * frame's latent, tanh and NaN -> 0: frame_features), 1 gx [256] (W_ih lat + b_ih, gate order i, f, g, o).  The
+ * frames themselves are not copied.  vad_ae_frame_cache_floats: its size in floats; vad_ae_frame_cache_offset: a
+ * field's offset in floats (both -1 on a bad argument). */
+int64_t vad_ae_frame_cache_floats(int64_t nframes);
+int64_t vad_ae_frame_cache_offset(int64_t nframes, int field);
+/* The per-frame stage on a plan created as (B = F, T = 1): the eval-mode encoder on the F frames frames_chunk
+ * [F,1,64,64], lat and gx written to frames f0 .. f0 + F - 1 of the cache.  It stops after the gx GEMM: no recurrence,
+ * decoder, loss, counter or ring update.  No parameter or buffer changes; the plan's activations of an earlier
+ * forward do, so a vad_ae_backward of that forward fails ("needs a preceding full forward").  f0 + F > nframes is an
+ * error and launches nothing. */
+int vad_ae_frames_forward(vad_ae_plan* plan, const float* frames_chunk, int64_t nframes, float* cache, int64_t f0,
+                          void* stream);
+/* The per-window stage for windows w0 .. w0 + nw - 1 (window w = frames w*stride .. w*stride + T - 1; nw at most the
+ * plan's B): the LSTM recurrence over the window's cached gx rows, the ring score of its last hidden state
+ * (cad1:262-301), one decoder call (the reference stacks T copies of it, cad1:254-259), the mean over the window's
+ * T*4096 pixels of (r - x)^2 against frames [nframes,1,64,64] (NaN -> 0 on both sides) and the blend 0.7 * error +
+ * 0.3 * ring score (cad1:548-552).  Row i of every output is window w0 + i and equals vad_ae_forward(training = 0,
+ * loss_mode = 1) on that clip.  Outputs: seq [nw,64] (16-byte aligned), recon_err [nw], mem_score [nw], score [nw],
+ * recon [nw,4096] (nullable: one frame per window).  The plan's losses vector is not touched; a pending
+ * vad_ae_backward of the plan fails as above.  T outside 1..nframes, stride < 1, nw outside 1..B or a window range
+ * outside the video is an error and launches nothing. */
+int vad_ae_windows_forward(vad_ae_plan* plan, const float* cache, const float* frames, int64_t nframes, int T,
+                           int stride, int64_t w0, int nw, float* seq, float* recon_err, float* mem_score,
+                           float* score, float* recon, void* stream);
 /* the memory ring of any VideoAutoEncoder: update_memory (cad1:201-219; n <= 500 features (n, 64)) and
  * compute_anomaly_score (cad1:262-301; n sequence features -> scores (n,)) */
 /* test access to the last forward's pre-activations (the gradient tests pin their LeakyReLU decisions): "ey" idx l:
