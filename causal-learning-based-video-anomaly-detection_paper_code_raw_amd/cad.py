@@ -237,3 +237,18 @@ class CausalAnomalyDetector(nn.Module):
         earlier forward raises the "most recent forward only" error."""
         from . import video as _video
         return _video.score_video(self, frames, window, stride, chunk=chunk, seed=seed, step=step, clip0=clip0)
+
+    def open_stream(self, window=16, stride=1, *, max_push=1, seed=0, step=0, clip0=0):
+        """A streaming scorer for a live source (eval mode, fp32; stream.py): ``s.push(frames)`` takes the next
+        1 <= k <= max_push frames, (k, 1, H, W) or (1, k, 1, H, W) on a HIP device, runs their backbone once and
+        returns score_video's dict for exactly the windows they complete -- window w, counted from the start of the
+        stream, covers frames w * stride .. w * stride + window - 1 and equals the eval forward of that clip at clip
+        index clip0 + w; window_starts are absolute, detections list the k pushed frames, and a push that completes
+        no window returns empty tensors.  Memory is a ring of window + max_push - 1 frames, allocated at the first
+        push, whatever the length of the stream.  ``s.frames_seen``, ``s.windows_emitted``, ``s.reset()``.  Raises
+        ValueError, before any device work, in training mode, with set_compute_dtype(torch.bfloat16), for window,
+        stride or max_push that is not an integer >= 1, and at a push for k outside 1..max_push, a channel count
+        other than 1 or a frame size other than the first push's.  Like score_video, a push overwrites the plans'
+        activations: a backward still pending on an earlier forward raises the "most recent forward only" error."""
+        from . import stream as _stream
+        return _stream.CadStream(self, window, stride, max_push=max_push, seed=seed, step=step, clip0=clip0)

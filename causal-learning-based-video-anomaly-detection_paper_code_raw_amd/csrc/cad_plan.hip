@@ -943,22 +943,24 @@ struct CadPlanImpl {
     return 0;
   }
 
-  // The per-frame stage of the eval forward on this plan's NF frames, into frames frame0.. of a frame cache.
-  int frames_forward(const float* x, int64_t nframes, float* cache, int64_t frame0, hipStream_t st) {
+  // The per-frame stage of the eval forward on this plan's NF frames, into frames frame0.. of a frame cache (ring:
+  // into slots (frame0 + f) mod nframes of a ring of nframes slots).
+  int frames_forward(const float* x, int64_t nframes, float* cache, int64_t frame0, bool ring, hipStream_t st) {
     training = 0;
     labels = nullptr;
     have_labels = false;
     VAD_TRY(forward(x, st, true));
-    TIMED("frame_cache", frame_cache_store(head_args(), head_out(), feats, cache, nframes, frame0, st));
+    TIMED("frame_cache", frame_cache_store(head_args(), head_out(), feats, cache, nframes, frame0, st, ring));
     return 0;
   }
 
-  // The per-window stage for windows w0 .. w0 + nw - 1 of a frame cache, nw <= B: the per-clip buffers of this plan
-  // (pooled, the direct classifier's activations, clip_flags) take one row per window.  The outputs go straight to the
-  // caller's arrays; the plan's own result arrays, flags and detector gate stay as the last forward left them.
-  int windows_forward(const float* cache, int64_t nframes, int Tw, int stride, int64_t w0, int nw, float* o_final,
-                      float* o_probs, float* o_causal, float* o_kl, float* o_z, float* o_adj, int* o_nmax,
-                      hipStream_t st) {
+  // The per-window stage for nw <= B windows of a frame cache, window i = frames first + i * stride + t at window
+  // index widx0 + i: the per-clip buffers of this plan (pooled, the direct classifier's activations, clip_flags) take
+  // one row per window.  The outputs go straight to the caller's arrays; the plan's own result arrays, flags and
+  // detector gate stay as the last forward left them.  ring: the cache is a ring of nframes slots.
+  int windows_forward(const float* cache, int64_t nframes, bool ring, int Tw, int stride, int64_t first, int64_t widx0,
+                      int nw, float* o_final, float* o_probs, float* o_causal, float* o_kl, float* o_z, float* o_adj,
+                      int* o_nmax, hipStream_t st) {
     const CadLayout& LY = layout();
     VAD_TRY(join_open_stage2(st));
     training = 0;
@@ -967,7 +969,7 @@ struct CadPlanImpl {
     bwd_state = 0;
     dir_pre = tail_pre = 0;
     const FrameCache C(nframes);
-    TIMED("window_mean", window_mean(cache, nframes, Tw, stride, w0, nw, pooled, st));
+    TIMED("window_mean", window_mean(cache, nframes, Tw, stride, first, nw, pooled, st, ring));
     // direct_classifier on the window means (cad:525-538, 568-570), eval activations, through the forward's launchers
     const int gd[6] = {6144, 512, 256, 128, 64, 2};
     const float* in = pooled;
@@ -989,7 +991,9 @@ struct CadPlanImpl {
     win.counts = reinterpret_cast<const int*>(cache) + C.counts;
     win.slot = reinterpret_cast<const int*>(cache) + C.slot;
     win.stride = stride;
-    win.w0 = w0;
+    win.first = first;
+    win.widx0 = widx0;
+    win.cap = ring ? (int)nframes : 0;
     const HeadOut ho{o_causal, o_kl, o_z, o_adj, nullptr, nullptr, o_nmax, clip_flags};
     TIMED("head_seq_win", head_seq_windows_fwd(a, win, nw, ho, st));
     TailArgs t{};
@@ -1463,7 +1467,19 @@ int vad_cad_frames_forward(vad_cad_plan* plan, const float* x, int64_t nframes, 
             "vad_cad_frames_forward: frame0 .. frame0 + B*T outside the nframes of the cache");
   VAD_CHECK((int64_t)c.NF * c.H * c.W * 4 < (1ll << 31), "vad_cad_frames_forward: x is 2 GB or more");
   VAD_CHECK(FrameCache(nframes).total * 4 < (1ll << 31), "vad_cad_frames_forward: cache is 2 GB or more");
-  return c.frames_forward(x, nframes, cache, frame0, (hipStream_t)stream);
+  return c.frames_forward(x, nframes, cache, frame0, false, (hipStream_t)stream);
+}
+
+int vad_cad_frames_forward_ring(vad_cad_plan* plan, const float* x, int64_t cap, float* cache, int64_t frame0,
+                                void* stream) {
+  VAD_CHECK(plan && x && cache, "vad_cad_frames_forward_ring: null argument");
+  CadPlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_cad_frames_forward_ring: plan not bound");
+  VAD_CHECK(cap >= 1 && c.NF <= cap, "vad_cad_frames_forward_ring: cap must hold the plan's B*T frames");
+  VAD_CHECK(frame0 >= 0, "vad_cad_frames_forward_ring: frame0 must be >= 0");
+  VAD_CHECK((int64_t)c.NF * c.H * c.W * 4 < (1ll << 31), "vad_cad_frames_forward_ring: x is 2 GB or more");
+  VAD_CHECK(FrameCache(cap).total * 4 < (1ll << 31), "vad_cad_frames_forward_ring: cache is 2 GB or more");
+  return c.frames_forward(x, cap, cache, frame0, true, (hipStream_t)stream);
 }
 
 int vad_cad_windows_forward(vad_cad_plan* plan, const float* cache, int64_t nframes, int T, int stride, int64_t w0,
@@ -1484,8 +1500,33 @@ int vad_cad_windows_forward(vad_cad_plan* plan, const float* cache, int64_t nfra
   c.seed = seed;
   c.step = step;
   c.clip0 = clip0;
-  return c.windows_forward(cache, nframes, T, stride, w0, nw, final_scores, probs, causal, kl, z, adj, nmax,
-                           (hipStream_t)stream);
+  return c.windows_forward(cache, nframes, false, T, stride, w0 * stride, w0, nw, final_scores, probs, causal, kl, z,
+                           adj, nmax, (hipStream_t)stream);
+}
+
+int vad_cad_windows_forward_ring(vad_cad_plan* plan, const float* cache, int64_t cap, int T, int stride,
+                                 int64_t first_frame, int64_t widx0, int nw, uint64_t seed, uint64_t step,
+                                 int64_t clip0, float* final_scores, float* probs, float* causal, float* kl, float* z,
+                                 float* adj, int32_t* nmax, void* stream) {
+  VAD_CHECK(plan && cache, "vad_cad_windows_forward_ring: null plan or cache");
+  VAD_CHECK(final_scores && probs && causal && kl && z && adj && nmax, "vad_cad_windows_forward_ring: null output");
+  CadPlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_cad_windows_forward_ring: plan not bound");
+  VAD_CHECK(cap >= 1, "vad_cad_windows_forward_ring: cap must be >= 1");
+  VAD_CHECK(T >= 1 && T <= cap, "vad_cad_windows_forward_ring: T must be in 1..cap");
+  VAD_CHECK(T <= 4096, "vad_cad_windows_forward_ring: T too large (head: at most 4096 steps)");
+  VAD_CHECK(stride >= 1, "vad_cad_windows_forward_ring: stride must be >= 1");
+  VAD_CHECK(first_frame >= 0 && widx0 >= 0, "vad_cad_windows_forward_ring: first_frame and widx0 must be >= 0");
+  VAD_CHECK(nw >= 1 && nw <= c.B,
+            "vad_cad_windows_forward_ring: nw must be in 1..the plan's B (one per-clip scratch row per window)");
+  VAD_CHECK((int64_t)(nw - 1) * stride + T <= cap,
+            "vad_cad_windows_forward_ring: the span (nw - 1) * stride + T of the batch exceeds cap");
+  VAD_CHECK(FrameCache(cap).total * 4 < (1ll << 31), "vad_cad_windows_forward_ring: cache is 2 GB or more");
+  c.seed = seed;
+  c.step = step;
+  c.clip0 = clip0;
+  return c.windows_forward(cache, cap, true, T, stride, first_frame, widx0, nw, final_scores, probs, causal, kl, z,
+                           adj, nmax, (hipStream_t)stream);
 }
 
 int vad_cad_backward(vad_cad_plan* plan, int use_loss, const float* d_final, const float* d_probs,

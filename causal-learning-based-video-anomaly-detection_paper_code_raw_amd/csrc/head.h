@@ -87,23 +87,28 @@ struct FrameCache {
     total = o;
   }
 };
+// The same layout serves as a ring of N slots for a stream of frames (ring = true below): frame g, counted from the
+// start of the stream, lives in slot g mod N.  Which frames are resident is the caller's bookkeeping.
 // copies the B*T frames head_rows_fwd just processed (a.rows / a.iws, o.boxes / o.counts) and their pooled features
-// to frames frame0.. of the cache
+// to frames frame0.. of the cache (ring: to slots (frame0 + f) mod nframes; the chunk may straddle the wrap)
 int frame_cache_store(const HeadArgs& a, const HeadOut& o, const float* feats, float* cache, int64_t nframes,
-                      int64_t frame0, hipStream_t st);
-// pooled[i][k] = (sum_{t < T} feats[(w0 + i) * stride + t][k]) / T for i < nw, summed in ascending t from 0 as
-// avgpool_fwd forms a clip's mean
-int window_mean(const float* cache, int64_t nframes, int T, int stride, int64_t w0, int nw, float* pooled,
-                hipStream_t st);
-// head_seq_fwd on windows of the cache, forward only: block i runs window w0 + i (frames (w0 + i) * stride + t) with
-// the RNG key of clip a.clip0 + w0 + i and writes row i of o.causal / kl / z / adj / nmax / clip_flags; a.T is the
-// window length; a.rows / a.ws / a.iws are not used (no backward state is kept)
+                      int64_t frame0, hipStream_t st, bool ring = false);
+// pooled[i][k] = (sum_{t < T} feats[first + i * stride + t][k]) / T for i < nw, summed in ascending t from 0 as
+// avgpool_fwd forms a clip's mean (ring: row t is slot (first + i * stride + t) mod nframes, the same sum)
+int window_mean(const float* cache, int64_t nframes, int T, int stride, int64_t first, int nw, float* pooled,
+                hipStream_t st, bool ring = false);
+// head_seq_fwd on windows of the cache, forward only: block i runs the window of frames first + i * stride + t with
+// the RNG key of clip a.clip0 + widx0 + i and writes row i of o.causal / kl / z / adj / nmax / clip_flags; a.T is the
+// window length; a.rows / a.ws / a.iws are not used (no backward state is kept).  cap = 0: the cache is linear;
+// cap > 0: a ring of cap >= a.T slots, frame g in slot g mod cap.
 struct SeqWindows {
   const float* gi;    // FrameCache::gi
   const int* counts;  // FrameCache::counts
   const int* slot;    // FrameCache::slot
   int stride;
-  int64_t w0;
+  int64_t first;      // the first frame of window 0
+  int64_t widx0;      // the index of window 0 (RNG key)
+  int cap;
 };
 int head_seq_windows_fwd(const HeadArgs& a, const SeqWindows& win, int nw, const HeadOut& o, hipStream_t st);
 

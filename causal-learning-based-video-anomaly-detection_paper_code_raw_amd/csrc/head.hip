@@ -386,11 +386,16 @@ __global__ __launch_bounds__(256) void head_rows_fwd_kernel(HeadArgs a, const fl
 // The per-clip sequence forward, for two callers.  WIN = false (head_seq_fwd_kernel): block b runs clip b of the batch
 // -- frames b*T + t of a.rows / a.iws -- and keeps the recurrence's state (r, z, n, W_hn h, h_prev rows) and its
 // small activations for the backward.  WIN = true (head_seq_win_kernel, sliding-window scoring): block b runs window
-// win.w0 + b of a frame cache -- frames (win.w0 + b) * win.stride + t -- with the RNG key of clip a.clip0 + win.w0 + b,
-// forward only: none of the backward state is stored (most of the clip kernel's memory traffic).  Every difference is
-// an `if constexpr`, so the clip kernel's arithmetic and its order are those of the untemplated kernel.
-template <bool WIN>
+// b of a batch of windows of a frame cache -- frames win.first + b * win.stride + t -- with the RNG key of clip
+// a.clip0 + win.widx0 + b, forward only: none of the backward state is stored (most of the clip kernel's memory
+// traffic).  RING (head_seq_ring_kernel, with WIN): the cache is a ring of win.cap >= T slots and frame g lives in slot
+// g mod cap; the window's first slot is reduced once per block, step t then reads slot s0 + t less cap where it passes
+// the end (s0 + t < 2 cap) -- an add, a compare and a select on wave-uniform values, no division in the recurrence.
+// Every difference is an `if constexpr`, so the clip kernel's and the linear window kernel's arithmetic and its order
+// are those of the untemplated kernel.
+template <bool WIN, bool RING = false>
 __device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWindows win) {
+  static_assert(WIN || !RING, "the ring form addresses a frame cache");
   const int b = blockIdx.x, T = a.T, tid = threadIdx.x;
   const HL L;
   const RowLayout RL((int64_t)a.B * T * NMAX);
@@ -399,13 +404,27 @@ __device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWind
   const int* iw = a.iws + (int64_t)b * a.iws_stride;
   const int* cnt = iw;
   const int* slot = iw + T;
-  const float* gi_win = nullptr;  // WIN: the projections of the window's first frame
+  const float* gi_win = nullptr;  // WIN: the projections of the window's first frame (RING: of slot 0)
+  int s0 = 0;                     // RING: the slot of the window's first frame
+  // frame t of the window: row t of cnt / slot / gi_win, or with RING row fr(t)
+  auto fr = [&](int t) {
+    if constexpr (RING) {
+      const int s = s0 + t;
+      return s >= win.cap ? s - win.cap : s;
+    } else {
+      return t;
+    }
+  };
   if constexpr (WIN) {
-    const int64_t f0 = (win.w0 + b) * win.stride;
+    int64_t f0 = win.first + (int64_t)b * win.stride;
+    if constexpr (RING) {
+      s0 = (int)(f0 % win.cap);
+      f0 = 0;
+    }
     cnt = win.counts + f0;
     slot = win.slot + f0 * NMAX;
     gi_win = win.gi + f0 * NMAX * G3;
-    a.clip0 += win.w0;  // the RNG key of block b: clip a.clip0 + b
+    a.clip0 += win.widx0;  // the RNG key of block b: clip a.clip0 + b
   }
   __shared__ __attribute__((aligned(16))) float big[HF_BIG];  // W_hh during the recurrence, then the MLP weights
   __shared__ __attribute__((aligned(16))) float sw[HL_TOTAL];
@@ -422,8 +441,8 @@ __device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWind
   if (tid == 0) {
     int N = 1, any = 0;
     for (int t = 0; t < T; ++t) {
-      N = max(N, cnt[t]);
-      if (slot[t * NMAX] >= 0) any = 1;
+      N = max(N, cnt[fr(t)]);
+      if (slot[fr(t) * NMAX] >= 0) any = 1;
     }
     s_N = N;
     s_any = any;
@@ -467,7 +486,7 @@ __device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWind
           g[k][0] = g[k][1] = g[k][2] = 0.f;
           if (t0 + k < T) {
             const float* gi;
-            if constexpr (WIN) gi = gi_win + ((int64_t)(t0 + k) * NMAX + nn) * G3;
+            if constexpr (WIN) gi = gi_win + ((int64_t)fr(t0 + k) * NMAX + nn) * G3;
             else gi = rows + RL.gi + (((int64_t)b * T + t0 + k) * NMAX + nn) * G3;
             g[k][0] = gi[u]; g[k][1] = gi[GH + u]; g[k][2] = gi[2 * GH + u];
           }
@@ -667,6 +686,9 @@ __global__ __launch_bounds__(HT) void head_seq_fwd_kernel(HeadArgs a, HeadOut o)
 __global__ __launch_bounds__(HT) void head_seq_win_kernel(HeadArgs a, HeadOut o, SeqWindows win) {
   head_seq_fwd_body<true>(a, o, win);
 }
+__global__ __launch_bounds__(HT) void head_seq_ring_kernel(HeadArgs a, HeadOut o, SeqWindows win) {
+  head_seq_fwd_body<true, true>(a, o, win);
+}
 
 int head_rows_fwd(const HeadArgs& a, const float* det_logits, const HeadOut& o, hipStream_t st) {
   VAD_CHECK(a.T <= 4096, "head: T too large");
@@ -680,8 +702,12 @@ int head_seq_fwd(const HeadArgs& a, const HeadOut& o, hipStream_t st) {
   return 0;
 }
 int head_seq_windows_fwd(const HeadArgs& a, const SeqWindows& win, int nw, const HeadOut& o, hipStream_t st) {
-  VAD_CHECK(a.T >= 1 && a.T <= 4096 && win.stride >= 1 && win.w0 >= 0 && nw >= 1, "head: bad window arguments");
-  VAD_KLAUNCH(head_seq_win_kernel, dim3(nw), dim3(HT), 0, st, a, o, win);
+  VAD_CHECK(a.T >= 1 && a.T <= 4096 && win.stride >= 1 && win.first >= 0 && nw >= 1, "head: bad window arguments");
+  // (a ring holds the batch's whole span, so no slot stands for two frames of it)
+  VAD_CHECK(win.cap == 0 || (win.cap >= a.T && (int64_t)(nw - 1) * win.stride + a.T <= win.cap),
+            "head: the windows do not fit the ring");
+  if (win.cap > 0) VAD_KLAUNCH(head_seq_ring_kernel, dim3(nw), dim3(HT), 0, st, a, o, win);
+  else VAD_KLAUNCH(head_seq_win_kernel, dim3(nw), dim3(HT), 0, st, a, o, win);
   VAD_LAUNCH_CHECK();
   return 0;
 }

@@ -2,7 +2,9 @@
 // vad_cad_windows_forward).  With running BatchNorm statistics everything up to the GRU input projection depends on the
 // frame alone, so the per-frame stage of the forward runs once per frame and leaves its results in a frame cache; a
 // window then reads frames start + t of the cache.  This file: the cache's store kernel and the per-window mean of
-// the pooled features; the windowed sequence kernel shares its body with the clip kernel (head.hip).
+// the pooled features; the windowed sequence kernel shares its body with the clip kernel (head.hip).  For a live
+// stream (vad_cad_frames_forward_ring / vad_cad_windows_forward_ring) the same cache is a ring: frame g, counted from
+// the start of the stream, lives in slot g mod nframes, and both kernels here have a RING form beside the linear one.
 #include "../../include/vad.h"
 #include "head.h"
 
@@ -13,7 +15,9 @@ constexpr int G3V = 3 * GH;
 static_assert(FEAT % 4 == 0 && (NMAX * G3V) % 4 == 0 && (NMAX * 4) % 4 == 0, "float4 copies");
 
 // One block per frame f = b*T + t of the chunk: its features, its five projection rows and its boxes as float4s, its
-// count and slots as words, to frame frame0 + f of the cache.
+// count and slots as words, to frame frame0 + f of the cache.  RING: to slot (frame0 + f) mod nframes, with
+// frame0 < nframes already reduced on the host and at most nframes frames in the chunk, so one conditional subtract.
+template <bool RING>
 __global__ __launch_bounds__(256) void frame_cache_store_kernel(const float* __restrict__ feats,
                                                                 const float* __restrict__ gi,
                                                                 const float* __restrict__ boxes,
@@ -24,7 +28,10 @@ __global__ __launch_bounds__(256) void frame_cache_store_kernel(const float* __r
   const int f = blockIdx.x, tid = threadIdx.x;
   const int b = f / T, t = f - b * T;
   const FrameCache C(nframes);
-  const int64_t g = frame0 + f;
+  int64_t g = frame0 + f;
+  if constexpr (RING) {
+    if (g >= nframes) g -= nframes;
+  }
   const f32x4* sf = reinterpret_cast<const f32x4*>(feats + (int64_t)f * FEAT);
   f32x4* df = reinterpret_cast<f32x4*>(cache + C.feats + g * FEAT);
   // (6 loads in flight per thread before the first store)
@@ -49,39 +56,61 @@ __global__ __launch_bounds__(256) void frame_cache_store_kernel(const float* __r
 static_assert(FEAT / 4 % 256 == 0 && NMAX * G3V / 4 <= 256, "frame_cache_store_kernel: thread roles");
 
 int frame_cache_store(const HeadArgs& a, const HeadOut& o, const float* feats, float* cache, int64_t nframes,
-                      int64_t frame0, hipStream_t st) {
+                      int64_t frame0, hipStream_t st, bool ring) {
   const int64_t nf = (int64_t)a.B * a.T;
-  VAD_CHECK(frame0 >= 0 && frame0 + nf <= nframes, "frame cache: frames outside the cache");
+  VAD_CHECK(nframes >= 1 && frame0 >= 0 && (ring ? nf <= nframes : frame0 + nf <= nframes),
+            "frame cache: frames outside the cache");
   VAD_CHECK((reinterpret_cast<uintptr_t>(cache) & 15) == 0, "frame cache: the cache must be 16-B aligned");
-  VAD_KLAUNCH(frame_cache_store_kernel, dim3((unsigned)nf), dim3(256), 0, st, feats,
-              a.rows + head_rows_gi_offset(a.B, a.T), o.boxes, o.counts, a.iws, a.iws_stride, a.T, cache, nframes,
-              frame0);
+  const float* gi = a.rows + head_rows_gi_offset(a.B, a.T);
+  if (ring)
+    VAD_KLAUNCH(frame_cache_store_kernel<true>, dim3((unsigned)nf), dim3(256), 0, st, feats, gi, o.boxes, o.counts,
+                a.iws, a.iws_stride, a.T, cache, nframes, frame0 % nframes);
+  else
+    VAD_KLAUNCH(frame_cache_store_kernel<false>, dim3((unsigned)nf), dim3(256), 0, st, feats, gi, o.boxes, o.counts,
+                a.iws, a.iws_stride, a.T, cache, nframes, frame0);
   VAD_LAUNCH_CHECK();
   return 0;
 }
 
-// pooled[i][k] of window w0 + i: thread = one float4 of columns, the window's T frames summed in ascending t from
-// 0.f and divided by T -- the sum avgpool_fwd_kernel forms for a clip (pool += f; pool / T), so the direct
-// classifier reads the number the clip path gives it.  A warp's loads are 1 KB contiguous; the loop is unrolled so
-// several frames' loads are in flight per thread (the adds stay in order).
+// pooled[i][k] of window i (frames first + i * stride + t): thread = one float4 of columns, the window's T frames
+// summed in ascending t from 0.f and divided by T -- the sum avgpool_fwd_kernel forms for a clip (pool += f;
+// pool / T), so the direct classifier reads the number the clip path gives it.  A warp's loads are 1 KB contiguous;
+// the loop is unrolled so several frames' loads are in flight per thread (the adds stay in order).  RING: row t is
+// slot (first + i * stride + t) mod nframes -- one modulo per thread, then increment and wrap -- and the sum is
+// the same one.
+template <bool RING>
 __global__ __launch_bounds__(256) void window_mean_kernel(const float* __restrict__ cache, int64_t nframes, int T,
-                                                          int stride, int64_t w0, float* __restrict__ pooled) {
+                                                          int stride, int64_t first, float* __restrict__ pooled) {
   const int i = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;  // c < FEAT / 4 (the grid covers it exactly)
   const FrameCache C(nframes);
-  const f32x4* src = reinterpret_cast<const f32x4*>(cache + C.feats + (w0 + i) * stride * FEAT) + c;
   f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (RING) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(cache + C.feats) + c;
+    const int cap = (int)nframes;
+    int sl = (int)((first + (int64_t)i * stride) % nframes);
 #pragma unroll 8
-  for (int t = 0; t < T; ++t) s += src[(int64_t)t * (FEAT / 4)];
+    for (int t = 0; t < T; ++t) {
+      s += src[(int64_t)sl * (FEAT / 4)];
+      if (++sl == cap) sl = 0;
+    }
+  } else {
+    const f32x4* src = reinterpret_cast<const f32x4*>(cache + C.feats + (first + (int64_t)i * stride) * FEAT) + c;
+#pragma unroll 8
+    for (int t = 0; t < T; ++t) s += src[(int64_t)t * (FEAT / 4)];
+  }
   const float fT = (float)T;
   reinterpret_cast<f32x4*>(pooled + (int64_t)i * FEAT)[c] = f32x4{s[0] / fT, s[1] / fT, s[2] / fT, s[3] / fT};
 }
 
-int window_mean(const float* cache, int64_t nframes, int T, int stride, int64_t w0, int nw, float* pooled,
-                hipStream_t st) {
-  VAD_CHECK(T >= 1 && stride >= 1 && w0 >= 0 && nw >= 1 && (w0 + nw - 1) * stride + T <= nframes,
+int window_mean(const float* cache, int64_t nframes, int T, int stride, int64_t first, int nw, float* pooled,
+                hipStream_t st, bool ring) {
+  // (ring: the batch's span fits the ring, so no slot is read as two different frames)
+  VAD_CHECK(T >= 1 && stride >= 1 && first >= 0 && nw >= 1 &&
+                (ring ? 0 : first) + (int64_t)(nw - 1) * stride + T <= nframes && nframes < (1ll << 31),
             "window_mean: windows outside the cache");
-  VAD_KLAUNCH(window_mean_kernel, dim3(FEAT / 4 / 256, (unsigned)nw), dim3(256), 0, st, cache, nframes, T, stride, w0,
-              pooled);
+  const dim3 grid(FEAT / 4 / 256, (unsigned)nw);
+  if (ring) VAD_KLAUNCH(window_mean_kernel<true>, grid, dim3(256), 0, st, cache, nframes, T, stride, first, pooled);
+  else VAD_KLAUNCH(window_mean_kernel<false>, grid, dim3(256), 0, st, cache, nframes, T, stride, first, pooled);
   VAD_LAUNCH_CHECK();
   return 0;
 }

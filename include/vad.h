@@ -155,6 +155,24 @@ int vad_cad_frames_forward(vad_cad_plan* plan, const float* x, int64_t nframes, 
 int vad_cad_windows_forward(vad_cad_plan* plan, const float* cache, int64_t nframes, int T, int stride, int64_t w0,
                             int nw, uint64_t seed, uint64_t step, int64_t clip0, float* final_scores, float* probs,
                             float* causal, float* kl, float* z, float* adj, int32_t* nmax, void* stream);
+/* The same two stages on a live stream of frames, with the cache used as a ring: a cache of cap slots (the layout
+ * vad_cad_frame_cache_floats(cap) / vad_cad_frame_cache_offset(cap, field) describe) in which frame g, counted from
+ * the start of the stream, lives in slot g mod cap.  The library keeps no record of which frames a ring holds: that
+ * is the caller's bookkeeping -- a frame is resident from its vad_cad_frames_forward_ring until a later one stores
+ * frame g + cap over it, and a window must be scored while all its frames are.
+ * vad_cad_frames_forward_ring: vad_cad_frames_forward on the plan's B*T frames, stored as frames frame0 .. frame0 +
+ * B*T - 1 of the ring (the chunk may straddle the wrap).  B*T > cap or frame0 < 0 is an error and launches nothing. */
+int vad_cad_frames_forward_ring(vad_cad_plan* plan, const float* x, int64_t cap, float* cache, int64_t frame0,
+                                void* stream);
+/* vad_cad_windows_forward for nw windows of the ring: window i < nw covers frames first_frame + i*stride + t, t < T,
+ * and row i of every output equals vad_cad_forward(training = 0) on that clip at clip index clip0 + widx0 + i (widx0:
+ * the index of the batch's first window since the start of the stream).  The batch must fit the ring: T outside
+ * 1..cap, stride < 1, nw outside 1..the plan's B, or a span (nw - 1)*stride + T > cap is an error, names the argument
+ * in vad_last_error and launches nothing. */
+int vad_cad_windows_forward_ring(vad_cad_plan* plan, const float* cache, int64_t cap, int T, int stride,
+                                 int64_t first_frame, int64_t widx0, int nw, uint64_t seed, uint64_t step,
+                                 int64_t clip0, float* final_scores, float* probs, float* causal, float* kl, float* z,
+                                 float* adj, int32_t* nmax, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Single building blocks (kernel unit tests; same kernels as the fused step)
