@@ -141,6 +141,15 @@ class VideoAutoEncoder(nn.Module):
         from .ae_video import score_video
         return score_video(self, frames, window, stride, chunk=chunk, return_reconstructions=return_reconstructions)
 
+    def open_stream(self, window=16, stride=1, *, max_push=1, return_reconstructions=False):
+        """Eval-mode scoring of a live stream (ae_stream.py): ``s = model.open_stream(...)``, then ``s.push(frames)``
+        with the next 1 <= k <= max_push frames (k, 1, 64, 64) or (1, k, 1, 64, 64) returns score_video's keys for
+        exactly the windows those frames complete ('window_starts' absolute from the stream's first frame,
+        'frame_features' (k, 64) of the pushed frames), equal to score_video on the same frames in any chunking of
+        the pushes.  Memory is a ring of window + max_push - 1 frames.  Changes nothing in the model."""
+        from .ae_stream import AeStream
+        return AeStream(self, window, stride, max_push=max_push, return_reconstructions=return_reconstructions)
+
     def forward(self, frames):
         x = _clip_input(frames)
         e = self.engine()

@@ -30,7 +30,8 @@
 //   scoring   a whole video in sliding windows, eval mode (vad_ae_frames_forward / vad_ae_windows_forward): the
 //             encoder and the LSTM input projection once per frame into a frame cache, then per window the
 //             recurrence over cached rows (the LSTM kernel's WIN instantiation), ring score, one decoder call and
-//             the error against the window's T frames
+//             the error against the window's T frames; a live stream keeps the per-frame results and the frames in a
+//             ring of cap slots (vad_ae_frames_forward_ring / vad_ae_windows_forward_ring), frame g in slot g mod cap
 // Status word (losses[3]): 0 = skipped before backward (train-loop mode: a non-finite input, cad1:385-387 -- the BN
 // running stats, counters and the memory ring stay untouched, as the reference's `continue` before the forward -- or
 // a non-finite loss), 1 = non-finite grads, no step, 2 = stepped.
@@ -68,6 +69,15 @@ struct AeFrameCache {
   int64_t lat, gx, total;  // offsets in floats: lat [N][64] (tanh latents), gx [N][256] (W_ih lat + b_ih)
   explicit AeFrameCache(int64_t n) : lat(0), gx(n * AE_LAT), total(n * (AE_LAT + AE_GATES)) {}
 };
+
+// Ring of a live stream (include/vad.h): the same two arrays and the frames themselves (NaN -> 0: the plan's xf) over
+// cap slots, each 64-float aligned; frame g of the stream lives in slot g mod cap
+struct AeRing {
+  int64_t lat, gx, pix, total;  // offsets in floats: lat [cap][64], gx [cap][256], pix [cap][4096]
+  explicit AeRing(int64_t cap)
+      : lat(0), gx(cap * AE_LAT), pix(cap * (AE_LAT + AE_GATES)), total(cap * (AE_LAT + AE_GATES + AE_PIX)) {}
+};
+constexpr int64_t AE_RING_MAX = 1ll << 24;  // slots: slot arithmetic in the kernels stays in int
 
 // model.named_parameters() and BN running-stat order (cad1:129-188)
 struct AeLayout : FlatLayout {
@@ -155,6 +165,29 @@ __global__ __launch_bounds__(256) void ae_frames_kernel(const float* __restrict_
     *reinterpret_cast<f32x4*>(xf + ((int64_t)t * B + b) * AE_PIX + p) = v;
   }
   if (nonfin) atomicOr(bad, 1);
+}
+
+// Ring store of a (B = k, T = 1) plan's per-frame results: block f copies row f of lat [k][64], gx [k][256] and xf
+// [k][4096] to slot s0 + f of the ring's arrays, less cap once if it passes the end (s0 = f0 mod cap, reduced on the
+// host; k <= cap), so a chunk may straddle the wrap.  float4 copies, no division.
+__global__ __launch_bounds__(256) void ae_ring_store_kernel(const float* __restrict__ lat,
+                                                            const float* __restrict__ gx,
+                                                            const float* __restrict__ xf, int s0, int cap,
+                                                            float* __restrict__ rlat, float* __restrict__ rgx,
+                                                            float* __restrict__ rpix) {
+  const int f = blockIdx.x, t = threadIdx.x;
+  int slot = s0 + f;
+  if (slot >= cap) slot -= cap;
+  if (t < AE_LAT / 4)
+    reinterpret_cast<f32x4*>(rlat + (int64_t)slot * AE_LAT)[t] =
+        reinterpret_cast<const f32x4*>(lat + (int64_t)f * AE_LAT)[t];
+  if (t < AE_GATES / 4)
+    reinterpret_cast<f32x4*>(rgx + (int64_t)slot * AE_GATES)[t] =
+        reinterpret_cast<const f32x4*>(gx + (int64_t)f * AE_GATES)[t];
+  const f32x4* src = reinterpret_cast<const f32x4*>(xf + (int64_t)f * AE_PIX);
+  f32x4* dst = reinterpret_cast<f32x4*>(rpix + (int64_t)slot * AE_PIX);
+#pragma unroll
+  for (int i = 0; i < AE_PIX / 4 / 256; ++i) dst[i * 256 + t] = src[i * 256 + t];
 }
 
 // ------------------------------------------------------------------ grouped train-mode BatchNorm + LeakyReLU(0.1)
@@ -539,15 +572,20 @@ __global__ __launch_bounds__(256) void ae_add_kernel(float* __restrict__ a, cons
 // plan's gx and keeps post-activation gates, c_t and h_{t-1} for BPTT.  The windowed form (WIN = true, eval scoring of
 // a video) reads the frame cache's gx row first + b*stride + t -- one coalesced 1 KB load per step, whose address
 // does not depend on h, so the rows of the next AE_PF steps are fetched into registers ahead of the dependent chain --
-// and stores nothing but the sequence feature.  Both forms run the same floating-point instructions per step.
+// and stores nothing but the sequence feature.  The ring form (WIN and RING, a live stream) reads the gx array of a
+// ring of cap slots: the block reduces its first slot s0 = (first + b*stride) mod cap once (first: already mod cap),
+// and the row of step t -- the look-ahead row t + AE_PF of the prefetch too -- is s0 + t, less cap where it reaches
+// it (T <= cap: one block-uniform conditional subtract, no division in the recurrence).  All forms run the same
+// floating-point instructions per step.
 constexpr int AE_PF = 4;
 
-template <bool WIN>
+template <bool WIN, bool RING = false>
 __device__ __forceinline__ void ae_lstm_fwd_body(const float* __restrict__ gx, const float* __restrict__ whh,
                                                  const float* __restrict__ bhh, int B, int T, int stride,
-                                                 int64_t first, float* __restrict__ gates, float* __restrict__ cs,
-                                                 float* __restrict__ hprev, float* __restrict__ seq,
-                                                 float* __restrict__ seq_out) {
+                                                 int64_t first, int cap, float* __restrict__ gates,
+                                                 float* __restrict__ cs, float* __restrict__ hprev,
+                                                 float* __restrict__ seq, float* __restrict__ seq_out) {
+  static_assert(WIN || !RING, "the ring form is a windowed form");
   __shared__ float h[AE_LAT], act[AE_GATES];
   const int b = blockIdx.x, j = threadIdx.x;
   float w[AE_LAT];
@@ -584,17 +622,34 @@ __device__ __forceinline__ void ae_lstm_fwd_body(const float* __restrict__ gx, c
     __syncthreads();
   };
   if constexpr (WIN) {
-    const float* row = gx + (first + (int64_t)b * stride) * AE_GATES + j;  // frame (w0 + b) * stride + t, t = 0
+    // the input projection of step t: frame (w0 + b) * stride + t of the cache, or its slot of the ring
+    const float* row;
+    int s0 = 0;
+    if constexpr (RING) {
+      row = gx + j;
+      s0 = (int)(((unsigned)first + (unsigned)b * (unsigned)stride) % (unsigned)cap);
+    } else {
+      row = gx + (first + (int64_t)b * stride) * AE_GATES + j;
+    }
+    auto gx_at = [&](int t) -> float {
+      if constexpr (RING) {
+        int r = s0 + t;
+        if (r >= cap) r -= cap;  // (block-uniform)
+        return row[(int64_t)r * AE_GATES];
+      } else {
+        return row[(int64_t)t * AE_GATES];
+      }
+    };
     float pf[AE_PF];
 #pragma unroll
-    for (int i = 0; i < AE_PF; ++i) pf[i] = i < T ? row[(int64_t)i * AE_GATES] : 0.f;
+    for (int i = 0; i < AE_PF; ++i) pf[i] = i < T ? gx_at(i) : 0.f;
     for (int t0 = 0; t0 < T; t0 += AE_PF) {
 #pragma unroll
       for (int i = 0; i < AE_PF; ++i) {
         const int t = t0 + i;
         if (t < T) {  // (block-uniform)
           const float g = pf[i];
-          pf[i] = t + AE_PF < T ? row[(int64_t)(t + AE_PF) * AE_GATES] : 0.f;
+          pf[i] = t + AE_PF < T ? gx_at(t + AE_PF) : 0.f;
           step(g, 0);
         }
       }
@@ -617,14 +672,22 @@ __global__ __launch_bounds__(256) void ae_lstm_fwd_kernel(const float* __restric
                                                           float* __restrict__ gates, float* __restrict__ cs,
                                                           float* __restrict__ hprev, float* __restrict__ seq,
                                                           float* __restrict__ seq_out) {
-  ae_lstm_fwd_body<false>(gx, whh, bhh, B, T, 0, 0, gates, cs, hprev, seq, seq_out);
+  ae_lstm_fwd_body<false>(gx, whh, bhh, B, T, 0, 0, 0, gates, cs, hprev, seq, seq_out);
 }
 
 // window i of the launch = frames first + i*stride .. + T - 1 of the cache's gx; seq_out [gridDim.x][64]
 __global__ __launch_bounds__(256) void ae_lstm_win_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
                                                           const float* __restrict__ bhh, int T, int stride,
                                                           int64_t first, float* __restrict__ seq_out) {
-  ae_lstm_fwd_body<true>(gx, whh, bhh, 0, T, stride, first, nullptr, nullptr, nullptr, nullptr, seq_out);
+  ae_lstm_fwd_body<true>(gx, whh, bhh, 0, T, stride, first, 0, nullptr, nullptr, nullptr, nullptr, seq_out);
+}
+
+// window i of the launch = frames first + i*stride .. + T - 1 of a ring of cap slots (gx: the ring's gx array; first
+// already reduced mod cap on the host; T <= cap)
+__global__ __launch_bounds__(256) void ae_lstm_ring_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
+                                                           const float* __restrict__ bhh, int T, int stride,
+                                                           int first, int cap, float* __restrict__ seq_out) {
+  ae_lstm_fwd_body<true, true>(gx, whh, bhh, 0, T, stride, first, cap, nullptr, nullptr, nullptr, nullptr, seq_out);
 }
 
 // BPTT, one block per clip in reverse time: thread (q, k) holds column k of W_hh rows [64q, 64q + 64) for
@@ -736,21 +799,37 @@ __global__ __launch_bounds__(256) void ae_loss_finalize_kernel(const float* __re
 // The windowed form (eval scoring of a video): one block per (window i of the launch, 256-pixel chunk); the window's
 // one reconstruction r against its T frames first + i*stride + t of the caller's video, NaN -> 0 on both sides, in
 // ae_loss_kernel's order (fmaf(d, d, sq) over t ascending, the same LDS tree).  recon (nullable) [windows][4096]: r
-// once per window.
+// once per window.  RING (a live stream): frames is the ring's pix array of cap slots -- the plan's xf rows, NaN -> 0
+// already, so nan0 is the identity there and the sums are those of the linear form on the caller's frames -- first is
+// reduced mod cap on the host and the row of step t is s0 + t, less cap where it reaches it (T <= cap).
+template <bool RING>
 __global__ __launch_bounds__(256) void ae_win_loss_kernel(const float* __restrict__ y3,
                                                           const float* __restrict__ frames, int T, int stride,
-                                                          int64_t first, float* __restrict__ recon,
+                                                          int64_t first, int cap, float* __restrict__ recon,
                                                           float* __restrict__ part) {
   __shared__ float red[256];
   const int b = blockIdx.x / AE_CHUNKS, p = (blockIdx.x % AE_CHUNKS) * 256 + threadIdx.x;
   const float r0 = 1.f / (1.f + expf(-y3[(int64_t)b * AE_PIX + p]));
   const float r = r0 != r0 ? 0.f : r0;
-  const float* x = frames + (first + (int64_t)b * stride) * AE_PIX + p;
+  const float* x;
+  int s0 = 0;
+  if constexpr (RING) {
+    x = frames + p;
+    s0 = (int)(((unsigned)first + (unsigned)b * (unsigned)stride) % (unsigned)cap);
+  } else {
+    x = frames + (first + (int64_t)b * stride) * AE_PIX + p;
+  }
   float sq = 0.f;
   // (the loads of an unrolled group issue before its arithmetic; the adds stay in t order)
 #pragma unroll 4
   for (int t = 0; t < T; ++t) {
-    const float d = r - nan0(x[(int64_t)t * AE_PIX]);
+    int64_t row = t;
+    if constexpr (RING) {
+      int q = s0 + t;
+      if (q >= cap) q -= cap;  // (block-uniform)
+      row = q;
+    }
+    const float d = r - nan0(x[row * AE_PIX]);
     sq = fmaf(d, d, sq);
   }
   if (recon) recon[(int64_t)b * AE_PIX + p] = r;
@@ -1170,25 +1249,48 @@ struct AePlanImpl {
                   st);
   }
 
-  // per-window stage for windows w0 .. w0 + nw - 1 (nw <= B): recurrence over the cached rows, ring score, one decoder
-  // call per window, its error against the window's T frames, the blend
-  int windows_forward(const float* cache, const float* frames, int64_t nframes, int T_, int stride, int64_t w0,
-                      int nw, float* seq_out, float* recon_err, float* mem_score, float* score, float* recon,
-                      hipStream_t st) {
+  // The same on a live stream: the encoder writes the plan's own lat / gx rows, and those and the plan's NaN -> 0
+  // frames xf go to slots (f0 + f) mod cap of the ring
+  int frames_forward_ring(const float* frames_chunk, float* ring, int64_t cap, int64_t f0, hipStream_t st) {
+    const AeRing R(cap);
+    training = 0;
+    loss_mode = 0;
+    have_fwd = 0;  // the encoder activations of an earlier forward are gone
+    VAD_TRY(encode(frames_chunk, false, nullptr, lat, gx, nullptr, st));
+    hipLaunchKernelGGL(ae_ring_store_kernel, dim3(NF), dim3(256), 0, st, lat, gx, xf, (int)(f0 % cap), (int)cap,
+                       ring + R.lat, ring + R.gx, ring + R.pix);
+    VAD_LAUNCH_CHECK();
+    return 0;
+  }
+
+  // per-window stage for nw <= B windows, window i = frames first + i*stride + t: recurrence over the cached rows, ring
+  // score, one decoder call per window, its error against the window's T frames, the blend.  ring: cache is a ring of
+  // nframes slots that holds the frames too (frames is not read)
+  int windows_forward(const float* cache, const float* frames, int64_t nframes, bool ring, int T_, int stride,
+                      int64_t first, int nw, float* seq_out, float* recon_err, float* mem_score, float* score,
+                      float* recon, hipStream_t st) {
     const AeLayout& L = ae_layout();
-    const AeFrameCache C(nframes);
-    const int64_t first = w0 * stride;
     training = 0;
     loss_mode = 0;
     have_fwd = 0;  // the decoder activations of an earlier forward are gone
-    hipLaunchKernelGGL(ae_lstm_win_kernel, dim3(nw), dim3(AE_GATES), 0, st, cache + C.gx, P(L.whh), P(L.bhh), T_,
-                       stride, first, seq_out);
+    if (ring) {
+      hipLaunchKernelGGL(ae_lstm_ring_kernel, dim3(nw), dim3(AE_GATES), 0, st, cache + AeRing(nframes).gx, P(L.whh),
+                         P(L.bhh), T_, stride, (int)(first % nframes), (int)nframes, seq_out);
+    } else {
+      hipLaunchKernelGGL(ae_lstm_win_kernel, dim3(nw), dim3(AE_GATES), 0, st, cache + AeFrameCache(nframes).gx,
+                         P(L.whh), P(L.bhh), T_, stride, first, seq_out);
+    }
     VAD_LAUNCH_CHECK();
     hipLaunchKernelGGL(ae_memory_score_kernel, dim3(nw), dim3(256), 0, st, memory, mptr, seq_out, mem_score);
     VAD_LAUNCH_CHECK();
     VAD_TRY(decode(seq_out, nw, false, nullptr, st));
-    hipLaunchKernelGGL(ae_win_loss_kernel, dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3], frames, T_, stride, first,
-                       recon, lpart);
+    if (ring) {
+      hipLaunchKernelGGL(ae_win_loss_kernel<true>, dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3],
+                         cache + AeRing(nframes).pix, T_, stride, first % nframes, (int)nframes, recon, lpart);
+    } else {
+      hipLaunchKernelGGL(ae_win_loss_kernel<false>, dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3], frames, T_, stride,
+                         first, 0, recon, lpart);
+    }
     VAD_LAUNCH_CHECK();
     hipLaunchKernelGGL(ae_win_finalize_kernel, dim3((unsigned)cdiv(nw, 256)), dim3(256), 0, st, lpart, nw, T_,
                        mem_score, recon_err, score);
@@ -1468,8 +1570,64 @@ int vad_ae_windows_forward(vad_ae_plan* plan, const float* cache, const float* f
   VAD_CHECK(nw >= 1 && nw <= c.B, "vad_ae_windows_forward: nw must be in 1..B of the plan (its per-clip buffers)");
   VAD_CHECK(w0 >= 0 && w0 <= (nframes - T) / stride && nw - 1 <= (nframes - T) / stride - w0,
             "vad_ae_windows_forward: w0 .. w0 + nw - 1 reach outside the video");
-  return c.windows_forward(cache, frames, nframes, T, stride, w0, nw, seq, recon_err, mem_score, score, recon,
-                           (hipStream_t)stream);
+  return c.windows_forward(cache, frames, nframes, false, T, stride, w0 * stride, nw, seq, recon_err, mem_score,
+                           score, recon, (hipStream_t)stream);
+}
+
+int64_t vad_ae_ring_floats(int64_t cap) {
+  if (cap < 1 || cap > AE_RING_MAX) {
+    vad::set_error("vad_ae_ring_floats: cap must be in 1..2^24");
+    return -1;
+  }
+  return AeRing(cap).total;
+}
+
+int64_t vad_ae_ring_offset(int64_t cap, int field) {
+  if (cap < 1 || cap > AE_RING_MAX || field < 0 || field > 2) {
+    vad::set_error("vad_ae_ring_offset: cap must be in 1..2^24 and field in 0..2");
+    return -1;
+  }
+  const AeRing R(cap);
+  return field == 0 ? R.lat : field == 1 ? R.gx : R.pix;
+}
+
+int vad_ae_frames_forward_ring(vad_ae_plan* plan, const float* frames_chunk, int64_t cap, float* ring, int64_t f0,
+                               void* stream) {
+  VAD_CHECK(plan != nullptr, "vad_ae_frames_forward_ring: null plan");
+  AePlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_ae_frames_forward_ring: plan not bound");
+  VAD_CHECK(c.T == 1, "vad_ae_frames_forward_ring: needs a plan created as (B = frames per push, T = 1)");
+  VAD_CHECK(frames_chunk && (reinterpret_cast<uintptr_t>(frames_chunk) & 15) == 0,
+            "vad_ae_frames_forward_ring: frames_chunk must be a 16-byte aligned device pointer");
+  VAD_CHECK(ring && (reinterpret_cast<uintptr_t>(ring) & 15) == 0,
+            "vad_ae_frames_forward_ring: ring must be a 16-byte aligned device pointer");
+  VAD_CHECK(cap >= 1 && cap <= AE_RING_MAX, "vad_ae_frames_forward_ring: cap must be in 1..2^24");
+  VAD_CHECK(c.B <= cap, "vad_ae_frames_forward_ring: cap must hold the plan's B frames");
+  VAD_CHECK(f0 >= 0, "vad_ae_frames_forward_ring: f0 must be >= 0");
+  return c.frames_forward_ring(frames_chunk, ring, cap, f0, (hipStream_t)stream);
+}
+
+int vad_ae_windows_forward_ring(vad_ae_plan* plan, const float* ring, int64_t cap, int T, int stride,
+                                int64_t first_frame, int nw, float* seq, float* recon_err, float* mem_score,
+                                float* score, float* recon, void* stream) {
+  VAD_CHECK(plan != nullptr, "vad_ae_windows_forward_ring: null plan");
+  AePlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_ae_windows_forward_ring: plan not bound");
+  VAD_CHECK(c.T == 1, "vad_ae_windows_forward_ring: needs a plan created as (B = frames per push, T = 1)");
+  VAD_CHECK(ring && (reinterpret_cast<uintptr_t>(ring) & 15) == 0,
+            "vad_ae_windows_forward_ring: ring must be a 16-byte aligned device pointer");
+  VAD_CHECK(seq && recon_err && mem_score && score && (reinterpret_cast<uintptr_t>(seq) & 15) == 0,
+            "vad_ae_windows_forward_ring: seq (16-byte aligned), recon_err, mem_score and score must not be null");
+  VAD_CHECK(cap >= 1 && cap <= AE_RING_MAX, "vad_ae_windows_forward_ring: cap must be in 1..2^24");
+  VAD_CHECK(T >= 1 && T <= cap, "vad_ae_windows_forward_ring: T must be in 1..cap");
+  VAD_CHECK(stride >= 1, "vad_ae_windows_forward_ring: stride must be >= 1");
+  VAD_CHECK(first_frame >= 0, "vad_ae_windows_forward_ring: first_frame must be >= 0");
+  VAD_CHECK(nw >= 1 && nw <= c.B,
+            "vad_ae_windows_forward_ring: nw must be in 1..B of the plan (its per-clip buffers)");
+  VAD_CHECK((int64_t)(nw - 1) * stride + T <= cap,
+            "vad_ae_windows_forward_ring: the span (nw - 1) * stride + T of the batch exceeds cap");
+  return c.windows_forward(ring, nullptr, cap, true, T, stride, first_frame, nw, seq, recon_err, mem_score, score,
+                           recon, (hipStream_t)stream);
 }
 
 int vad_ae_debug_buffer(vad_ae_plan* plan, const char* name, int idx, void** ptr, int64_t* nfloats) {

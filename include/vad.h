@@ -464,6 +464,31 @@ int vad_ae_frames_forward(vad_ae_plan* plan, const float* frames_chunk, int64_t 
 int vad_ae_windows_forward(vad_ae_plan* plan, const float* cache, const float* frames, int64_t nframes, int T,
                            int stride, int64_t w0, int nw, float* seq, float* recon_err, float* mem_score,
                            float* score, float* recon, void* stream);
+/* The same two stages on a live stream of frames.  The window error re-reads the raw frames, so the ring holds them
+ * beside the per-frame results: three arrays over cap slots, each 64-float aligned -- 0 lat [cap][64], 1 gx
+ * [cap][256], 2 pix [cap][4096] (the frames with NaN -> 0), 17.25 KB per slot -- in which frame g, counted from the
+ * start of the stream, lives in slot g mod cap.  vad_ae_ring_floats: its size in floats; vad_ae_ring_offset: a
+ * field's offset in floats (both -1 on a bad argument: cap < 1, field outside 0..2).  The library keeps no record of
+ * which frames a ring holds: that is the caller's bookkeeping -- a frame is resident from its
+ * vad_ae_frames_forward_ring until a later one stores frame g + cap over it, and a window must be scored while all
+ * its frames are. */
+int64_t vad_ae_ring_floats(int64_t cap);
+int64_t vad_ae_ring_offset(int64_t cap, int field);
+/* vad_ae_frames_forward on a (B = k, T = 1) plan's k frames frames_chunk [k,1,64,64], stored as frames f0 .. f0 + k -
+ * 1 of the ring (the chunk may straddle the wrap): the encoder writes the plan's own lat / gx rows, one store kernel
+ * copies them and the plan's NaN -> 0 frames to their slots.  A null or unbound plan, a plan with T != 1, k > cap,
+ * f0 < 0 or a null or misaligned pointer is an error, names the argument in vad_last_error and launches nothing. */
+int vad_ae_frames_forward_ring(vad_ae_plan* plan, const float* frames_chunk, int64_t cap, float* ring, int64_t f0,
+                               void* stream);
+/* vad_ae_windows_forward for nw windows of the ring: window i < nw covers frames first_frame + i*stride + t, t < T,
+ * and row i of every output equals vad_ae_forward(training = 0, loss_mode = 1) on that clip (outputs as
+ * vad_ae_windows_forward; the frames come from the ring's pix array).  The batch must fit the ring: a null or unbound
+ * plan, a plan with T != 1, T outside 1..cap, stride < 1, first_frame < 0, nw outside 1..the plan's B, a span
+ * (nw - 1)*stride + T > cap or a null or misaligned pointer is an error, names the argument in vad_last_error and
+ * launches nothing. */
+int vad_ae_windows_forward_ring(vad_ae_plan* plan, const float* ring, int64_t cap, int T, int stride,
+                                int64_t first_frame, int nw, float* seq, float* recon_err, float* mem_score,
+                                float* score, float* recon, void* stream);
 /* the memory ring of any VideoAutoEncoder: update_memory (cad1:201-219; n <= 500 features (n, 64)) and
  * compute_anomaly_score (cad1:262-301; n sequence features -> scores (n,)) */
 /* test access to the last forward's pre-activations (the gradient tests pin their LeakyReLU decisions): "ey" idx l:
