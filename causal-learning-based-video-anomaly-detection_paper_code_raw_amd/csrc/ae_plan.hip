@@ -897,10 +897,14 @@ __global__ __launch_bounds__(256) void ae_memory_score_kernel(const float* __res
   for (int64_t m = threadIdx.x; m < n; m += 256) {
     const float* row = memory + m * AE_LAT;
     float ss = 0.f;
-    for (int k = 0; k < AE_LAT; ++k) ss = fmaf(row[k], row[k], ss);
+    // (the populated rows are NaN-fixed before they are normalised, cad1:272: both passes see the fixed values)
+    for (int k = 0; k < AE_LAT; ++k) {
+      const float v = nan0(row[k]);
+      ss = fmaf(v, v, ss);
+    }
     const float nm = fmaxf(sqrtf(ss), 1e-8f);
     float dot = 0.f;
-    for (int k = 0; k < AE_LAT; ++k) dot = fmaf(sn[k], row[k] / nm, dot);
+    for (int k = 0; k < AE_LAT; ++k) dot = fmaf(sn[k], nan0(row[k]) / nm, dot);
     best = fminf(best, 1.f - fminf(fmaxf(dot, -1.f), 1.f));
   }
   red[threadIdx.x] = best;
@@ -1639,6 +1643,13 @@ int vad_ae_debug_buffer(vad_ae_plan* plan, const char* name, int idx, void** ptr
   else if (n == "dy" && idx >= 0 && idx < 3) { *ptr = c.dy[idx]; *nfloats = c.gd[idx].in.numel(); }
   else if (n == "dst" && idx >= 0 && idx < 3) { *ptr = c.dst[idx]; *nfloats = (int64_t)AE_ST * DEC_CO[idx]; }
   else if (n == "u") { *ptr = c.u; *nfloats = (int64_t)c.B * AE_FLAT; }
+  // the LSTM's per-step state, rows t * B + b: latents, input projection, activated gates, cell state, d pre-gates
+  else if (n == "lat") { *ptr = c.lat; *nfloats = (int64_t)c.NF * AE_LAT; }
+  else if (n == "gx") { *ptr = c.gx; *nfloats = (int64_t)c.NF * AE_GATES; }
+  else if (n == "gates") { *ptr = c.gates; *nfloats = (int64_t)c.NF * AE_GATES; }
+  else if (n == "cs") { *ptr = c.cs; *nfloats = (int64_t)c.NF * AE_LAT; }
+  else if (n == "seq") { *ptr = c.seq; *nfloats = (int64_t)c.B * AE_LAT; }
+  else if (n == "dG") { *ptr = c.dG; *nfloats = (int64_t)c.NF * AE_GATES; }
   else { vad::set_error("vad_ae_debug_buffer: unknown buffer " + n); return 1; }
   return 0;
 }

@@ -494,7 +494,10 @@ int vad_ae_windows_forward_ring(vad_ae_plan* plan, const float* ring, int64_t ca
 /* test access to the last forward's pre-activations (the gradient tests pin their LeakyReLU decisions): "ey" idx l:
  * encoder conv l's raw output [T*B frames, t-major][H][W][Co]; "est" idx l: its per-frame-index BN state [T][8][Co]
  * (mean | invstd | scale | shift | ...); "dy" idx j < 3: decoder ConvTranspose2d j's raw output [B][H][W][Co]; "dst"
- * idx j: its BN state [8][Co]; "u": the decoder Linear's output [B][2048].  Device pointers (vad_debug_d2h). */
+ * idx j: its BN state [8][Co]; "u": the decoder Linear's output [B][2048]; the LSTM's per-step state, rows t*B + b:
+ * "lat" [T*B][64] frame latents, "gx" [T*B][256] input projection, "gates" [T*B][256] activated gates (i f g o), "cs"
+ * [T*B][64] cell state, "dG" [T*B][256] the backward's d pre-activation gates; "seq" [B][64] the sequence feature.
+ * Device pointers (vad_debug_d2h). */
 int vad_ae_debug_buffer(vad_ae_plan* plan, const char* name, int idx, void** ptr, int64_t* nfloats);
 int vad_ae_update_memory(float* memory, int64_t* memory_ptr, const float* features, int n, void* stream);
 int vad_ae_memory_score(const float* memory, const int64_t* memory_ptr, const float* seq, int n, float* scores,

@@ -70,6 +70,9 @@ AE_CASES = [
          test_labels=[1, 0, 0], mem=(500, 498)),
     dict(name="b2t16_skip", B=2, T=16, seed=42, lr=2e-5, labels=[[1, 1], [0, 0]], val_labels=[0, 1],
          test_labels=[0, 1], mem=(20, 20)),
+    # one normal clip per batch: the train step runs at B = 1 (BN over 16 values in the last encoder layer)
+    dict(name="b1t3_single", B=3, T=3, seed=43, lr=1e-5, labels=[[1, 0, 1], [0, 1, 1]], val_labels=[0, 1],
+         test_labels=[0, 1], mem=(20, 20)),
 ]
 
 
