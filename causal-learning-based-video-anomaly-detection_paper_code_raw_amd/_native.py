@@ -131,6 +131,9 @@ _SIGS = {
     "vad_a2_loss_grads": (_I, [_P, _P, _P, _P]),
     "vad_a2_backward": (_I, [_P, _P, _P, _P, _P]),
     "vad_a2_optimizer_step": (_I, [_P, _F, _F, _F, _F, _F, _F, _P]),
+    # the a2 head and loss alone (kernel unit tests; saved / dz are host ctypes arrays of device pointers)
+    "vad_a2_head_forward": (_I, [_P, _P, _I, _U64, _U64, _I64, _I, _P, _P, _P, _P, _P, _P]),
+    "vad_a2_head_backward": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     # bbox clip scorer (config 5)
     "vad_bbox_num_slots": (_I, []),
     "vad_bbox_slot_name": (ctypes.c_char_p, [_I]),

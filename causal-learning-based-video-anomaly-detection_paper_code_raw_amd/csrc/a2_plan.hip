@@ -898,6 +898,12 @@ struct A2PlanImpl {
                         scratch, scratch_floats, st));
     }
     VAD_TRY(adaptive_avgpool3d_fwd(y[2], nullptr, 0, g[2].out(), 4, 4, 4, pooled, st));
+    return head(st);
+  }
+
+  // everything behind the average pool, on the plan's pooled rows: fc (+ Dropout), the head chain, the loss
+  // (vad_a2_head_forward runs this alone)
+  int head(hipStream_t st) {
     DenseAct fc;
     if (training) {
       fc.drop = 1;
@@ -937,6 +943,13 @@ struct A2PlanImpl {
   }
 
   int backward(const float* ext_ds, const float* ext_dadj, const float* ext_df, hipStream_t st) {
+    VAD_TRY(backward_head(ext_ds, ext_dadj, ext_df, st));
+    return backward_convs(st);
+  }
+
+  // the head's share of the backward: up to and including dpooled and the head / fc weight gradients
+  // (vad_a2_head_backward runs this alone)
+  int backward_head(const float* ext_ds, const float* ext_dadj, const float* ext_df, hipStream_t st) {
     const bool from_loss = !ext_ds && !ext_dadj && !ext_df;
     VAD_CHECK(!from_loss || with_loss, "vad_a2_backward: the forward computed no loss and no upstream grads given");
     if (!from_loss) {
@@ -974,6 +987,10 @@ struct A2PlanImpl {
       VAD_TRY(dense_wgrad(dfeat, B, 16, pooled, 4096, G(S_FCW), G(S_FCB), scratch, scratch_floats, nullptr, st));
       VAD_TRY(dense_dgrad(dfeat, B, 16, P(S_FCW), 4096, dpooled, nullptr, 1.f, nullptr, st));
     }
+    return 0;
+  }
+
+  int backward_convs(hipStream_t st) {
     // (direct: each ReLU backward is fused into the producer of its gradient -- the average-pool backward for
     // conv3d_3, the parity-class input gradients for conv3d_2 / conv3d_1 -- instead of a relu_gate pass)
     VAD_TRY(adaptive_avgpool3d_bwd(dpooled, g[2].out(), 4, 4, 4, dA, st, direct ? y[2] : nullptr));
@@ -1166,6 +1183,52 @@ int vad_a2_backward(vad_a2_plan* plan, const float* d_scores, const float* d_adj
                     void* stream) {
   VAD_CHECK(plan != nullptr, "vad_a2_backward: null plan");
   return plan->impl.backward(d_scores, d_adj, d_features, (hipStream_t)stream);
+}
+
+int vad_a2_head_forward(vad_a2_plan* plan, const float* pooled, int training, uint64_t seed, uint64_t step,
+                        int64_t clip0, int with_loss, float* scores, float* adj, float* features, float* losses,
+                        float* const* saved, void* stream) {
+  VAD_CHECK(plan != nullptr, "vad_a2_head_forward: null plan");
+  A2PlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_a2_head_forward: plan not bound");
+  VAD_CHECK((training == 0 || training == 1) && (with_loss == 0 || with_loss == 1),
+            "vad_a2_head_forward: training and with_loss are 0 or 1");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t B = c.B;
+  if (pooled) VAD_HIP(hipMemcpyAsync(c.pooled, pooled, sizeof(float) * B * 4096, hipMemcpyDeviceToDevice, st));
+  c.training = training;
+  c.seed = seed;
+  c.step = step;
+  c.clip0 = clip0;
+  c.with_loss = with_loss;
+  VAD_TRY(c.head(st));
+  const float* src[12] = {c.s, c.adj, c.f, with_loss ? c.losses : nullptr, c.hc0, c.sig, c.g1, c.g1d, c.g2, c.cat,
+                          c.hp0, with_loss ? c.pseudo : nullptr};
+  float* dst[12] = {scores, adj, features, losses};
+  const int64_t n[12] = {B, B * 256, B * 16, 10, B * 32, B * 256, B * 128, B * 128, B * 64, B * 80, B * 32, B};
+  for (int k = 0; k < 8; ++k) dst[4 + k] = saved ? saved[k] : nullptr;
+  for (int k = 0; k < 12; ++k)
+    if (dst[k] && src[k]) VAD_HIP(hipMemcpyAsync(dst[k], src[k], sizeof(float) * n[k], hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
+int vad_a2_head_backward(vad_a2_plan* plan, const float* d_scores, const float* d_adj, const float* d_features,
+                         float* dpooled, float* const* dz, void* stream) {
+  VAD_CHECK(plan != nullptr, "vad_a2_head_backward: null plan");
+  A2PlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_a2_head_backward: plan not bound");
+  VAD_CHECK(d_scores || d_adj || d_features || c.with_loss,
+            "vad_a2_head_backward: the forward computed no loss and no upstream grads given");
+  hipStream_t st = (hipStream_t)stream;
+  VAD_TRY(c.backward_head(d_scores, d_adj, d_features, st));
+  const int64_t B = c.B;
+  const float* src[8] = {c.dpooled, c.dz_ap2, c.dz_ap0, c.dg2, c.dz_ge0, c.dz_cn2, c.dz_cn0, c.dfeat};
+  float* dst[8] = {dpooled};
+  const int64_t n[8] = {B * 4096, B, B * 32, B * 64, B * 128, B * 256, B * 32, B * 16};
+  for (int k = 0; k < 7; ++k) dst[1 + k] = dz ? dz[k] : nullptr;
+  for (int k = 0; k < 8; ++k)
+    if (dst[k]) VAD_HIP(hipMemcpyAsync(dst[k], src[k], sizeof(float) * n[k], hipMemcpyDeviceToDevice, st));
+  return 0;
 }
 
 int vad_a2_optimizer_step(vad_a2_plan* plan, float lr, float beta1, float beta2, float eps, float weight_decay,

@@ -370,6 +370,23 @@ int vad_a2_backward(vad_a2_plan* plan, const float* d_scores, const float* d_adj
                     void* stream);
 int vad_a2_optimizer_step(vad_a2_plan* plan, float lr, float beta1, float beta2, float eps, float weight_decay,
                           float max_norm, void* stream);
+/* The a2 head and compute_improved_loss alone (kernel unit tests): the part of vad_a2_forward / vad_a2_backward behind
+ * the average pool -- fc (+ Dropout), causal discovery, graph encoder, predictor, the loss -- run by the plan's own
+ * code on pooled rows the caller chose; the convs are never run, so a plan of the smallest clip (T = 1, H = W = 4)
+ * serves.  pooled [B][4096] is copied into the plan's buffer (NULL: the rows of the plan's last forward stay).
+ * Outputs as vad_a2_forward's; saved (nullable): host array of 8 nullable device pointers that receive the saved
+ * activations hc0 [B][32], sig [B][256], g1 [B][128], g1d [B][128], g2 [B][64], cat [B][80], hp0 [B][32] and the
+ * pseudo-labels [B] (written with with_loss only).
+ * vad_a2_head_backward: upstream gradients as vad_a2_backward's -> the fc and head slots of the bound grads (written;
+ * the conv slots are left alone), dpooled [B][4096] (nullable) and dz (nullable): host array of 7 nullable device
+ * pointers that receive the pre-activation gradients dz_ap2 [B], dz_ap0 [B][32], dg2 [B][64], dz_ge0 [B][128],
+ * dz_cn2 [B][256], dz_cn0 [B][32] and dfeat [B][16] (fc's output gradient).  A refused call returns non-zero before
+ * anything is queued. */
+int vad_a2_head_forward(vad_a2_plan* plan, const float* pooled, int training, uint64_t seed, uint64_t step,
+                        int64_t clip0, int with_loss, float* scores, float* adj, float* features, float* losses,
+                        float* const* saved, void* stream);
+int vad_a2_head_backward(vad_a2_plan* plan, const float* d_scores, const float* d_adj, const float* d_features,
+                         float* dpooled, float* const* dz, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * avenue_training_script_bbox.py — CausalAnomalyDetector forward (bbox:51-101), eval mode, as run by

@@ -269,3 +269,24 @@ def test_head_entry_points_refuse_before_any_launch():
     assert b"vad_head_forward: null argument" in L.vad_last_error()
     assert bwd(2, 3, 1, a, a, a, need, g=None) != 0
     assert b"vad_head_backward: null argument" in L.vad_last_error()
+
+
+def test_a2_head_entry_points_refuse_before_any_launch():
+    """vad_a2_head_forward / vad_a2_head_backward check the plan and the flags on the host, before anything is queued:
+    a refused call returns non-zero with a text and needs no device (creating a plan touches none)."""
+    from vad_amd import _native
+    L = _native.lib()
+    h = ctypes.c_void_p()
+    _native.check(L.vad_a2_create(2, 1, 4, 4, ctypes.byref(h)))  # the smallest clip: what the head tests run on
+    try:
+        fwd = lambda p: L.vad_a2_head_forward(p, None, 1, 0, 0, 0, 1, None, None, None, None, None, None)
+        bwd = lambda p: L.vad_a2_head_backward(p, None, None, None, None, None, None)
+        for who, call in ((b"vad_a2_head_forward", fwd), (b"vad_a2_head_backward", bwd)):
+            assert call(None) != 0
+            assert who + b": null plan" in L.vad_last_error()
+            assert call(h) != 0
+            assert who + b": plan not bound" in L.vad_last_error()
+    finally:
+        L.vad_a2_destroy(h)
+    assert L.vad_a2_create(1, 1, 4, 4, ctypes.byref(h)) != 0 and L.vad_a2_create(257, 1, 4, 4, ctypes.byref(h)) != 0
+    assert b"unsupported shape" in L.vad_last_error()
