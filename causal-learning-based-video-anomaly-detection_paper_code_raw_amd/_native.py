@@ -116,6 +116,9 @@ _SIGS = {
     "vad_mc_forward": (_I, [_P, _P, _I, _U64, _U64, _I64, _P, _P, _P, _P, _P]),
     "vad_mc_backward": (_I, [_P, _P, _P]),
     "vad_mc_optimizer_step": (_I, [_P, _F, _F, _F, _F, _F, _F, _F, _P]),
+    # the minicausal classifier and BCE alone (kernel unit tests; saved / dz are host ctypes arrays of device pointers)
+    "vad_mc_head_forward": (_I, [_P, _P, _I, _U64, _U64, _I64, _P, _P, _P, _P, _P, _P]),
+    "vad_mc_head_backward": (_I, [_P, _P, _P, _P, _P]),
     # a2 (avenue_training_script2.py)
     "vad_a2_num_slots": (_I, []),
     "vad_a2_slot_name": (ctypes.c_char_p, [_I]),

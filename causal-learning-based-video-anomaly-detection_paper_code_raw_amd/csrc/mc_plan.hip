@@ -341,10 +341,7 @@ struct McPlanImpl {
                             st));
     }
     VAD_TRY(adaptive_avgpool3d_fwd(pooled[2], nullptr, 0, pooled_vol[2], 1, 1, 1, feats, st));
-    McHeadArgs a = head_args();
-    a.scores = scores;
-    hipLaunchKernelGGL(mc_head_fwd_kernel, dim3(1), dim3(256), 0, st, a);
-    VAD_LAUNCH_CHECK();
+    VAD_TRY(head(scores, st));
     if (training && nbt) {
       hipLaunchKernelGGL(mc_nbt_kernel, dim3(1), dim3(64), 0, st, nbt, 3);
       VAD_LAUNCH_CHECK();
@@ -352,8 +349,25 @@ struct McPlanImpl {
     return 0;
   }
 
+  // everything behind the average pool, on the plan's feature rows: the classifier (Dropout x2 from the keyed RNG),
+  // the BCE and the status words (vad_mc_head_forward runs this alone)
+  int head(float* scores, hipStream_t st) {
+    McHeadArgs a = head_args();
+    a.scores = scores;
+    hipLaunchKernelGGL(mc_head_fwd_kernel, dim3(1), dim3(256), 0, st, a);
+    VAD_LAUNCH_CHECK();
+    return 0;
+  }
+
   int backward(const float* d_scores, hipStream_t st) {
     VAD_CHECK(d_scores || have_labels, "vad_mc_backward: no labels in the forward and no d_scores");
+    VAD_TRY(backward_head(d_scores, st));
+    return backward_convs(st);
+  }
+
+  // the head's share of the backward: up to and including dfeat and the six classifier gradients
+  // (vad_mc_head_backward runs this alone)
+  int backward_head(const float* d_scores, hipStream_t st) {
     McHeadBwdArgs hb{};
     hb.f = head_args();
     hb.d_scores = d_scores;
@@ -363,6 +377,10 @@ struct McPlanImpl {
     hb.dz1 = dz1; hb.dz2 = dz2; hb.dz3 = dz3; hb.dfeat = dfeat;
     hipLaunchKernelGGL(mc_head_bwd_kernel, dim3(1), dim3(256), 0, st, hb);
     VAD_LAUNCH_CHECK();
+    return 0;
+  }
+
+  int backward_convs(hipStream_t st) {
     VAD_TRY(adaptive_avgpool3d_bwd(dfeat, pooled_vol[2], 1, 1, 1, dpool, st));
     for (int s = 2; s >= 0; --s) {
       const int Co = MC_CO[s];
@@ -476,6 +494,52 @@ int vad_mc_forward(vad_mc_plan* plan, const float* x, int training, uint64_t see
 int vad_mc_backward(vad_mc_plan* plan, const float* d_scores, void* stream) {
   VAD_CHECK(plan != nullptr, "vad_mc_backward: null plan");
   return plan->impl.backward(d_scores, (hipStream_t)stream);
+}
+
+int vad_mc_head_forward(vad_mc_plan* plan, const float* feats, int training, uint64_t seed, uint64_t step,
+                        int64_t clip0, const float* labels, float* scores, float* losses, int32_t* flags,
+                        float* const* saved, void* stream) {
+  VAD_CHECK(plan != nullptr, "vad_mc_head_forward: null plan");
+  McPlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_mc_head_forward: plan not bound");
+  VAD_CHECK(training == 0 || training == 1, "vad_mc_head_forward: training is 0 or 1");
+  VAD_CHECK(scores != nullptr, "vad_mc_head_forward: null scores");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t B = c.B;
+  if (feats) VAD_HIP(hipMemcpyAsync(c.feats, feats, sizeof(float) * B * 32, hipMemcpyDeviceToDevice, st));
+  c.training = training;
+  c.seed = seed;
+  c.step = step;
+  c.clip0 = clip0;
+  c.have_labels = labels != nullptr;
+  c.flags = flags;
+  if (labels) VAD_HIP(hipMemcpyAsync(c.labels_copy, labels, sizeof(float) * B, hipMemcpyDeviceToDevice, st));
+  VAD_TRY(c.head(scores, st));
+  plan->user_losses = losses;
+  const float* src[6] = {c.losses, c.fd, c.h1, c.h1d, c.h2, c.o};
+  float* dst[6] = {losses};
+  const int64_t n[6] = {4, B * 32, B * 16, B * 16, B * 8, B};
+  for (int k = 0; k < 5; ++k) dst[1 + k] = saved ? saved[k] : nullptr;
+  for (int k = 0; k < 6; ++k)
+    if (dst[k]) VAD_HIP(hipMemcpyAsync(dst[k], src[k], sizeof(float) * n[k], hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
+int vad_mc_head_backward(vad_mc_plan* plan, const float* d_scores, float* dfeat, float* const* dz, void* stream) {
+  VAD_CHECK(plan != nullptr, "vad_mc_head_backward: null plan");
+  McPlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_mc_head_backward: plan not bound");
+  VAD_CHECK(d_scores || c.have_labels, "vad_mc_head_backward: no labels in the last head forward and no d_scores");
+  hipStream_t st = (hipStream_t)stream;
+  VAD_TRY(c.backward_head(d_scores, st));
+  const int64_t B = c.B;
+  const float* src[4] = {c.dfeat, c.dz1, c.dz2, c.dz3};
+  float* dst[4] = {dfeat};
+  const int64_t n[4] = {B * 32, B * 16, B * 8, B};
+  for (int k = 0; k < 3; ++k) dst[1 + k] = dz ? dz[k] : nullptr;
+  for (int k = 0; k < 4; ++k)
+    if (dst[k]) VAD_HIP(hipMemcpyAsync(dst[k], src[k], sizeof(float) * n[k], hipMemcpyDeviceToDevice, st));
+  return 0;
 }
 
 int vad_mc_optimizer_step(vad_mc_plan* plan, float lr, float beta1, float beta2, float eps, float weight_decay,

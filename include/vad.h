@@ -334,6 +334,21 @@ int vad_mc_backward(vad_mc_plan* plan, const float* d_scores, void* stream);
 /* grad norm (float64 sum of per-param norm^2); clip_grad_norm_(max_norm) only when norm > clip_above; Adam */
 int vad_mc_optimizer_step(vad_mc_plan* plan, float lr, float beta1, float beta2, float eps, float weight_decay,
                           float clip_above, float max_norm, void* stream);
+/* The minicausal classifier and its BCE alone (kernel unit tests): the part of vad_mc_forward / vad_mc_backward
+ * behind the average pool -- Dropout(.5), Linear(32, 16), ReLU, Dropout(.3), Linear(16, 8), ReLU, Linear(8, 1),
+ * sigmoid, the BCE, the status words -- run by the plan's own code on feature rows the caller chose; the convs are
+ * never run, so a plan of the smallest clip (T = 4, H = W = 8) serves, and neither the BatchNorm running statistics
+ * nor num_batches_tracked are touched.  feats [B][32] is copied into the plan's buffer (NULL: the rows of the plan's
+ * last forward stay).  labels, scores, losses, flags as vad_mc_forward's; saved (nullable): host array of 5 nullable
+ * device pointers that receive the saved activations fd [B][32], h1 [B][16], h1d [B][16], h2 [B][8] and o [B].
+ * vad_mc_head_backward: d_scores as vad_mc_backward's (NULL needs labels in the last head forward) -> the six
+ * classifier slots of the bound grads (written; the conv and BatchNorm slots are left alone), dfeat [B][32]
+ * (nullable) and dz (nullable): host array of 3 nullable device pointers that receive the pre-activation gradients
+ * dz1 [B][16], dz2 [B][8] and dz3 [B].  A refused call returns non-zero before anything is queued. */
+int vad_mc_head_forward(vad_mc_plan* plan, const float* feats, int training, uint64_t seed, uint64_t step,
+                        int64_t clip0, const float* labels, float* scores, float* losses, int32_t* flags,
+                        float* const* saved, void* stream);
+int vad_mc_head_backward(vad_mc_plan* plan, const float* d_scores, float* dfeat, float* const* dz, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * avenue_training_script2.py — a2 CausalAnomalyDetector (a2:15-101), compute_improved_loss (a2:135-205) and the

@@ -290,3 +290,34 @@ def test_a2_head_entry_points_refuse_before_any_launch():
         L.vad_a2_destroy(h)
     assert L.vad_a2_create(1, 1, 4, 4, ctypes.byref(h)) != 0 and L.vad_a2_create(257, 1, 4, 4, ctypes.byref(h)) != 0
     assert b"unsupported shape" in L.vad_last_error()
+
+
+def test_mc_head_entry_points_refuse_before_any_launch():
+    """vad_mc_head_forward / vad_mc_head_backward check the plan, the binding and the flags on the host, before
+    anything is queued: a refused call returns non-zero with a text and needs no device (creating a plan touches
+    none; the fake binding below is never dereferenced, because every call made on it is refused)."""
+    from vad_amd import _native
+    L = _native.lib()
+    h = ctypes.c_void_p()
+    _native.check(L.vad_mc_create(2, 1, 4, 8, 8, ctypes.byref(h)))  # the smallest clip: what the head tests run on
+    try:
+        fwd = lambda p, training=1, scores=None: L.vad_mc_head_forward(p, None, training, 0, 0, 0, None, scores,
+                                                                        None, None, None, None)
+        bwd = lambda p: L.vad_mc_head_backward(p, None, None, None, None)
+        for who, call in ((b"vad_mc_head_forward", fwd), (b"vad_mc_head_backward", bwd)):
+            assert call(None) != 0
+            assert who + b": null plan" in L.vad_last_error()
+            assert call(h) != 0
+            assert who + b": plan not bound" in L.vad_last_error()
+        fake = ctypes.c_void_p(256)
+        _native.check(L.vad_mc_bind(h, fake, fake, fake, fake, None, fake, fake, fake))  # stores pointers only
+        assert fwd(h, training=2, scores=fake) != 0
+        assert b"vad_mc_head_forward: training is 0 or 1" in L.vad_last_error()
+        assert fwd(h) != 0
+        assert b"vad_mc_head_forward: null scores" in L.vad_last_error()
+        assert bwd(h) != 0  # no head forward with labels on this plan, and no d_scores
+        assert b"vad_mc_head_backward: no labels in the last head forward and no d_scores" in L.vad_last_error()
+    finally:
+        L.vad_mc_destroy(h)
+    assert L.vad_mc_create(0, 1, 4, 8, 8, ctypes.byref(h)) != 0 and L.vad_mc_create(1025, 1, 4, 8, 8, ctypes.byref(h)) != 0
+    assert b"unsupported shape" in L.vad_last_error()
