@@ -209,7 +209,7 @@ def reshape_masks(masks, x):
 
 
 def pinned_oracle_grads(state_dict, x, labels, draws, masks, sync_group=None, bf16=False, dtype=torch.float64,
-                        head_masks=None, det_masks=None, fault=None):
+                        head_masks=None, det_masks=None, fault=None, reverse_channels=False, stem_pins=None):
     """float64 oracle forward/backward of one train step with the ReLU decisions of another forward (masks from
     hip_relu_masks): the exact gradient of that forward's piecewise-linear branch, free of kink flips.  Returns
     (grads {name: float64 tensor or None}, losses {name: float64}, the oracle's result dict incl. "bufs" and
@@ -218,7 +218,9 @@ def pinned_oracle_grads(state_dict, x, labels, draws, masks, sync_group=None, bf
     sum the input channels in reverse order).  dtype: the oracle's arithmetic (float64; float32 gives further,
     independent restatements at fp32 accumulation).  head_masks: the direct classifier's ReLU decisions too
     (cad_oracle.direct_forward's masks; its pre-activations land in record["dir_z{i}"]); det_masks: the detector
-    MLP's likewise (record["det_z{i}"]); fault: backbone_forward_bf16's ragged-edge faults (tests of the bounds)."""
+    MLP's likewise (record["det_z{i}"]); fault: backbone_forward_bf16's ragged-edge faults or, on the exact path,
+    backbone_forward's (tests of the bounds); reverse_channels: the exact path's convs sum their input channels in reverse
+    order; stem_pins: hip_stem_pins' decisions of a training stem -- conv1 and bn1 then train too."""
     from oracle import cad_oracle as co
     params = {k: v.detach().to(dtype).clone() for k, v in state_dict.items()
               if "running" not in k and "num_batches" not in k}
@@ -233,6 +235,10 @@ def pinned_oracle_grads(state_dict, x, labels, draws, masks, sync_group=None, bf
         kw["det_masks"] = det_masks
     if fault is not None:
         kw["fault"] = fault
+    if reverse_channels:
+        kw["reverse_channels"] = True
+    if stem_pins is not None:
+        kw.update(stem_pins=stem_pins, train_stem=True)
     res = co.cad_train_step(params, bufs, {}, xd, labels, draws, relu_masks=rm, sync_group=sync_group,
                             record=record, **kw)
     res["bufs"] = bufs  # running stats after the step's forward
@@ -296,12 +302,30 @@ def restatement_as_device(triple):
                 grads={n: (None if t is None else t.detach().double().numpy().reshape(-1)) for n, t in g.items()})
 
 
-def check_bf16_step(dev, refs, masks, hm, draws, label, yards=("a1", "a2"), det_hm=None):
+F32_SPREAD = 4.0  # the fp32 step: BF16_SPREAD between two correct fp32 summation orders, times the 2 x that
+#                   test_conv3x3_split_accuracy_matches_f32 grants the split-bf16 kernels over exact-f32 MFMA
+
+
+def f32_step_references(sd, x, y, draws, masks, hm, det_masks=None, stem_pins=None):
+    """The pinned oracle steps an fp32 step is judged by, in bf16_step_references' form: "ref" (and "ex", the same
+    step) the exact float64 step, "a1" / "a2" the exact path in float32, channel sums as written / reversed."""
+    kw = dict(head_masks=hm, det_masks=det_masks, stem_pins=stem_pins)
+    ref = pinned_oracle_grads(sd, x, y, draws, masks, **kw)
+    return dict(ref=ref, ex=ref, a1=pinned_oracle_grads(sd, x, y, draws, masks, dtype=torch.float32, **kw),
+                a2=pinned_oracle_grads(sd, x, y, draws, masks, dtype=torch.float32, reverse_channels=True, **kw))
+
+
+def check_bf16_step(dev, refs, masks, hm, draws, label, yards=("a1", "a2"), det_hm=None, spread=BF16_SPREAD,
+                    grad_floor=1e-5, near=2.0 ** -8, bias_tol=1e-4, mode="bf16"):
     """bf16 parity of one step: dev (final, probs, total, grads {name: flat array}) against the float64 bf16
     restatement refs["ref"], with the float32 restatements named by yards as the yardstick (see BF16_SPREAD) and the
     exact float64 step as a loose backstop.  masks / hm / det_hm: dev's ReLU decisions (backbone, direct classifier,
     detector MLP or None), which every reference was pinned to.  Returns the worst device / yardstick ratio over the
-    gradient tensors."""
+    gradient tensors.
+    The defaults are the bf16 mode's bound.  spread: the factor on the yardsticks' distance; grad_floor: the floor of a
+    gradient tensor's relative L2 distance; near: a ReLU decision within this fraction of its layer's rms from zero
+    may flip on a single rounding; bias_tol: the bound on the pre-BatchNorm biases' gradients (exactly 0); mode: the
+    printout's label (the fp32 step: refs of f32_step_references, spread F32_SPREAD, both floors F32_STAT_FLOOR)."""
     from tests.test_oracle_golden import is_pre_bn_bias
     ref_g, ref_l, ref = refs["ref"]
     ys = [refs[k] for k in yards]
@@ -313,9 +337,9 @@ def check_bf16_step(dev, refs, masks, hm, draws, label, yards=("a1", "a2"), det_
         fl = ((z > 0) != hm[i]) & live
         rms = float(z.pow(2).mean().sqrt())
         wz = float(z.abs()[fl].max()) if bool(fl.any()) else 0.0
-        print(f"  bf16 direct_classifier ReLU {i}: {int(fl.sum())} flips against the float64 restatement "
+        print(f"  {mode} direct_classifier ReLU {i}: {int(fl.sum())} flips against the float64 restatement "
               f"(worst |z| {wz / rms:.3g} rms)")
-        assert wz <= 2.0 ** -8 * rms, i
+        assert wz <= near * rms, i
     if det_hm is not None:
         # the detector MLP's hidden units, pinned the same way; a decision may differ from the float64 restatement's
         # own sign as far as the float32 restatements' own signs do (the backbone layers' rule below)
@@ -328,20 +352,20 @@ def check_bf16_step(dev, refs, masks, hm, draws, label, yards=("a1", "a2"), det_
             rms = float(z.pow(2).mean().sqrt())
             wz = float(z.abs()[fl].max()) if bool(fl.any()) else 0.0
             wa = max(float(z.abs()[fa].max()) if bool(fa.any()) else 0.0 for fa in fas)
-            print(f"  bf16 detector ReLU {i}: {int(fl.sum())} flips against the float64 restatement (worst |z| "
+            print(f"  {mode} detector ReLU {i}: {int(fl.sum())} flips against the float64 restatement (worst |z| "
                   f"{wz / rms:.3g} rms; float32 restatements {max(int(fa.sum()) for fa in fas)}, {wa / rms:.3g} rms)")
-            assert wz <= BF16_SPREAD * wa + 2.0 ** -8 * rms, i
+            assert wz <= spread * wa + near * rms, i
     bad = []
 
     def within(d, yard, floor, what):
-        if not d <= BF16_SPREAD * yard + floor:
-            bad.append(f"{what}: device {d:.3g} vs float32 restatement {yard:.3g} (bound {BF16_SPREAD} x + {floor:g})")
+        if not d <= spread * yard + floor:
+            bad.append(f"{what}: device {d:.3g} vs float32 restatement {yard:.3g} (bound {spread} x + {floor:g})")
 
     for key, out_key, floor in (("final", "anomaly_scores", 1e-6), ("probs", "direct_predictions", 1e-6)):
         r64 = ref["out"][out_key].detach().double().numpy()
         d = float(np.abs(dev[key] - r64).max())
         yard = max(float(np.abs(a[2]["out"][out_key].detach().double().numpy() - r64).max()) for a in ys)
-        print(f"  bf16 {key}: device {d:.3g}, float32 restatements {yard:.3g}")
+        print(f"  {mode} {key}: device {d:.3g}, float32 restatements {yard:.3g}")
         within(d, yard, floor, key)
     d = abs(dev["total"] - float(ref_l["total"]))
     yard = max(abs(float(a[1]["total"]) - float(ref_l["total"])) for a in ys)
@@ -357,29 +381,29 @@ def check_bf16_step(dev, refs, masks, hm, draws, label, yards=("a1", "a2"), det_
         wa = max(float(z64.abs()[fa].max()) if bool(fa.any()) else 0.0 for fa in fas)
         na = max(int(fa.sum()) for fa in fas)
         rms = float(z64.pow(2).mean().sqrt())
-        print(f"  bf16 layer {l} ReLU flips: device {int(fd.sum())} (worst |z| {wd / rms:.3g} rms), float32 "
+        print(f"  {mode} layer {l} ReLU flips: device {int(fd.sum())} (worst |z| {wd / rms:.3g} rms), float32 "
               f"restatements {na} ({wa / rms:.3g} rms)")
         # (floors: a decision within one bf16 ulp of the layer's scale from zero may flip on a single rounding flip)
-        near = int((z64.abs() <= 2.0 ** -8 * rms).sum())
-        assert int(fd.sum()) <= BF16_SPREAD * na + near, l
-        assert wd <= BF16_SPREAD * wa + 2.0 ** -8 * rms, l
+        close = int((z64.abs() <= near * rms).sum())
+        assert int(fd.sum()) <= spread * na + close, l
+        assert wd <= spread * wa + near * rms, l
     worst = 0.0
     for n, mine in dev["grads"].items():
         r = ref_g.get(n)
         if r is None:
             assert mine is None or np.abs(mine).max() == 0.0, n
             continue
-        if is_pre_bn_bias(n):
-            assert np.abs(mine).max() < 1e-4, n
+        if is_pre_bn_bias(n) or n == "backbone.conv1.bias":  # true gradient 0 (BatchNorm removes the mean)
+            assert np.abs(mine).max() < bias_tol, n
             continue
         r = r.detach().double().numpy()
         d = rel_l2(mine, r)
         yard = max(rel_l2(a[0][n].detach().double().numpy(), r) for a in ys)
         exact = rel_l2(mine, ex_g[n].detach().double().numpy())
         worst = max(worst, d / max(yard, 1e-12))
-        print(f"  bf16 {n}: device {d:.3g}, float32 restatements {yard:.3g} (device vs the exact step "
+        print(f"  {mode} {n}: device {d:.3g}, float32 restatements {yard:.3g} (device vs the exact step "
               f"{exact:.3g})")
-        within(d, yard, 1e-5, n)
+        within(d, yard, grad_floor, n)
         if not exact <= 0.15:
             bad.append(f"{n}: device vs the exact float64 step {exact:.3g} > 0.15 (backstop)")
     for key, out_key in (("final", "anomaly_scores"), ("probs", "direct_predictions")):
@@ -388,7 +412,7 @@ def check_bf16_step(dev, refs, masks, hm, draws, label, yards=("a1", "a2"), det_
             bad.append(f"{key}: device vs the exact float64 step {d:.3g} > 2e-2 (backstop)")
     if not abs(dev["total"] - float(ex_l["total"])) <= 2e-2 * abs(float(ex_l["total"])):
         bad.append("total loss: device vs the exact float64 step beyond 2e-2 relative (backstop)")
-    print(f"{label}, bf16: worst device / float32-restatements distance ratio {worst:.3g}")
+    print(f"{label}, {mode}: worst device / float32-restatements distance ratio {worst:.3g}")
     assert not bad, "; ".join(bad)
     return worst
 
@@ -403,13 +427,16 @@ def _nhwc(t):
     return np.ascontiguousarray(t.detach().double().permute(0, 2, 3, 1).numpy())
 
 
-def restatement_layer_tensors(triple, masks):
-    """The per-layer tensors of a pinned bf16 restatement step as the device stores them, {name: float64 array}:
+def restatement_layer_tensors(triple, masks, store="bf16"):
+    """The per-layer tensors of a pinned restatement step as the device stores them (store: "bf16", the bf16 mode's
+    storage rounding of dY / dA, or None for the fp32 mode's unrounded ones), {name: float64 array}:
     "pool" and "y{l}" (NF, OH, OW, C); "dY{l}" and "dA{l}" (the gradients of y{l} and of the post-ReLU activation
     a{l}, rounded to bf16 as stored); per channel "mean{l}", "invstd{l}", "mdz{l}" = mean(dZ), "mdzx{l}" =
     mean(dZ * xhat) with dZ = dA{l} masked by the layer's ReLU decision -- taken from the record where a fault
     injection put its own there."""
     from oracle.cad_oracle import bf16r
+    if store is None:
+        bf16r = lambda t: t  # noqa: E731
     rec = triple[2]["record"]
     out = {"pool": _nhwc(rec["pool_raw"])}
     for l in range(8):
@@ -431,7 +458,7 @@ def device_layer_tensors(eng, run, shapes):
     """The same tensors read from the device after one whole forward + backward of the step.  run() repeats that step
     (called once per layer with the plan's stop_layer debug set, so that layer's dY and the dA under it are still in
     their buffers); shapes: per layer (NF, OH, OW, C).  dA7 (the average pool's backward output) is overwritten inside
-    every backward and is not read."""
+    every backward and is not read.  Either storage mode: read_act widens what the plan's last forward stored."""
     from vad_amd import _native as nat
     pl = eng._last[0]
     out = {"pool": read_act(pl, "pool").reshape(shapes[0][:3] + (32,))}  # (layer 0 has stride 1: the pooled map's size)
@@ -451,6 +478,26 @@ def device_layer_tensors(eng, run, shapes):
                 out[f"dA{l - 1}"] = read_act(pl, "dA", 0, n=int(np.prod(shapes[l - 1]))).reshape(shapes[l - 1])
     finally:
         nat.check(nat.lib().vad_cad_set_debug(pl.h, b"stop_layer", -1))
+    return out
+
+
+def local_input_gradients(tens, ref, sd):
+    """Each stride's input gradient judged on its own: {"dA{l-1}": ref's dA{l-1} + (tens' dA{l-1} - the float64 input
+    gradient of layer l taken from tens' OWN dY{l} and the fp32 weights sd)}, l = 1..7, for check_edge_local against
+    ref.  dA{l-1} compared down the whole chain carries the rounding of the forward and of every layer above it (the
+    float32 runs: ~1e-6 of its rms), which hides what one input-gradient kernel adds; this residual holds that kernel's
+    error alone (the float32 runs: ~2e-7).  fp32 storage only (dY is read as stored)."""
+    from oracle.cad_oracle import BACKBONE_CONVS
+    out = {}
+    for l in range(1, 8):
+        if f"dY{l}" not in tens or f"dA{l - 1}" not in tens:
+            continue
+        conv, _, s = BACKBONE_CONVS[l]
+        da = tens[f"dA{l - 1}"]
+        dy = torch.from_numpy(np.ascontiguousarray(tens[f"dY{l}"])).permute(0, 3, 1, 2)
+        own = torch.nn.grad.conv2d_input((da.shape[0], da.shape[3], da.shape[1], da.shape[2]),
+                                         sd[conv + ".weight"].detach().double(), dy, stride=s, padding=1)
+        out[f"dA{l - 1}"] = ref[f"dA{l - 1}"] + (da - own.permute(0, 2, 3, 1).numpy())
     return out
 
 
@@ -480,12 +527,14 @@ def edge_sets(shape, tiles=()):
     return out
 
 
-def check_edge_local(dev, ref, yards, tiles, label, quiet=False):
-    """The per-layer, edge-local bf16 bound.  dev / ref / yards: {name: array} (restatement_layer_tensors /
+def check_edge_local(dev, ref, yards, tiles, label, quiet=False, spread=BF16_SPREAD, act_floor=BF16_ACT_FLOOR,
+                     stat_floor=F32_STAT_FLOOR):
+    """The per-layer, edge-local bound (the defaults: the bf16 mode's; the fp32 mode's: spread F32_SPREAD and
+    F32_STAT_FLOOR for the maps too).  dev / ref / yards: {name: array} (restatement_layer_tensors /
     device_layer_tensors) of the device, the float64 restatement and the float32 restatements; tiles: {tensor name:
     edge_sets' tiles}.  For every tensor V and pixel set S: E(S) = rms over S of (V - V64) / rms of V64 over the
-    whole tensor; the device's must not exceed BF16_SPREAD x the largest of the yardsticks' + the floor (2^-9 for the
-    bf16-stored maps, 1e-6 for the fp32 statistics).  Pixel sets under MIN_SET elements are skipped (printed); a
+    whole tensor; the device's must not exceed spread x the largest of the yardsticks' + the floor (act_floor for the
+    maps: 2^-9 for bf16-stored ones; stat_floor for the fp32 statistics: 1e-6).  Pixel sets under MIN_SET elements are skipped (printed); a
     statistics vector is one set whatever its channel count: each element is already a mean over every pixel.
     Returns (worst E_dev / max E_f32 over the sets the yardstick moved at all, the failures as strings)."""
     worst, bad = 0.0, []
@@ -494,7 +543,7 @@ def check_edge_local(dev, ref, yards, tiles, label, quiet=False):
             continue
         scale = max(float(np.sqrt(np.mean(v64 * v64))), 1e-300)
         stat = v64.ndim == 1
-        floor = F32_STAT_FLOOR if stat else BF16_ACT_FLOOR
+        floor = stat_floor if stat else act_floor
         sets = {"whole": (slice(None),)} if stat else edge_sets(v64.shape, tiles.get(name, ()))
         for sname, ix in sets.items():
             r = v64[ix]
@@ -508,9 +557,9 @@ def check_edge_local(dev, ref, yards, tiles, label, quiet=False):
                 worst = max(worst, ratio)
             if not quiet:
                 print(f"  {label} {name} [{sname}]: device {e:.3g}, float32 restatements {ey:.3g}, ratio {ratio:.3g}")
-            if not e <= BF16_SPREAD * ey + floor:
+            if not e <= spread * ey + floor:
                 bad.append(f"{name} [{sname}]: device {e:.3g} vs float32 restatements {ey:.3g} "
-                           f"(bound {BF16_SPREAD} x + {floor:.3g})")
+                           f"(bound {spread} x + {floor:.3g})")
     return worst, bad
 
 

@@ -98,7 +98,48 @@ def test_conv3x3_forward_and_dgrad(NF, Ci, Co, IH, IW, s, patch):
     np.testing.assert_allclose(dx.cpu().permute(0, 3, 1, 2).numpy(), xr.grad.numpy(), rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("NF,Ci,Co,IH,IW,s", [(2, 64, 64, 29, 29, 1), (2, 32, 64, 57, 57, 2), (1, 256, 256, 8, 8, 1)])
+def _patch_blocks(NF, OH, OW):
+    """conv3_patch_blocks (conv_patch.hip) restated."""
+    if OH <= 8 and OW <= 8:
+        return -(-NF // 2) * -(-OH // 8) * -(-OW // 8)
+    return NF * -(-OH // 8) * -(-OW // 16) if OW <= 16 else NF * -(-OH // 4) * -(-OW // 32)
+
+
+def _s1_forward_route(NF, Ci, Co, OH, OW):
+    """The stride-1 split forward's launcher (conv3_fwd / dispatch_x3<1, true> of conv_x3.hip) restated: (kernel,
+    NI, TH, TW, NT, WCH), kernel "pipe" = conv3x3_x3p_kernel, "x3" = conv3x3_x3_kernel; None where conv3_fwd leaves
+    the patch kernels (more patch blocks than BatchNorm partial rows)."""
+    if _patch_blocks(NF, OH, OW) > -(-(NF * OH * OW) // 64):
+        return None
+    nt = 2 if Co % 64 == 0 and _patch_blocks(NF, OH, OW) * (Co // 64) >= 512 else 1
+    tile = (4, 8, 8) if OH <= 8 and OW <= 8 else (2, 8, 16) if OW <= 16 else (1, 8, 32)
+    if nt == 1 and 16 < Ci <= 256:
+        return ("pipe",) + tile + (1, 2 if Ci == 32 else 1)
+    return ("x3",) + tile + (nt, 2 if nt == 1 and Ci == 32 else 1)
+
+
+# the three shapes the test began with, then ragged ones (map sizes that cut the tile; NF leaving the last frame group
+# of the NI > 1 tiles partly empty): one per pipelined tile, its resident-weight arm, and the 64-channel-per-block
+# (NT = 2) stride-1 forward, which the launcher takes from 512 tile-slices up
+SPLIT_FWD_SHAPES = [(2, 64, 64, 29, 29, 1), (2, 32, 64, 57, 57, 2), (1, 256, 256, 8, 8, 1),
+                    (5, 64, 64, 7, 5, 1), (3, 64, 64, 11, 13, 1), (2, 128, 128, 13, 37, 1), (3, 32, 32, 19, 17, 1),
+                    (64, 64, 128, 13, 27, 1)]
+
+
+def test_split_forward_shapes_reach_their_kernels():
+    """The routes the ragged shapes of SPLIT_FWD_SHAPES were chosen for, by the restated launcher."""
+    want = {(5, 64, 64, 7, 5, 1): ("pipe", 4, 8, 8, 1, 1), (3, 64, 64, 11, 13, 1): ("pipe", 2, 8, 16, 1, 1),
+            (2, 128, 128, 13, 37, 1): ("pipe", 1, 8, 32, 1, 1), (3, 32, 32, 19, 17, 1): ("pipe", 1, 8, 32, 1, 2),
+            (64, 64, 128, 13, 27, 1): ("x3", 1, 8, 32, 2, 1)}
+    for shape, route in want.items():
+        NF, Ci, Co, IH, IW, s = shape
+        assert shape in SPLIT_FWD_SHAPES and s == 1
+        assert _s1_forward_route(NF, Ci, Co, IH, IW) == route, shape
+        ni, th, tw = route[1:4]
+        assert IH % th and IW % tw and (ni == 1 or NF % ni), shape
+
+
+@pytest.mark.parametrize("NF,Ci,Co,IH,IW,s", SPLIT_FWD_SHAPES)
 def test_conv3x3_split_accuracy_matches_f32(NF, Ci, Co, IH, IW, s):
     """The split-bf16 kernels (three bf16 planes per fp32 operand, six products per K step) against an fp64
     reference: their worst error, relative to sum |x||w| of each output, is within 2x that of the exact-f32 MFMA
@@ -160,6 +201,40 @@ def test_conv3x3_dgrad_s2_split_accuracy_matches_f32(NF, Ci, Co, IH, IW):
     nat.lib().vad_set_tuning(b"conv_dgrad_s2_x3", 1)
     assert errs[1] < 1e-6, errs
     assert errs[1] <= 2.0 * errs[0] + 1e-8, errs
+
+
+@pytest.mark.parametrize("NF,Ci,Co,IH,IW", [(3, 32, 32, 19, 17), (5, 64, 64, 9, 13), (3, 256, 256, 7, 5),
+                                            (2, 128, 128, 29, 27)])
+def test_conv3x3_dgrad_s1_split_accuracy_matches_f32(NF, Ci, Co, IH, IW):
+    """Stride-1 input gradient on the split-bf16 kernel (conv3_x3_dgrad: conv3x3_x3_kernel with FWD = false; 8x32
+    tiles with the weights resident at Co = 32, 2 x 8x16 and 4 x 8x8 tiles with a partly empty last frame group, 8x32
+    tiles at 128 channels; every map cuts its tile) against an fp64 reference: worst error relative to sum |dy||w|
+    below 1e-6 and within 2x that of the exact-f32 patch kernel."""
+    nat = _lib()
+    g = torch.Generator().manual_seed(23 + Ci + IH)
+    w = torch.randn(Co, Ci, 3, 3, generator=g) / (9 * Ci) ** 0.5
+    dy = torch.randn(NF, Co, IH, IW, generator=g)
+    ref = torch.nn.grad.conv2d_input((NF, Ci, IH, IW), w.double(), dy.double(), stride=1, padding=1)
+    mag = torch.nn.grad.conv2d_input((NF, Ci, IH, IW), w.double().abs(), dy.double().abs(), stride=1, padding=1)
+    d = torch.device("cuda")
+    dyh = dy.permute(0, 2, 3, 1).contiguous().to(d)
+    wdev = w.contiguous().to(d)
+    errs = {}
+    try:
+        for patch in (1, 3):
+            _conv_path(nat, patch)
+            wf = torch.empty(9 * Ci * Co, device=d)
+            wd = torch.empty(9 * Ci * Co, device=d)
+            dx = torch.empty(NF, IH, IW, Ci, device=d)
+            nat.check(nat.lib().vad_conv3x3_dgrad(dyh.data_ptr(), NF, Ci, IH, IW, wdev.data_ptr(), Co, 1,
+                                                  dx.data_ptr(), wf.data_ptr(), wd.data_ptr(), nat.stream_of(d)))
+            torch.cuda.synchronize()
+            errs[patch] = float(((dx.cpu().permute(0, 3, 1, 2).double() - ref).abs() / (mag + 1e-30)).max())
+    finally:
+        _conv_default(nat)
+    print(f"stride-1 dgrad {NF, Ci, Co, IH, IW}: worst |err| / sum |dy||w| split {errs[3]:.3g}, f32 {errs[1]:.3g}")
+    assert errs[3] < 1e-6, errs
+    assert errs[3] <= 2.0 * errs[1] + 1e-8, errs
 
 
 @pytest.mark.parametrize("stream", [rng.S_DET_DROP1, rng.S_EPS, rng.S_INPUT])
