@@ -50,7 +50,11 @@ _SIGS = {
     "vad_cad_frames_forward_ring": (_I, [_P, _P, _I64, _P, _I64, _P]),
     "vad_cad_windows_forward_ring": (_I, [_P, _P, _I64, _I, _I, _I64, _I64, _I, _U64, _U64, _I64, _P, _P, _P, _P, _P,
                                           _P, _P, _P]),
-    "vad_cad_backward": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vad_cad_group_table_bytes": (_I64, [_I64, _I64]),
+    "vad_cad_frames_forward_group": (_I, [_P, _P, _I64, _P, _P, _P, _P]),
+    "vad_cad_windows_forward_group": (_I, [_P, _P, _I64, _I, _I, _P, _I, _P, _U64, _U64, _P, _P, _P, _P, _P, _P, _P,
+                                           _P]),
+    "vad_cad_backward":(_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vad_cad_backward_stage": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vad_cad_wait_side": (_I, [_P, _P]),
     "vad_cad_wait_layer_grads": (_I, [_P, _I, _P]),

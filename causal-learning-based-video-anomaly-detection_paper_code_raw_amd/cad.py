@@ -252,3 +252,20 @@ class CausalAnomalyDetector(nn.Module):
         activations: a backward still pending on an earlier forward raises the "most recent forward only" error."""
         from . import stream as _stream
         return _stream.CadStream(self, window, stride, max_push=max_push, seed=seed, step=step, clip0=clip0)
+
+    def open_stream_group(self, num_streams, window=16, stride=1, *, max_push=1, seed=0, step=0, clip0=0):
+        """num_streams live sources of one frame size scored in shared launches (eval mode, fp32; stream_group.py):
+        ``g.push(frames)`` takes a list of num_streams entries, entry s the next 0 <= k_s <= max_push frames of
+        stream s as (k_s, 1, H, W) on a HIP device or None, and returns a list of num_streams dicts, dict s being what
+        ``open_stream(window, stride, max_push=max_push, seed=seed, step=step, clip0=clip0[s]).push(frames_s)``
+        returns on the same history of frames (empty tensors where stream s completed no window, no detections where
+        it pushed nothing).  clip0: an int or num_streams ints.  All frames of a push go through one per-frame pass
+        and all the windows they complete through one per-window pass, so a push costs about what one open_stream
+        push costs, whatever num_streams.  Memory is num_streams rings of window + max_push - 1 frames in one
+        allocation, made at the first push, which also fixes the frame size.  ``g.frames_seen[s]`` /
+        ``g.windows_emitted[s]`` count per stream; ``g.reset(s=None)`` restarts one stream or all.  ValueError, before
+        any device work, as for open_stream, and at a push for a sequence of another length, k_s > max_push, a
+        channel count other than 1, a frame size other than the group's, or no frame at all."""
+        from . import stream_group as _group
+        return _group.CadStreamGroup(self, num_streams, window, stride, max_push=max_push, seed=seed, step=step,
+                                     clip0=clip0)

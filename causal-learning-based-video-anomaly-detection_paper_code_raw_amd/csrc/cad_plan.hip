@@ -945,22 +945,27 @@ struct CadPlanImpl {
 
   // The per-frame stage of the eval forward on this plan's NF frames, into frames frame0.. of a frame cache (ring:
   // into slots (frame0 + f) mod nframes of a ring of nframes slots).
-  int frames_forward(const float* x, int64_t nframes, float* cache, int64_t frame0, bool ring, hipStream_t st) {
+  // dst (a group of streams): a device table of NF slots; frame f goes to slot dst[f] of the nframes slots, or nowhere.
+  int frames_forward(const float* x, int64_t nframes, float* cache, int64_t frame0, bool ring, hipStream_t st,
+                     const int* dst = nullptr) {
     training = 0;
     labels = nullptr;
     have_labels = false;
     VAD_TRY(forward(x, st, true));
-    TIMED("frame_cache", frame_cache_store(head_args(), head_out(), feats, cache, nframes, frame0, st, ring));
+    if (dst) TIMED("frame_cache", frame_cache_store_group(head_args(), head_out(), feats, cache, nframes, dst, st));
+    else TIMED("frame_cache", frame_cache_store(head_args(), head_out(), feats, cache, nframes, frame0, st, ring));
     return 0;
   }
 
   // The per-window stage for nw <= B windows of a frame cache, window i = frames first + i * stride + t at window
   // index widx0 + i: the per-clip buffers of this plan (pooled, the direct classifier's activations, clip_flags) take
   // one row per window.  The outputs go straight to the caller's arrays; the plan's own result arrays, flags and
-  // detector gate stay as the last forward left them.  ring: the cache is a ring of nframes slots.
+  // detector gate stay as the last forward left them.  ring: the cache is a ring of nframes slots.  tab (a group of
+  // streams): the cache holds nframes / cap rings of cap slots and window i is row i of the device window table
+  // (head.h); ring, stride, first, widx0 and clip0 are not used then.
   int windows_forward(const float* cache, int64_t nframes, bool ring, int Tw, int stride, int64_t first, int64_t widx0,
                       int nw, float* o_final, float* o_probs, float* o_causal, float* o_kl, float* o_z, float* o_adj,
-                      int* o_nmax, hipStream_t st) {
+                      int* o_nmax, hipStream_t st, const int64_t* tab = nullptr, int cap = 0) {
     const CadLayout& LY = layout();
     VAD_TRY(join_open_stage2(st));
     training = 0;
@@ -969,7 +974,8 @@ struct CadPlanImpl {
     bwd_state = 0;
     dir_pre = tail_pre = 0;
     const FrameCache C(nframes);
-    TIMED("window_mean", window_mean(cache, nframes, Tw, stride, first, nw, pooled, st, ring));
+    if (tab) TIMED("window_mean", window_mean_group(cache, nframes, cap, Tw, tab, nw, pooled, st));
+    else TIMED("window_mean", window_mean(cache, nframes, Tw, stride, first, nw, pooled, st, ring));
     // direct_classifier on the window means (cad:525-538, 568-570), eval activations, through the forward's launchers
     const int gd[6] = {6144, 512, 256, 128, 64, 2};
     const float* in = pooled;
@@ -993,9 +999,10 @@ struct CadPlanImpl {
     win.stride = stride;
     win.first = first;
     win.widx0 = widx0;
-    win.cap = ring ? (int)nframes : 0;
+    win.cap = tab ? cap : ring ? (int)nframes : 0;
     const HeadOut ho{o_causal, o_kl, o_z, o_adj, nullptr, nullptr, o_nmax, clip_flags};
-    TIMED("head_seq_win", head_seq_windows_fwd(a, win, nw, ho, st));
+    if (tab) TIMED("head_seq_win", head_seq_group_fwd(a, win, tab, nw, ho, st));
+    else TIMED("head_seq_win", head_seq_windows_fwd(a, win, nw, ho, st));
     TailArgs t{};
     t.B = nw;
     t.direct_logits = glog;
@@ -1527,6 +1534,88 @@ int vad_cad_windows_forward_ring(vad_cad_plan* plan, const float* cache, int64_t
   c.clip0 = clip0;
   return c.windows_forward(cache, cap, true, T, stride, first_frame, widx0, nw, final_scores, probs, causal, kl, z,
                            adj, nmax, (hipStream_t)stream);
+}
+
+// A group of streams.  The device table of one push: the plan's B*T destination slots (int32) from byte 0, the window
+// rows (3 int64 each) from the next multiple of 16 bytes.  Both calls validate their host table entry by entry before
+// anything is queued: the kernels trust what they read.
+static int64_t group_window_table_offset(int64_t nf) { return (nf * 4 + 15) & ~15ll; }
+
+int64_t vad_cad_group_table_bytes(int64_t nf, int64_t nw) {
+  if (nf < 1 || nw < 0 || nf > (1ll << 31) || nw > (1ll << 31)) {
+    vad::set_error("vad_cad_group_table_bytes: nf must be >= 1 and nw >= 0");
+    return -1;
+  }
+  return group_window_table_offset(nf) + nw * 24;
+}
+
+int vad_cad_frames_forward_group(vad_cad_plan* plan, const float* x, int64_t total_slots, float* cache,
+                                 const int32_t* host_dst, void* dev_table, void* stream) {
+  VAD_CHECK(plan && x && cache, "vad_cad_frames_forward_group: null argument");
+  VAD_CHECK(host_dst && dev_table, "vad_cad_frames_forward_group: null table (host_dst or dev_table)");
+  VAD_CHECK((reinterpret_cast<uintptr_t>(dev_table) & 15) == 0,
+            "vad_cad_frames_forward_group: dev_table must be 16-B aligned");
+  CadPlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_cad_frames_forward_group: plan not bound");
+  VAD_CHECK(total_slots >= 1, "vad_cad_frames_forward_group: total_slots must be >= 1");
+  VAD_CHECK((int64_t)c.NF * c.H * c.W * 4 < (1ll << 31), "vad_cad_frames_forward_group: x is 2 GB or more");
+  VAD_CHECK(FrameCache(total_slots).total * 4 < (1ll << 31), "vad_cad_frames_forward_group: cache is 2 GB or more");
+  std::vector<int32_t> seen;
+  for (int f = 0; f < c.NF; ++f) {
+    const int32_t d = host_dst[f];
+    if (d < -1 || d >= total_slots) {
+      vad::set_error("vad_cad_frames_forward_group: dst[" + std::to_string(f) + "] = " + std::to_string(d) +
+                     " is outside -1 .. total_slots - 1 = " + std::to_string(total_slots - 1));
+      return 1;
+    }
+    if (d >= 0) seen.push_back(d);
+  }
+  std::sort(seen.begin(), seen.end());
+  for (size_t i = 1; i < seen.size(); ++i)
+    if (seen[i] == seen[i - 1]) {
+      vad::set_error("vad_cad_frames_forward_group: two entries of dst name slot " + std::to_string(seen[i]));
+      return 1;
+    }
+  VAD_HIP(hipMemcpyAsync(dev_table, host_dst, (size_t)c.NF * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+  return c.frames_forward(x, total_slots, cache, 0, false, (hipStream_t)stream, static_cast<const int*>(dev_table));
+}
+
+int vad_cad_windows_forward_group(vad_cad_plan* plan, const float* cache, int64_t total_slots, int cap, int T,
+                                  const int64_t* host_windows, int nw, void* dev_table, uint64_t seed, uint64_t step,
+                                  float* final_scores, float* probs, float* causal, float* kl, float* z, float* adj,
+                                  int32_t* nmax, void* stream) {
+  VAD_CHECK(plan && cache, "vad_cad_windows_forward_group: null plan or cache");
+  VAD_CHECK(host_windows && dev_table, "vad_cad_windows_forward_group: null table (host_windows or dev_table)");
+  VAD_CHECK((reinterpret_cast<uintptr_t>(dev_table) & 15) == 0,
+            "vad_cad_windows_forward_group: dev_table must be 16-B aligned");
+  VAD_CHECK(final_scores && probs && causal && kl && z && adj && nmax, "vad_cad_windows_forward_group: null output");
+  CadPlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_cad_windows_forward_group: plan not bound");
+  VAD_CHECK(cap >= 1 && total_slots >= cap, "vad_cad_windows_forward_group: cap must be in 1..total_slots");
+  VAD_CHECK(T >= 1 && T <= cap, "vad_cad_windows_forward_group: T must be in 1..cap");
+  VAD_CHECK(T <= 4096, "vad_cad_windows_forward_group: T too large (head: at most 4096 steps)");
+  VAD_CHECK(nw >= 1 && nw <= c.B,
+            "vad_cad_windows_forward_group: nw must be in 1..the plan's B (one per-clip scratch row per window)");
+  VAD_CHECK(FrameCache(total_slots).total * 4 < (1ll << 31), "vad_cad_windows_forward_group: cache is 2 GB or more");
+  for (int i = 0; i < nw; ++i) {
+    const int64_t base = host_windows[3 * i], s0 = host_windows[3 * i + 1];
+    const char* what = nullptr;
+    if (base < 0 || base % cap != 0) what = "base must be a non-negative multiple of cap";
+    else if (base + cap > total_slots) what = "base + cap exceeds total_slots";
+    else if (s0 < 0 || s0 >= cap) what = "first must be in 0..cap - 1";
+    if (what) {
+      vad::set_error("vad_cad_windows_forward_group: window " + std::to_string(i) + " (base " + std::to_string(base) +
+                     ", first " + std::to_string(s0) + "): " + what);
+      return 1;
+    }
+  }
+  int64_t* tab = reinterpret_cast<int64_t*>(static_cast<char*>(dev_table) + group_window_table_offset(c.NF));
+  VAD_HIP(hipMemcpyAsync(tab, host_windows, (size_t)nw * 24, hipMemcpyHostToDevice, (hipStream_t)stream));
+  c.seed = seed;
+  c.step = step;
+  c.clip0 = 0;
+  return c.windows_forward(cache, total_slots, true, T, 1, 0, 0, nw, final_scores, probs, causal, kl, z, adj, nmax,
+                           (hipStream_t)stream, tab, cap);
 }
 
 int vad_cad_backward(vad_cad_plan* plan, int use_loss, const float* d_final, const float* d_probs,

@@ -112,6 +112,20 @@ struct SeqWindows {
 };
 int head_seq_windows_fwd(const HeadArgs& a, const SeqWindows& win, int nw, const HeadOut& o, hipStream_t st);
 
+// A group of streams: one cache of total_slots = (number of rings) * cap slots, ring s in slots s * cap .. (s + 1) *
+// cap - 1.  The three kernels take their addresses from device tables that the caller has validated on the host
+// (vad_cad_*_group in cad_plan.hip); nothing here looks at a table's contents.
+// frame_cache_store with frame f going to slot dst[f] of the cache, or nowhere where dst[f] < 0
+int frame_cache_store_group(const HeadArgs& a, const HeadOut& o, const float* feats, float* cache, int64_t total_slots,
+                            const int* dst, hipStream_t st);
+// Window table: int64 (base, s0, key) per window -- the window's T frames are slots base + ((s0 + t) wrapped once at
+// cap) and key is its RNG clip key.  window_mean / head_seq_windows_fwd on the nw windows of such a table; win.gi /
+// counts / slot / cap are read, win.stride / first / widx0 and a.clip0 are not.
+int window_mean_group(const float* cache, int64_t total_slots, int cap, int T, const int64_t* tab, int nw,
+                      float* pooled, hipStream_t st);
+int head_seq_group_fwd(const HeadArgs& a, const SeqWindows& win, const int64_t* tab, int nw, const HeadOut& o,
+                       hipStream_t st);
+
 // backward: upstream grads -> grad slabs [B][slab] and d(det logits) [B*T][20]
 struct HeadUp {
   const float* d_causal;  // [B]

@@ -391,11 +391,17 @@ __global__ __launch_bounds__(256) void head_rows_fwd_kernel(HeadArgs a, const fl
 // traffic).  RING (head_seq_ring_kernel, with WIN): the cache is a ring of win.cap >= T slots and frame g lives in slot
 // g mod cap; the window's first slot is reduced once per block, step t then reads slot s0 + t less cap where it passes
 // the end (s0 + t < 2 cap) -- an add, a compare and a select on wave-uniform values, no division in the recurrence.
+// GROUP (head_seq_group_kernel, with RING): the cache holds many rings of win.cap slots and block b reads its entry
+// (base_b, s0_b, key_b) of the window table once, before the recurrence: cnt / slot / gi_win start at slot base_b,
+// s0_b is the window's first slot within that ring and key_b its RNG clip key.  The entry's address depends on
+// blockIdx alone, so the three values are scalar loads and stay in scalar registers; the recurrence is the ring form's.
 // Every difference is an `if constexpr`, so the clip kernel's and the linear window kernel's arithmetic and its order
 // are those of the untemplated kernel.
-template <bool WIN, bool RING = false>
-__device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWindows win) {
+template <bool WIN, bool RING = false, bool GROUP = false>
+__device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWindows win,
+                                                  const int64_t* __restrict__ tab = nullptr) {
   static_assert(WIN || !RING, "the ring form addresses a frame cache");
+  static_assert(RING || !GROUP, "the group form addresses rings");
   const int b = blockIdx.x, T = a.T, tid = threadIdx.x;
   const HL L;
   const RowLayout RL((int64_t)a.B * T * NMAX);
@@ -415,7 +421,15 @@ __device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWind
       return t;
     }
   };
-  if constexpr (WIN) {
+  if constexpr (GROUP) {
+    const int64_t* e = tab + 3 * (int64_t)b;
+    const int64_t f0 = e[0];
+    s0 = (int)e[1];
+    cnt = win.counts + f0;
+    slot = win.slot + f0 * NMAX;
+    gi_win = win.gi + f0 * NMAX * G3;
+    a.clip0 = e[2] - b;  // the RNG key of block b, a.clip0 + b below, is the table's
+  } else if constexpr (WIN) {
     int64_t f0 = win.first + (int64_t)b * win.stride;
     if constexpr (RING) {
       s0 = (int)(f0 % win.cap);
@@ -689,6 +703,10 @@ __global__ __launch_bounds__(HT) void head_seq_win_kernel(HeadArgs a, HeadOut o,
 __global__ __launch_bounds__(HT) void head_seq_ring_kernel(HeadArgs a, HeadOut o, SeqWindows win) {
   head_seq_fwd_body<true, true>(a, o, win);
 }
+__global__ __launch_bounds__(HT) void head_seq_group_kernel(HeadArgs a, HeadOut o, SeqWindows win,
+                                                            const int64_t* __restrict__ tab) {
+  head_seq_fwd_body<true, true, true>(a, o, win, tab);
+}
 
 int head_rows_fwd(const HeadArgs& a, const float* det_logits, const HeadOut& o, hipStream_t st) {
   VAD_CHECK(a.T <= 4096, "head: T too large");
@@ -708,6 +726,14 @@ int head_seq_windows_fwd(const HeadArgs& a, const SeqWindows& win, int nw, const
             "head: the windows do not fit the ring");
   if (win.cap > 0) VAD_KLAUNCH(head_seq_ring_kernel, dim3(nw), dim3(HT), 0, st, a, o, win);
   else VAD_KLAUNCH(head_seq_win_kernel, dim3(nw), dim3(HT), 0, st, a, o, win);
+  VAD_LAUNCH_CHECK();
+  return 0;
+}
+int head_seq_group_fwd(const HeadArgs& a, const SeqWindows& win, const int64_t* tab, int nw, const HeadOut& o,
+                       hipStream_t st) {
+  VAD_CHECK(tab != nullptr && nw >= 1 && a.T >= 1 && a.T <= 4096 && win.cap >= a.T,
+            "head: bad window-table arguments");
+  VAD_KLAUNCH(head_seq_group_kernel, dim3(nw), dim3(HT), 0, st, a, o, win, tab);
   VAD_LAUNCH_CHECK();
   return 0;
 }

@@ -173,6 +173,33 @@ int vad_cad_windows_forward_ring(vad_cad_plan* plan, const float* cache, int64_t
                                  int64_t first_frame, int64_t widx0, int nw, uint64_t seed, uint64_t step,
                                  int64_t clip0, float* final_scores, float* probs, float* causal, float* kl, float* z,
                                  float* adj, int32_t* nmax, void* stream);
+/* The same two stages for a group of streams that share launches: one cache of total_slots slots (the layout of
+ * vad_cad_frame_cache_floats(total_slots)) holding total_slots / cap rings of cap slots, ring s in slots s*cap ..
+ * (s+1)*cap - 1.  Which slot a frame goes to and which slots a window reads come from tables the caller passes as
+ * HOST pointers.  Each call validates its table entry by entry on the host -- a violation returns non-zero, names the
+ * entry in vad_last_error and launches nothing, so a bad table cannot cause a store or a load outside the cache --
+ * and then copies it with one hipMemcpyAsync on `stream` into dev_table, which the kernels read.  dev_table is
+ * caller-owned device memory, 16-byte aligned, of at least vad_cad_group_table_bytes(B*T of the frames plan, nw)
+ * bytes (the destinations from byte 0, the window rows after them; -1 on a bad argument); the library still owns no
+ * device memory.  The caller must not reuse dev_table -- for another call or anything else -- while an earlier call
+ * on ANOTHER stream may still read it; calls on one stream are ordered by the stream.  A pageable host table may be
+ * changed as soon as the call returns; a pinned one only once `stream` has passed the copy. */
+int64_t vad_cad_group_table_bytes(int64_t nf, int64_t nw);
+/* vad_cad_frames_forward on the plan's B*T frames, frame f stored to slot host_dst[f] of the cache, or nowhere where
+ * host_dst[f] is -1 (a padding frame: its per-frame stage runs, nothing of it is kept).  Every host_dst[f] must lie
+ * in -1 .. total_slots - 1 and no two entries >= 0 may be equal. */
+int vad_cad_frames_forward_group(vad_cad_plan* plan, const float* x, int64_t total_slots, float* cache,
+                                 const int32_t* host_dst, void* dev_table, void* stream);
+/* vad_cad_windows_forward_ring for nw windows that may lie in different rings: host_windows holds three int64 per
+ * window, (base, first, key) -- the window's frame t is slot base + ((first + t) wrapped once at cap), and row i of
+ * every output equals vad_cad_forward(training = 0) on that clip at clip index key (the key of its VAE noise).
+ * base must be a multiple of cap with base + cap <= total_slots, 0 <= first < cap, 1 <= T <= cap, T <= 4096 and
+ * 1 <= nw <= the plan's B.  dev_table is the one of the frames call on the same plan (the window rows lie after that
+ * plan's B*T destinations).  Outputs as vad_cad_windows_forward_ring. */
+int vad_cad_windows_forward_group(vad_cad_plan* plan, const float* cache, int64_t total_slots, int cap, int T,
+                                  const int64_t* host_windows, int nw, void* dev_table, uint64_t seed, uint64_t step,
+                                  float* final_scores, float* probs, float* causal, float* kl, float* z, float* adj,
+                                  int32_t* nmax, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Single building blocks (kernel unit tests; same kernels as the fused step)
