@@ -152,6 +152,8 @@ _SIGS = {
     "vad_bbox_workspace_bytes": (_I64, [_P]),
     "vad_bbox_bind": (_I, [_P, _P, _P]),
     "vad_bbox_forward": (_I, [_P, _P, _P, _P, _P, _P]),
+    "vad_bbox_head_forward": (_I, [_P, _P, _P, _P, _P]),
+    "vad_bbox_debug_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(_I64)]),
     # cad1 memory autoencoder (causal_anomaly_detection1.py)
     "vad_ae_num_slots": (_I, []),
     "vad_ae_slot_name": (ctypes.c_char_p, [_I]),

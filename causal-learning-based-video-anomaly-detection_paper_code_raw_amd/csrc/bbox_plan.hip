@@ -94,7 +94,10 @@ __global__ __launch_bounds__(256) void bbox_conv1_pool_kernel(const float* __res
     for (int c = 0; c < 8; ++c) {
       float m = acc[0][c];
 #pragma unroll
-      for (int v = 1; v < 8; ++v) m = fmaxf(m, acc[v][c]);
+      for (int v = 1; v < 8; ++v) {  // (not fmaxf: one NaN in the window makes the pooled voxel NaN, as maxpool3d_fwd)
+        const float a = acc[v][c];
+        if (a > m || a != a) m = a;
+      }
       o[c] = relu_nan(m + bias[c0 + c]);
     }
     float* dst = pooled + ((((int64_t)b * T2 + pd) * H2 + py) * W2 + px) * 32 + c0;
@@ -160,10 +163,10 @@ struct BbPlanImpl {
     w3 = w.take<float>(64 * 32 * 27);
   }
 
-  int forward(const float* x, float* scores, float* adj, float* features, hipStream_t st) {
+  // x -> feature rows f (B, 1024)
+  int encoder(const float* x, float* f, hipStream_t st) {
     DenseAct relu;
     relu.relu = 1;
-    float* f = features ? features : feats;
     if (g_bbox_im2col) {  // (knob "bbox_im2col": the round-2 path -- im2col columns + f32 MFMA GEMMs)
       VAD_TRY(im2col3d(x, ncdhw_strides(g1.in), g1, nullptr, nullptr, 0, cols1, st));
       VAD_TRY(dense_fwd(cols1, (int)g1.rows(), g1.K(), P(0), P(1), 32, y1, relu, scratch, scratch_floats, st));
@@ -187,12 +190,25 @@ struct BbPlanImpl {
       VAD_TRY(conv3d_x3_fwd(B, pv.D, pv.H, pv.W, 32, 64, pooled, w3, P(3), y2, st));
       VAD_TRY(adaptive_avgpool3d_fwd(y2, nullptr, 1, g2.out(), 1, 4, 4, f, st));
     }
+    return 0;
+  }
+
+  // feature rows -> causal_net and classifier GEMMs -> tail (vad_bbox_head_forward runs this alone)
+  int head(const float* f, float* scores, float* adj, hipStream_t st) {
+    DenseAct relu;
+    relu.relu = 1;
     VAD_TRY(dense_fwd(f, B, 1024, P(4), P(5), 256, hc, relu, scratch, scratch_floats, st));
     VAD_TRY(dense_fwd(hc, B, 256, P(6), P(7), 256, logits, DenseAct{}, scratch, scratch_floats, st));
     VAD_TRY(dense_fwd(f, B, 1024, P(8), P(9), 128, hcl, relu, scratch, scratch_floats, st));
     hipLaunchKernelGGL(bbox_tail_kernel, dim3(B), dim3(256), 0, st, logits, hcl, P(10), P(11), adj, scores);
     VAD_LAUNCH_CHECK();
     return 0;
+  }
+
+  int forward(const float* x, float* scores, float* adj, float* features, hipStream_t st) {
+    float* f = features ? features : feats;
+    VAD_TRY(encoder(x, f, st));
+    return head(f, scores, adj, st);
   }
 };
 
@@ -237,6 +253,26 @@ int vad_bbox_forward(vad_bbox_plan* plan, const float* x, float* scores, float* 
   VAD_CHECK(plan && x && scores && adj, "vad_bbox_forward: null argument");
   VAD_CHECK(plan->impl.params != nullptr, "vad_bbox_forward: plan not bound");
   return plan->impl.forward(x, scores, adj, features, (hipStream_t)stream);
+}
+
+int vad_bbox_head_forward(vad_bbox_plan* plan, const float* features, float* scores, float* adj, void* stream) {
+  VAD_CHECK(plan && features && scores && adj, "vad_bbox_head_forward: null argument");
+  VAD_CHECK(plan->impl.params != nullptr, "vad_bbox_head_forward: plan not bound");
+  return plan->impl.head(features, scores, adj, (hipStream_t)stream);
+}
+
+int vad_bbox_debug_buffer(vad_bbox_plan* plan, const char* name, void** ptr, int64_t* nfloats) {
+  VAD_CHECK(plan && name && ptr && nfloats, "vad_bbox_debug_buffer: null argument");
+  VAD_CHECK(plan->impl.params != nullptr, "vad_bbox_debug_buffer: plan not bound");
+  BbPlanImpl& c = plan->impl;
+  const std::string n(name);
+  if (n == "pooled") { *ptr = c.pooled; *nfloats = c.pool_vol.numel(); }
+  else if (n == "y2") { *ptr = c.y2; *nfloats = c.g2.out().numel(); }
+  else if (n == "hc") { *ptr = c.hc; *nfloats = (int64_t)c.B * 256; }
+  else if (n == "logits") { *ptr = c.logits; *nfloats = (int64_t)c.B * 256; }
+  else if (n == "hcl") { *ptr = c.hcl; *nfloats = (int64_t)c.B * 128; }
+  else { vad::set_error("vad_bbox_debug_buffer: unknown buffer " + n); return 1; }
+  return 0;
 }
 
 }  // extern "C"

@@ -448,6 +448,15 @@ int64_t vad_bbox_workspace_bytes(const vad_bbox_plan* plan);
 int vad_bbox_bind(vad_bbox_plan* plan, void* workspace, const float* params);
 /* scores (B,), adj (B,16,16), features (B,1024, nullable) */
 int vad_bbox_forward(vad_bbox_plan* plan, const float* x, float* scores, float* adj, float* features, void* stream);
+/* Test seams.  vad_bbox_forward is encoder (x -> features) then head (features -> scores, adj);
+ * vad_bbox_head_forward runs the head alone -- the causal_net and classifier GEMMs and the sigmoid tail -- on feature
+ * rows (B, 1024) the caller chose.  vad_bbox_debug_buffer hands out the workspace arrays of the last forward:
+ * "pooled" (B, T/2, H/2, W/2, 32) NDHWC, "y2" (B, T/2, H/2, W/2, 64) NDHWC (conv2 + bias; before the ReLU, which the
+ * average pool applies on load -- on the bbox_im2col path the GEMM epilogue has applied it), "hc" (B, 256),
+ * "logits" (B, 256), "hcl" (B, 128).  Null arguments, an unbound plan or an unknown name return non-zero before
+ * anything is queued. */
+int vad_bbox_head_forward(vad_bbox_plan* plan, const float* features, float* scores, float* adj, void* stream);
+int vad_bbox_debug_buffer(vad_bbox_plan* plan, const char* name, void** ptr, int64_t* nfloats);
 
 /* ------------------------------------------------------------------------------------------
  * causal_anomaly_detection1.py — memory-bank VideoAutoEncoder (cad1:124-321) and the train_model iteration

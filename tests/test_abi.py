@@ -321,3 +321,39 @@ def test_mc_head_entry_points_refuse_before_any_launch():
         L.vad_mc_destroy(h)
     assert L.vad_mc_create(0, 1, 4, 8, 8, ctypes.byref(h)) != 0 and L.vad_mc_create(1025, 1, 4, 8, 8, ctypes.byref(h)) != 0
     assert b"unsupported shape" in L.vad_last_error()
+
+
+def test_bbox_seam_entry_points_refuse_before_any_launch():
+    """vad_bbox_head_forward / vad_bbox_debug_buffer check their arguments, the binding and the buffer name on the
+    host, before anything is queued: a refused call returns non-zero with a text and needs no device (creating a plan
+    touches none; the fake binding below is never dereferenced, because every call made on it is refused or only
+    computes an address)."""
+    from vad_amd import _native
+    L = _native.lib()
+    h = ctypes.c_void_p()
+    _native.check(L.vad_bbox_create(2, 2, 2, 2, ctypes.byref(h)))  # the smallest clip: what the seam tests run on
+    fake = ctypes.c_void_p(256)
+    p, n = ctypes.c_void_p(), ctypes.c_int64()
+    try:
+        head = lambda plan, f=fake, s=fake, a=fake: L.vad_bbox_head_forward(plan, f, s, a, None)
+        dbg = lambda plan, name=b"hc", pp=ctypes.byref(p), nn=ctypes.byref(n): L.vad_bbox_debug_buffer(plan, name, pp, nn)
+        for who, call in ((b"vad_bbox_head_forward", head), (b"vad_bbox_debug_buffer", dbg)):
+            assert call(None) != 0
+            assert who + b": null argument" in L.vad_last_error()
+            assert call(h) != 0
+            assert who + b": plan not bound" in L.vad_last_error()
+        _native.check(L.vad_bbox_bind(h, fake, fake))  # stores pointers only
+        for kw in (dict(f=None), dict(s=None), dict(a=None)):
+            assert head(h, **kw) != 0
+            assert b"vad_bbox_head_forward: null argument" in L.vad_last_error()
+        for kw in (dict(name=None), dict(pp=None), dict(nn=None)):
+            assert dbg(h, **kw) != 0
+            assert b"vad_bbox_debug_buffer: null argument" in L.vad_last_error()
+        assert dbg(h, name=b"y3") != 0
+        assert b"vad_bbox_debug_buffer: unknown buffer y3" in L.vad_last_error()
+        sizes = dict(pooled=2 * 32, y2=2 * 64, hc=2 * 256, logits=2 * 256, hcl=2 * 128)
+        for name, k in sizes.items():
+            _native.check(dbg(h, name=name.encode()))
+            assert n.value == k and p.value is not None and p.value >= 256, name
+    finally:
+        L.vad_bbox_destroy(h)

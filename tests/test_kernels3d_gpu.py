@@ -74,6 +74,7 @@ CONV_CASES = [
     (2, 32, 64, 3, 18, 22, S1, NDHWC, 3),
     (1, 32, 64, 1, 4, 4, S1, NDHWC, 3),
     (3, 32, 64, 2, 9, 33, S1, NDHWC, 3),
+    (2, 32, 64, 5, 20, 13, S1, NDHWC, 3),  # the <2, 8, 16> tile (W <= 16, H > 8): 10 frames in pairs, ragged rows
 ]
 CONV_RUNS = [(c, p) for c in CONV_CASES for p in sorted({0, c[8]})]
 CONV_IDS = ["n{}_ci{}_co{}_{}x{}x{}_s{}{}{}_path{}".format(*c[:6], *c[6], p) for c, p in CONV_RUNS]
@@ -348,6 +349,25 @@ def test_adaptive_avgpool3d(shape, bins):
     nat.check(nat.lib().vad_adaptive_avgpool3d_forward(xd.data_ptr(), None, 0, N, C, D, H, W, *bins, out.data_ptr(), st))
     torch.cuda.synchronize()
     assert _ratio(out.cpu(), ref.detach(), mag.detach(), "adaptive avgpool fwd") <= 1e-5
+    # relu = 1 (ReLU on load, no BatchNorm statistics: the bbox scorer's call) on the same input -- about half of it is
+    # negative -- and with one NaN voxel, which has to reach exactly the bins that hold it
+    out = _nan(N, C, *bins)
+    nat.check(nat.lib().vad_adaptive_avgpool3d_forward(xd.data_ptr(), None, 1, N, C, D, H, W, *bins, out.data_ptr(), st))
+    torch.cuda.synchronize()
+    assert float((x < 0).float().mean()) > 0.3
+    rref = F.adaptive_avg_pool3d(F.relu(x.double()), bins)
+    assert _ratio(out.cpu(), rref, rref, "adaptive avgpool fwd relu") <= 1e-5
+    xn = x.clone()
+    xn[N - 1, C // 2, D // 2, H // 2, W // 2] = float("nan")
+    want = torch.isnan(F.adaptive_avg_pool3d(F.relu(xn.double()), bins))
+    assert 1 <= int(want.sum()) < want.numel()
+    out = _nan(N, C, *bins)
+    nat.check(nat.lib().vad_adaptive_avgpool3d_forward(_dev(_to_ndhwc(xn)).data_ptr(), None, 1, N, C, D, H, W, *bins,
+                                                       out.data_ptr(), st))
+    torch.cuda.synchronize()
+    got = out.cpu()
+    assert torch.equal(torch.isnan(got), want), "relu = 1: the NaN voxel's bins"
+    assert bool(((got.double() - rref).abs()[~want] <= 1e-5 * rref[~want]).all()), "relu = 1: the bins without the NaN"
     dd = _dev(dout)
     for gated in (0, 1):
         gd = _dev(_to_ndhwc(gate)) if gated else None
