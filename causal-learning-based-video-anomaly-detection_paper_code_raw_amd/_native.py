@@ -180,6 +180,9 @@ _SIGS = {
     "vad_ae_ring_offset": (_I64, [_I64, _I]),
     "vad_ae_frames_forward_ring": (_I, [_P, _P, _I64, _P, _I64, _P]),
     "vad_ae_windows_forward_ring": (_I, [_P, _P, _I64, _I, _I, _I64, _I, _P, _P, _P, _P, _P, _P]),
+    "vad_ae_group_table_bytes": (_I64, [_I64, _I64]),
+    "vad_ae_frames_forward_group": (_I, [_P, _P, _I64, _P, _P, _P, _P]),
+    "vad_ae_windows_forward_group": (_I, [_P, _P, _I64, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vad_ae_update_memory": (_I, [_P, _P, _P, _I, _P]),
     "vad_ae_memory_score": (_I, [_P, _P, _P, _I, _P, _P]),
     "vad_a2_set_option": (_I, [_P, ctypes.c_char_p, _I64]),

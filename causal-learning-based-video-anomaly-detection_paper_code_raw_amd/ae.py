@@ -150,6 +150,17 @@ class VideoAutoEncoder(nn.Module):
         from .ae_stream import AeStream
         return AeStream(self, window, stride, max_push=max_push, return_reconstructions=return_reconstructions)
 
+    def open_stream_group(self, num_streams, window=16, stride=1, *, max_push=1, return_reconstructions=False):
+        """Eval-mode scoring of num_streams live streams on shared launches (ae_stream_group.py):
+        ``g = model.open_stream_group(S, ...)``, then ``g.push([frames_0, ..., frames_{S-1}])`` -- entry s the next
+        0 <= k_s <= max_push frames (k_s, 1, 64, 64) of stream s, or None -- returns S dicts, dict s what
+        ``open_stream(window, stride, max_push=max_push, return_reconstructions=...).push(frames_s)`` returns on the
+        same history of frames, from one per-frame pass and one per-window pass over all streams.  num_streams *
+        max_push may be at most memory_size.  Changes nothing in the model."""
+        from .ae_stream_group import AeStreamGroup
+        return AeStreamGroup(self, num_streams, window, stride, max_push=max_push,
+                             return_reconstructions=return_reconstructions)
+
     def forward(self, frames):
         x = _clip_input(frames)
         e = self.engine()

@@ -31,7 +31,9 @@
 //             encoder and the LSTM input projection once per frame into a frame cache, then per window the
 //             recurrence over cached rows (the LSTM kernel's WIN instantiation), ring score, one decoder call and
 //             the error against the window's T frames; a live stream keeps the per-frame results and the frames in a
-//             ring of cap slots (vad_ae_frames_forward_ring / vad_ae_windows_forward_ring), frame g in slot g mod cap
+//             ring of cap slots (vad_ae_frames_forward_ring / vad_ae_windows_forward_ring), frame g in slot g mod cap;
+//             a group of streams keeps many such rings in one allocation and scores them on shared launches, each
+//             block addressed through a host-validated table (vad_ae_frames_forward_group / _windows_forward_group)
 // Status word (losses[3]): 0 = skipped before backward (train-loop mode: a non-finite input, cad1:385-387 -- the BN
 // running stats, counters and the memory ring stay untouched, as the reference's `continue` before the forward -- or
 // a non-finite loss), 1 = non-finite grads, no step, 2 = stepped.
@@ -78,6 +80,9 @@ struct AeRing {
       : lat(0), gx(cap * AE_LAT), pix(cap * (AE_LAT + AE_GATES)), total(cap * (AE_LAT + AE_GATES + AE_PIX)) {}
 };
 constexpr int64_t AE_RING_MAX = 1ll << 24;  // slots: slot arithmetic in the kernels stays in int
+// How the per-window stage addresses its frames: rows of a frame cache, slots of one ring, or -- a group of streams --
+// slots of many rings of cap slots in one AeRing(total_slots), through a window table
+enum class AeWindows { Linear, Ring, Group };
 
 // model.named_parameters() and BN running-stat order (cad1:129-188)
 struct AeLayout : FlatLayout {
@@ -169,15 +174,24 @@ __global__ __launch_bounds__(256) void ae_frames_kernel(const float* __restrict_
 
 // Ring store of a (B = k, T = 1) plan's per-frame results: block f copies row f of lat [k][64], gx [k][256] and xf
 // [k][4096] to slot s0 + f of the ring's arrays, less cap once if it passes the end (s0 = f0 mod cap, reduced on the
-// host; k <= cap), so a chunk may straddle the wrap.  float4 copies, no division.
+// host; k <= cap), so a chunk may straddle the wrap.  float4 copies, no division.  TABLE (a group of streams: the three
+// arrays hold many rings): block f stores to the absolute slot table[f], or, where that is < 0 (a padding frame),
+// returns before any load; table[f] is block-uniform, so it is one scalar load.  The host validated the table
+// (below): the kernel checks nothing.
+template <bool TABLE = false>
 __global__ __launch_bounds__(256) void ae_ring_store_kernel(const float* __restrict__ lat,
                                                             const float* __restrict__ gx,
                                                             const float* __restrict__ xf, int s0, int cap,
                                                             float* __restrict__ rlat, float* __restrict__ rgx,
-                                                            float* __restrict__ rpix) {
+                                                            float* __restrict__ rpix, const int* __restrict__ table) {
   const int f = blockIdx.x, t = threadIdx.x;
   int slot = s0 + f;
-  if (slot >= cap) slot -= cap;
+  if constexpr (TABLE) {
+    slot = table[f];
+    if (slot < 0) return;
+  } else {
+    if (slot >= cap) slot -= cap;
+  }
   if (t < AE_LAT / 4)
     reinterpret_cast<f32x4*>(rlat + (int64_t)slot * AE_LAT)[t] =
         reinterpret_cast<const f32x4*>(lat + (int64_t)f * AE_LAT)[t];
@@ -575,17 +589,22 @@ __global__ __launch_bounds__(256) void ae_add_kernel(float* __restrict__ a, cons
 // and stores nothing but the sequence feature.  The ring form (WIN and RING, a live stream) reads the gx array of a
 // ring of cap slots: the block reduces its first slot s0 = (first + b*stride) mod cap once (first: already mod cap),
 // and the row of step t -- the look-ahead row t + AE_PF of the prefetch too -- is s0 + t, less cap where it reaches
-// it (T <= cap: one block-uniform conditional subtract, no division in the recurrence).  All forms run the same
-// floating-point instructions per step.
+// it (T <= cap: one block-uniform conditional subtract, no division in the recurrence).  The group form (GROUP, with
+// RING: many rings of cap slots in one gx array) reads its block's entry (base_b, s0_b) of the window table once,
+// before the recurrence -- its address depends on blockIdx alone, so both are scalar loads and stay in scalar
+// registers -- offsets gx by base_b rows and then is the ring form on a ring that starts there.  All forms run the
+// same floating-point instructions per step.
 constexpr int AE_PF = 4;
 
-template <bool WIN, bool RING = false>
+template <bool WIN, bool RING = false, bool GROUP = false>
 __device__ __forceinline__ void ae_lstm_fwd_body(const float* __restrict__ gx, const float* __restrict__ whh,
                                                  const float* __restrict__ bhh, int B, int T, int stride,
                                                  int64_t first, int cap, float* __restrict__ gates,
                                                  float* __restrict__ cs, float* __restrict__ hprev,
-                                                 float* __restrict__ seq, float* __restrict__ seq_out) {
+                                                 float* __restrict__ seq, float* __restrict__ seq_out,
+                                                 const int64_t* __restrict__ tab = nullptr) {
   static_assert(WIN || !RING, "the ring form is a windowed form");
+  static_assert(RING || !GROUP, "the group form addresses rings");
   __shared__ float h[AE_LAT], act[AE_GATES];
   const int b = blockIdx.x, j = threadIdx.x;
   float w[AE_LAT];
@@ -625,7 +644,11 @@ __device__ __forceinline__ void ae_lstm_fwd_body(const float* __restrict__ gx, c
     // the input projection of step t: frame (w0 + b) * stride + t of the cache, or its slot of the ring
     const float* row;
     int s0 = 0;
-    if constexpr (RING) {
+    if constexpr (GROUP) {
+      const int64_t* e = tab + 2 * (int64_t)b;
+      row = gx + e[0] * AE_GATES + j;
+      s0 = (int)e[1];
+    } else if constexpr (RING) {
       row = gx + j;
       s0 = (int)(((unsigned)first + (unsigned)b * (unsigned)stride) % (unsigned)cap);
     } else {
@@ -688,6 +711,17 @@ __global__ __launch_bounds__(256) void ae_lstm_ring_kernel(const float* __restri
                                                            const float* __restrict__ bhh, int T, int stride,
                                                            int first, int cap, float* __restrict__ seq_out) {
   ae_lstm_fwd_body<true, true>(gx, whh, bhh, 0, T, stride, first, cap, nullptr, nullptr, nullptr, nullptr, seq_out);
+}
+
+// window i of the launch = slots tab[2i] + (tab[2i + 1] + t, less cap where it reaches it), t < T, of an array of many
+// rings of cap slots (gx: that array; tab: the validated window table on the device; T <= cap)
+__global__ __launch_bounds__(256) void ae_lstm_group_kernel(const float* __restrict__ gx,
+                                                            const float* __restrict__ whh,
+                                                            const float* __restrict__ bhh, int T, int cap,
+                                                            const int64_t* __restrict__ tab,
+                                                            float* __restrict__ seq_out) {
+  ae_lstm_fwd_body<true, true, true>(gx, whh, bhh, 0, T, 1, 0, cap, nullptr, nullptr, nullptr, nullptr, seq_out,
+                                     tab);
 }
 
 // BPTT, one block per clip in reverse time: thread (q, k) holds column k of W_hh rows [64q, 64q + 64) for
@@ -801,19 +835,28 @@ __global__ __launch_bounds__(256) void ae_loss_finalize_kernel(const float* __re
 // ae_loss_kernel's order (fmaf(d, d, sq) over t ascending, the same LDS tree).  recon (nullable) [windows][4096]: r
 // once per window.  RING (a live stream): frames is the ring's pix array of cap slots -- the plan's xf rows, NaN -> 0
 // already, so nan0 is the identity there and the sums are those of the linear form on the caller's frames -- first is
-// reduced mod cap on the host and the row of step t is s0 + t, less cap where it reaches it (T <= cap).
-template <bool RING>
+// reduced mod cap on the host and the row of step t is s0 + t, less cap where it reaches it (T <= cap).  GROUP (with
+// RING: frames is the pix array of many rings of cap slots): the block reads its window's entry (base, s0) of the
+// window table once, ahead of the loop (block-uniform: scalar loads), offsets frames by base rows and then is the ring
+// form; the sum and the tree are the same.
+template <bool RING, bool GROUP = false>
 __global__ __launch_bounds__(256) void ae_win_loss_kernel(const float* __restrict__ y3,
                                                           const float* __restrict__ frames, int T, int stride,
                                                           int64_t first, int cap, float* __restrict__ recon,
-                                                          float* __restrict__ part) {
+                                                          float* __restrict__ part,
+                                                          const int64_t* __restrict__ tab) {
+  static_assert(RING || !GROUP, "the group form addresses rings");
   __shared__ float red[256];
   const int b = blockIdx.x / AE_CHUNKS, p = (blockIdx.x % AE_CHUNKS) * 256 + threadIdx.x;
   const float r0 = 1.f / (1.f + expf(-y3[(int64_t)b * AE_PIX + p]));
   const float r = r0 != r0 ? 0.f : r0;
   const float* x;
   int s0 = 0;
-  if constexpr (RING) {
+  if constexpr (GROUP) {
+    const int64_t* e = tab + 2 * (int64_t)b;
+    x = frames + e[0] * AE_PIX + p;
+    s0 = (int)e[1];
+  } else if constexpr (RING) {
     x = frames + p;
     s0 = (int)(((unsigned)first + (unsigned)b * (unsigned)stride) % (unsigned)cap);
   } else {
@@ -1261,23 +1304,44 @@ struct AePlanImpl {
     loss_mode = 0;
     have_fwd = 0;  // the encoder activations of an earlier forward are gone
     VAD_TRY(encode(frames_chunk, false, nullptr, lat, gx, nullptr, st));
-    hipLaunchKernelGGL(ae_ring_store_kernel, dim3(NF), dim3(256), 0, st, lat, gx, xf, (int)(f0 % cap), (int)cap,
-                       ring + R.lat, ring + R.gx, ring + R.pix);
+    hipLaunchKernelGGL(ae_ring_store_kernel<false>, dim3(NF), dim3(256), 0, st, lat, gx, xf, (int)(f0 % cap),
+                       (int)cap, ring + R.lat, ring + R.gx, ring + R.pix, (const int*)nullptr);
+    VAD_LAUNCH_CHECK();
+    return 0;
+  }
+
+  // The same for a group of streams: ring is AeRing(total_slots) and frame f goes to slot dst[f] of it, or nowhere
+  // (dst: the validated destinations on the device)
+  int frames_forward_group(const float* frames_chunk, float* ring, int64_t total_slots, const int* dst,
+                           hipStream_t st) {
+    const AeRing R(total_slots);
+    training = 0;
+    loss_mode = 0;
+    have_fwd = 0;  // the encoder activations of an earlier forward are gone
+    VAD_TRY(encode(frames_chunk, false, nullptr, lat, gx, nullptr, st));
+    hipLaunchKernelGGL(ae_ring_store_kernel<true>, dim3(NF), dim3(256), 0, st, lat, gx, xf, 0, 0, ring + R.lat,
+                       ring + R.gx, ring + R.pix, dst);
     VAD_LAUNCH_CHECK();
     return 0;
   }
 
   // per-window stage for nw <= B windows, window i = frames first + i*stride + t: recurrence over the cached rows, ring
-  // score, one decoder call per window, its error against the window's T frames, the blend.  ring: cache is a ring of
-  // nframes slots that holds the frames too (frames is not read)
-  int windows_forward(const float* cache, const float* frames, int64_t nframes, bool ring, int T_, int stride,
+  // score, one decoder call per window, its error against the window's T frames, the blend.  Ring: cache is a ring of
+  // nframes slots that holds the frames too (frames is not read).  Group: cache is AeRing(nframes) holding nframes /
+  // cap rings of cap slots, and window i is row i of tab (base, first slot; validated, on the device) -- stride and
+  // first are not read
+  int windows_forward(const float* cache, const float* frames, int64_t nframes, AeWindows mode, int T_, int stride,
                       int64_t first, int nw, float* seq_out, float* recon_err, float* mem_score, float* score,
-                      float* recon, hipStream_t st) {
+                      float* recon, hipStream_t st, const int64_t* tab = nullptr, int cap = 0) {
     const AeLayout& L = ae_layout();
+    const int64_t* no_tab = nullptr;
     training = 0;
     loss_mode = 0;
     have_fwd = 0;  // the decoder activations of an earlier forward are gone
-    if (ring) {
+    if (mode == AeWindows::Group) {
+      hipLaunchKernelGGL(ae_lstm_group_kernel, dim3(nw), dim3(AE_GATES), 0, st, cache + AeRing(nframes).gx, P(L.whh),
+                         P(L.bhh), T_, cap, tab, seq_out);
+    } else if (mode == AeWindows::Ring) {
       hipLaunchKernelGGL(ae_lstm_ring_kernel, dim3(nw), dim3(AE_GATES), 0, st, cache + AeRing(nframes).gx, P(L.whh),
                          P(L.bhh), T_, stride, (int)(first % nframes), (int)nframes, seq_out);
     } else {
@@ -1288,12 +1352,15 @@ struct AePlanImpl {
     hipLaunchKernelGGL(ae_memory_score_kernel, dim3(nw), dim3(256), 0, st, memory, mptr, seq_out, mem_score);
     VAD_LAUNCH_CHECK();
     VAD_TRY(decode(seq_out, nw, false, nullptr, st));
-    if (ring) {
+    if (mode == AeWindows::Group) {
+      hipLaunchKernelGGL((ae_win_loss_kernel<true, true>), dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3],
+                         cache + AeRing(nframes).pix, T_, 1, (int64_t)0, cap, recon, lpart, tab);
+    } else if (mode == AeWindows::Ring) {
       hipLaunchKernelGGL(ae_win_loss_kernel<true>, dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3],
-                         cache + AeRing(nframes).pix, T_, stride, first % nframes, (int)nframes, recon, lpart);
+                         cache + AeRing(nframes).pix, T_, stride, first % nframes, (int)nframes, recon, lpart, no_tab);
     } else {
       hipLaunchKernelGGL(ae_win_loss_kernel<false>, dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3], frames, T_, stride,
-                         first, 0, recon, lpart);
+                         first, 0, recon, lpart, no_tab);
     }
     VAD_LAUNCH_CHECK();
     hipLaunchKernelGGL(ae_win_finalize_kernel, dim3((unsigned)cdiv(nw, 256)), dim3(256), 0, st, lpart, nw, T_,
@@ -1574,8 +1641,8 @@ int vad_ae_windows_forward(vad_ae_plan* plan, const float* cache, const float* f
   VAD_CHECK(nw >= 1 && nw <= c.B, "vad_ae_windows_forward: nw must be in 1..B of the plan (its per-clip buffers)");
   VAD_CHECK(w0 >= 0 && w0 <= (nframes - T) / stride && nw - 1 <= (nframes - T) / stride - w0,
             "vad_ae_windows_forward: w0 .. w0 + nw - 1 reach outside the video");
-  return c.windows_forward(cache, frames, nframes, false, T, stride, w0 * stride, nw, seq, recon_err, mem_score,
-                           score, recon, (hipStream_t)stream);
+  return c.windows_forward(cache, frames, nframes, AeWindows::Linear, T, stride, w0 * stride, nw, seq, recon_err,
+                           mem_score, score, recon, (hipStream_t)stream);
 }
 
 int64_t vad_ae_ring_floats(int64_t cap) {
@@ -1630,8 +1697,96 @@ int vad_ae_windows_forward_ring(vad_ae_plan* plan, const float* ring, int64_t ca
             "vad_ae_windows_forward_ring: nw must be in 1..B of the plan (its per-clip buffers)");
   VAD_CHECK((int64_t)(nw - 1) * stride + T <= cap,
             "vad_ae_windows_forward_ring: the span (nw - 1) * stride + T of the batch exceeds cap");
-  return c.windows_forward(ring, nullptr, cap, true, T, stride, first_frame, nw, seq, recon_err, mem_score, score,
-                           recon, (hipStream_t)stream);
+  return c.windows_forward(ring, nullptr, cap, AeWindows::Ring, T, stride, first_frame, nw, seq, recon_err, mem_score,
+                           score, recon, (hipStream_t)stream);
+}
+
+// A group of streams.  The device table of one push: the plan's B destination slots (int32) from byte 0, the window
+// rows (2 int64 each: base, first) from the next multiple of 16 bytes.  Both calls validate their host table entry by
+// entry before anything is queued: the kernels trust what they read.
+static int64_t ae_group_window_table_offset(int64_t nf) { return (nf * 4 + 15) & ~15ll; }
+
+int64_t vad_ae_group_table_bytes(int64_t nf, int64_t nw) {
+  if (nf < 1 || nw < 0 || nf > (1ll << 31) || nw > (1ll << 31)) {
+    vad::set_error("vad_ae_group_table_bytes: nf must be >= 1 and nw >= 0");
+    return -1;
+  }
+  return ae_group_window_table_offset(nf) + nw * 16;
+}
+
+int vad_ae_frames_forward_group(vad_ae_plan* plan, const float* frames_chunk, int64_t total_slots, float* ring,
+                                const int32_t* host_dst, void* dev_table, void* stream) {
+  VAD_CHECK(plan != nullptr, "vad_ae_frames_forward_group: null plan");
+  AePlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_ae_frames_forward_group: plan not bound");
+  VAD_CHECK(c.T == 1, "vad_ae_frames_forward_group: needs a plan created as (B = frames per push, T = 1)");
+  VAD_CHECK(frames_chunk && (reinterpret_cast<uintptr_t>(frames_chunk) & 15) == 0,
+            "vad_ae_frames_forward_group: frames_chunk must be a 16-byte aligned device pointer");
+  VAD_CHECK(ring && (reinterpret_cast<uintptr_t>(ring) & 15) == 0,
+            "vad_ae_frames_forward_group: ring must be a 16-byte aligned device pointer");
+  VAD_CHECK(host_dst != nullptr, "vad_ae_frames_forward_group: null table (host_dst)");
+  VAD_CHECK(dev_table && (reinterpret_cast<uintptr_t>(dev_table) & 15) == 0,
+            "vad_ae_frames_forward_group: dev_table must be a 16-byte aligned device pointer");
+  VAD_CHECK(total_slots >= 1 && total_slots <= AE_RING_MAX,
+            "vad_ae_frames_forward_group: total_slots must be in 1..2^24");
+  std::vector<int32_t> seen;
+  for (int f = 0; f < c.NF; ++f) {
+    const int32_t d = host_dst[f];
+    if (d < -1 || d >= total_slots) {
+      vad::set_error("vad_ae_frames_forward_group: dst[" + std::to_string(f) + "] = " + std::to_string(d) +
+                     " is outside -1 .. total_slots - 1 = " + std::to_string(total_slots - 1));
+      return 1;
+    }
+    if (d >= 0) seen.push_back(d);
+  }
+  std::sort(seen.begin(), seen.end());
+  for (size_t i = 1; i < seen.size(); ++i)
+    if (seen[i] == seen[i - 1]) {
+      vad::set_error("vad_ae_frames_forward_group: two entries of dst name slot " + std::to_string(seen[i]));
+      return 1;
+    }
+  VAD_HIP(hipMemcpyAsync(dev_table, host_dst, (size_t)c.NF * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+  return c.frames_forward_group(frames_chunk, ring, total_slots, static_cast<const int*>(dev_table),
+                                (hipStream_t)stream);
+}
+
+int vad_ae_windows_forward_group(vad_ae_plan* plan, const float* ring, int64_t total_slots, int cap, int T,
+                                 const int64_t* host_windows, int nw, void* dev_table, float* seq, float* recon_err,
+                                 float* mem_score, float* score, float* recon, void* stream) {
+  VAD_CHECK(plan != nullptr, "vad_ae_windows_forward_group: null plan");
+  AePlanImpl& c = plan->impl;
+  VAD_CHECK(c.params != nullptr, "vad_ae_windows_forward_group: plan not bound");
+  VAD_CHECK(c.T == 1, "vad_ae_windows_forward_group: needs a plan created as (B = frames per push, T = 1)");
+  VAD_CHECK(ring && (reinterpret_cast<uintptr_t>(ring) & 15) == 0,
+            "vad_ae_windows_forward_group: ring must be a 16-byte aligned device pointer");
+  VAD_CHECK(host_windows != nullptr, "vad_ae_windows_forward_group: null table (host_windows)");
+  VAD_CHECK(dev_table && (reinterpret_cast<uintptr_t>(dev_table) & 15) == 0,
+            "vad_ae_windows_forward_group: dev_table must be a 16-byte aligned device pointer");
+  VAD_CHECK(seq && recon_err && mem_score && score && (reinterpret_cast<uintptr_t>(seq) & 15) == 0,
+            "vad_ae_windows_forward_group: seq (16-byte aligned), recon_err, mem_score and score must not be null");
+  VAD_CHECK(cap >= 1, "vad_ae_windows_forward_group: cap must be >= 1");
+  VAD_CHECK(total_slots >= 1 && total_slots <= AE_RING_MAX && total_slots % cap == 0,
+            "vad_ae_windows_forward_group: total_slots must be in 1..2^24 and a multiple of cap");
+  VAD_CHECK(T >= 1 && T <= cap, "vad_ae_windows_forward_group: T must be in 1..cap");
+  VAD_CHECK(T <= 4096, "vad_ae_windows_forward_group: T must be at most 4096");
+  VAD_CHECK(nw >= 1 && nw <= c.B,
+            "vad_ae_windows_forward_group: nw must be in 1..B of the plan (its per-clip buffers)");
+  for (int i = 0; i < nw; ++i) {
+    const int64_t base = host_windows[2 * i], s0 = host_windows[2 * i + 1];
+    const char* what = nullptr;
+    if (base < 0 || base % cap != 0) what = "base must be a non-negative multiple of cap";
+    else if (base + cap > total_slots) what = "base + cap exceeds total_slots";
+    else if (s0 < 0 || s0 >= cap) what = "first must be in 0..cap - 1";
+    if (what) {
+      vad::set_error("vad_ae_windows_forward_group: window " + std::to_string(i) + " (base " + std::to_string(base) +
+                     ", first " + std::to_string(s0) + "): " + what);
+      return 1;
+    }
+  }
+  int64_t* tab = reinterpret_cast<int64_t*>(static_cast<char*>(dev_table) + ae_group_window_table_offset(c.NF));
+  VAD_HIP(hipMemcpyAsync(tab, host_windows, (size_t)nw * 16, hipMemcpyHostToDevice, (hipStream_t)stream));
+  return c.windows_forward(ring, nullptr, total_slots, AeWindows::Group, T, 1, 0, nw, seq, recon_err, mem_score, score,
+                           recon, (hipStream_t)stream, tab, cap);
 }
 
 int vad_ae_debug_buffer(vad_ae_plan* plan, const char* name, int idx, void** ptr, int64_t* nfloats) {

@@ -557,6 +557,34 @@ int vad_ae_frames_forward_ring(vad_ae_plan* plan, const float* frames_chunk, int
 int vad_ae_windows_forward_ring(vad_ae_plan* plan, const float* ring, int64_t cap, int T, int stride,
                                 int64_t first_frame, int nw, float* seq, float* recon_err, float* mem_score,
                                 float* score, float* recon, void* stream);
+/* The same two stages for a group of streams that share launches: one ring allocation of total_slots slots (the
+ * layout of vad_ae_ring_floats(total_slots) / vad_ae_ring_offset(total_slots, field)) holding total_slots / cap rings
+ * of cap slots, ring s in slots s*cap .. (s+1)*cap - 1 of each of the three arrays.  Which slot a frame goes to and
+ * which slots a window reads come from tables the caller passes as HOST pointers.  Each call validates its table entry
+ * by entry on the host -- a violation returns non-zero, names the argument or the entry in vad_last_error and launches
+ * nothing, so a bad table cannot cause a store or a load outside the ring -- and then copies it with one
+ * hipMemcpyAsync on `stream` into dev_table, which the kernels read.  dev_table is caller-owned device memory, 16-byte
+ * aligned, of at least vad_ae_group_table_bytes(B of the frames plan, nw) bytes (the destinations from byte 0, the
+ * window rows after them; -1 on a bad argument); the library still owns no device memory.  The caller must not reuse
+ * dev_table while an earlier call on ANOTHER stream may still read it; calls on one stream are ordered by the stream.
+ * A pageable host table may be changed as soon as the call returns; a pinned one only once `stream` has passed the
+ * copy. */
+int64_t vad_ae_group_table_bytes(int64_t nf, int64_t nw);
+/* vad_ae_frames_forward_ring on a (B, T = 1) plan's B frames, frame f stored to slot host_dst[f] of the three arrays,
+ * or nowhere where host_dst[f] is -1 (a padding frame: it is encoded, nothing of it is kept).  A null or unbound plan,
+ * a plan with T != 1, a null or misaligned pointer, total_slots outside 1..2^24, a host_dst[f] outside
+ * -1 .. total_slots - 1 or two entries >= 0 that are equal is an error as above. */
+int vad_ae_frames_forward_group(vad_ae_plan* plan, const float* frames_chunk, int64_t total_slots, float* ring,
+                                const int32_t* host_dst, void* dev_table, void* stream);
+/* vad_ae_windows_forward_ring for nw windows that may lie in different rings: host_windows holds two int64 per window,
+ * (base, first) -- the window's frame t is slot base + ((first + t) wrapped once at cap) -- and row i of every output
+ * equals vad_ae_forward(training = 0, loss_mode = 1) on that clip (outputs as vad_ae_windows_forward).  total_slots
+ * must lie in 1..2^24 and be a multiple of cap, base must be a multiple of cap with base + cap <= total_slots,
+ * 0 <= first < cap, 1 <= T <= cap, T <= 4096 and 1 <= nw <= the plan's B; the plan and the pointers as above.
+ * dev_table is the one of the frames call on the same plan (the window rows lie after that plan's B destinations). */
+int vad_ae_windows_forward_group(vad_ae_plan* plan, const float* ring, int64_t total_slots, int cap, int T,
+                                 const int64_t* host_windows, int nw, void* dev_table, float* seq, float* recon_err,
+                                 float* mem_score, float* score, float* recon, void* stream);
 /* the memory ring of any VideoAutoEncoder: update_memory (cad1:201-219; n <= 500 features (n, 64)) and
  * compute_anomaly_score (cad1:262-301; n sequence features -> scores (n,)) */
 /* test access to the last forward's pre-activations (the gradient tests pin their LeakyReLU decisions): "ey" idx l:
