@@ -72,6 +72,9 @@ _SIGS = {
     "vad_u8_to_clip": (_I, [_P, _I64, _I, _P, _P]),
     "vad_host_device_ptr": (_I, [_P, _P]),
     "vad_resize_u8": (_I, [_P, _I, _I, _P, _I, _I]),
+    "vad_ingest_u8": (_I, [_P, _I64, _I, _I, _I64, _I64, _I, _I, _I, _P, _P]),
+    "vad_ingest_table_bytes": (_I64, [_I64]),
+    "vad_ingest_u8_table": (_I, [_P, _I64, _I, _I, _I, _P, _P, _P]),
     "vad_debug_d2h": (_I, [_P, _P, _I64]),
     "vad_cad_profile": (_I, [_P, _I, ctypes.c_char_p]),
     "vad_cad_profile_read": (_I, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I), _I]),

@@ -146,7 +146,10 @@ class VideoAutoEncoder(nn.Module):
         with the next 1 <= k <= max_push frames (k, 1, 64, 64) or (1, k, 1, 64, 64) returns score_video's keys for
         exactly the windows those frames complete ('window_starts' absolute from the stream's first frame,
         'frame_features' (k, 64) of the pushed frames), equal to score_video on the same frames in any chunking of
-        the pushes.  Memory is a ring of window + max_push - 1 frames.  Changes nothing in the model."""
+        the pushes.  Memory is a ring of window + max_push - 1 frames.  Changes nothing in the model.
+        ``s.push_u8(frames)`` takes the k frames as uint8 (k, Hs, Ws) or (k, 1, Hs, Ws) at the source's own size, on
+        the device or in host memory: one launch resizes them to 64x64 (data.resize_u8's bilinear) and normalises
+        them as the dataset does (u8 / 255 clamped to 0.001..0.999, cad1:110-114), then push's body runs."""
         from .ae_stream import AeStream
         return AeStream(self, window, stride, max_push=max_push, return_reconstructions=return_reconstructions)
 
@@ -156,7 +159,9 @@ class VideoAutoEncoder(nn.Module):
         0 <= k_s <= max_push frames (k_s, 1, 64, 64) of stream s, or None -- returns S dicts, dict s what
         ``open_stream(window, stride, max_push=max_push, return_reconstructions=...).push(frames_s)`` returns on the
         same history of frames, from one per-frame pass and one per-window pass over all streams.  num_streams *
-        max_push may be at most memory_size.  Changes nothing in the model."""
+        max_push may be at most memory_size.  Changes nothing in the model.  ``g.push_u8(frames)`` takes uint8 frames
+        (k_s, Hs, Ws) or (k_s, 1, Hs, Ws) instead, every camera at its own source size, on the device or in host
+        memory: one launch resizes, normalises (as open_stream's push_u8) and pads them, then push's body runs."""
         from .ae_stream_group import AeStreamGroup
         return AeStreamGroup(self, num_streams, window, stride, max_push=max_push,
                              return_reconstructions=return_reconstructions)

@@ -18,7 +18,7 @@ import torch
 
 from . import _native as nat
 from .ae_video import HW, LATENT
-from .stream import _positive_int, stream_schedule
+from .stream import _positive_int, check_push_u8, stream_schedule
 
 _RING_FIELDS = {"lat": (0, LATENT), "gx": (1, 4 * LATENT), "pix": (2, HW * HW)}
 
@@ -76,6 +76,7 @@ class AeStream:
         self.return_reconstructions = bool(return_reconstructions)
         self.cap = self.window + self.max_push - 1
         self._ring = None
+        self._ingest = self._u8 = None  # push_u8's U8Ingest and its fp32 buffer of max_push frames
         self.frames_seen = 0
         self.windows_emitted = 0
 
@@ -88,7 +89,25 @@ class AeStream:
         """frames: (k, 1, 64, 64) or (1, k, 1, 64, 64) on the device, 1 <= k <= max_push.  Encodes them and scores
         every window they complete; returns score_video's keys for exactly those windows (window_starts absolute;
         frame_features: the k pushed frames, a copy; empty tensors when no window completes)."""
-        x = check_push(self.model, frames, self.max_push)
+        return self._push(check_push(self.model, frames, self.max_push))
+
+    def push_u8(self, frames) -> dict:
+        """frames: the next 1 <= k <= max_push frames as uint8 (k, Hs, Ws) or (k, 1, Hs, Ws) at any source size, on
+        the device, in pinned host memory (read in place) or in pageable host memory.  One launch resizes them to
+        64x64 as data.resize_u8 does and normalises them as the reference's dataset does, u8 / 255 clamped to
+        0.001..0.999 (cad1:110-114), into a buffer the stream owns (data.U8Ingest); the rest is push: push_u8(u8)
+        returns what push returns for the same frames converted on the host."""
+        from .data import U8Ingest, ingest_device
+        check_model(self.model)
+        x = check_push_u8(self.model, frames, self.max_push)
+        dev = ingest_device(self.model, [x], "push_u8")
+        if self._ingest is None:
+            self._ingest = U8Ingest(dev)
+            self._u8 = torch.empty(self.max_push, 1, HW, HW, dtype=torch.float32, device=dev)
+        return self._push(self._ingest.ingest(x, (HW, HW), 2, out=self._u8[:x.shape[0]]))
+
+    def _push(self, x) -> dict:
+        """push's body: x (k, 1, 64, 64), checked."""
         T, stride, cap = self.window, self.stride, self.cap
         nat.require_hip(x)
         eng = self.model.engine()

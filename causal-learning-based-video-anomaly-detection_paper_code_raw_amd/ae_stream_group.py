@@ -27,7 +27,7 @@ from . import _native as nat
 from .ae_stream import check_model, ring_field
 from .ae_video import HW, LATENT
 from .stream import _positive_int, stream_schedule
-from .stream_group import group_schedule, padded_frames
+from .stream_group import check_group_push_u8, group_schedule, padded_frames
 
 
 def check_group_push(model, frames, num_streams, max_push):
@@ -81,6 +81,7 @@ class AeStreamGroup:
         self.cap = self.window + self.max_push - 1
         self.total_slots = self.num_streams * self.cap
         self._ring = None
+        self._ingest = self._u8 = None  # push_u8's U8Ingest and its fp32 buffer of max_frames frames
         self.frames_seen = [0] * self.num_streams
         self.windows_emitted = [0] * self.num_streams
 
@@ -111,10 +112,39 @@ class AeStreamGroup:
         (k_s, 1, 64, 64) on the device, or None.  Returns one AeStream.push dict per stream: empty tensors where the
         stream completed no window, frame_features (0, 64) where it pushed nothing."""
         chunks, ks = check_group_push(self.model, frames, self.num_streams, self.max_push)
-        T, stride, cap, S = self.window, self.stride, self.cap, self.num_streams
         live = [x for x in chunks if x is not None]
         for x in live:
             nat.require_hip(x)
+        F = sum(ks)
+        P = padded_frames(F, self.max_frames)
+        # the frames of all streams and the padding, in one copy
+        parts = [x.to(torch.float32) for x in live]
+        if P > F:
+            parts.append(torch.zeros(P - F, 1, HW, HW, dtype=torch.float32, device=live[0].device))
+        x = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
+        return self._push(x, ks)
+
+    def push_u8(self, frames) -> list:
+        """frames: a sequence of num_streams entries, entry s the next 0 <= k_s <= max_push frames of camera s as uint8
+        (k_s, Hs, Ws) or (k_s, 1, Hs, Ws), or None; cameras may differ in source size and in where their frames lie
+        (device, pinned host memory read in place, pageable host memory).  One table-form launch resizes every frame
+        to 64x64 as data.resize_u8 does, normalises it as u8 / 255 clamped to 0.001..0.999 (cad1:110-114) and writes
+        the zero padding, into a buffer the group owns (data.U8Ingest.table); the rest is push: push_u8 returns what
+        push returns for the same frames converted on the host."""
+        from .data import U8Ingest, ingest_device
+        chunks, ks = check_group_push_u8(self.model, frames, self.num_streams, self.max_push, check_model)
+        live = [x for x in chunks if x is not None]
+        dev = ingest_device(self.model, live, "push_u8")
+        if self._ingest is None:
+            self._ingest = U8Ingest(dev)
+            self._u8 = torch.empty(self.max_frames, 1, HW, HW, dtype=torch.float32, device=dev)
+        P = padded_frames(sum(ks), self.max_frames)
+        x = self._ingest.table(live, P, (HW, HW), 2, out=self._u8[:P], capacity=self.max_frames)
+        return self._push(x, ks)
+
+    def _push(self, x, ks) -> list:
+        """push's body: x (P, 1, 64, 64), the sum(ks) frames in stream order, then zeros."""
+        T, stride, cap, S = self.window, self.stride, self.cap, self.num_streams
         eng = self.model.engine()
         L = nat.lib()
         dev = eng.device
@@ -122,15 +152,9 @@ class AeStreamGroup:
         if self._ring is None:
             self._allocate(L, dev)
         ring = self._ring
-        F = sum(ks)
-        P = padded_frames(F, self.max_frames)
+        F, P = sum(ks), x.shape[0]
         dst, rows = group_schedule(self.frames_seen, self.windows_emitted, ks, T, stride, cap=cap)
         nw = len(rows)
-        # the frames of all streams and the padding, in one copy
-        parts = [x.to(torch.float32) for x in live]
-        if P > F:
-            parts.append(torch.zeros(P - F, 1, HW, HW, dtype=torch.float32, device=dev))
-        x = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
         self._copied.synchronize()  # (see _allocate: the device has the tables of the push before)
         self._h_dst[:P] = torch.tensor(dst + [-1] * (P - F), dtype=torch.int32)
         pl = eng.plan(P, 1)

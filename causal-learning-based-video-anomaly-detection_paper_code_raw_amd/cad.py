@@ -238,7 +238,7 @@ class CausalAnomalyDetector(nn.Module):
         from . import video as _video
         return _video.score_video(self, frames, window, stride, chunk=chunk, seed=seed, step=step, clip0=clip0)
 
-    def open_stream(self, window=16, stride=1, *, max_push=1, seed=0, step=0, clip0=0):
+    def open_stream(self, window=16, stride=1, *, max_push=1, seed=0, step=0, clip0=0, frame_size=None):
         """A streaming scorer for a live source (eval mode, fp32; stream.py): ``s.push(frames)`` takes the next
         1 <= k <= max_push frames, (k, 1, H, W) or (1, k, 1, H, W) on a HIP device, runs their backbone once and
         returns score_video's dict for exactly the windows they complete -- window w, counted from the start of the
@@ -249,11 +249,17 @@ class CausalAnomalyDetector(nn.Module):
         ValueError, before any device work, in training mode, with set_compute_dtype(torch.bfloat16), for window,
         stride or max_push that is not an integer >= 1, and at a push for k outside 1..max_push, a channel count
         other than 1 or a frame size other than the first push's.  Like score_video, a push overwrites the plans'
-        activations: a backward still pending on an earlier forward raises the "most recent forward only" error."""
+        activations: a backward still pending on an earlier forward raises the "most recent forward only" error.
+        ``s.push_u8(frames)`` takes the same k frames as uint8 (k, Hs, Ws) or (k, 1, Hs, Ws) at the source's own size,
+        on the device or in host memory: one launch resizes them to frame_size = (H, W) (data.resize_u8's bilinear)
+        and normalises them as (u8 - 0.5) / 0.5, then push's body runs.  frame_size=None: the first push fixes the
+        size, for a u8 push to the source size."""
         from . import stream as _stream
-        return _stream.CadStream(self, window, stride, max_push=max_push, seed=seed, step=step, clip0=clip0)
+        return _stream.CadStream(self, window, stride, max_push=max_push, seed=seed, step=step, clip0=clip0,
+                                 frame_size=frame_size)
 
-    def open_stream_group(self, num_streams, window=16, stride=1, *, max_push=1, seed=0, step=0, clip0=0):
+    def open_stream_group(self, num_streams, window=16, stride=1, *, max_push=1, seed=0, step=0, clip0=0,
+                          frame_size=None):
         """num_streams live sources of one frame size scored in shared launches (eval mode, fp32; stream_group.py):
         ``g.push(frames)`` takes a list of num_streams entries, entry s the next 0 <= k_s <= max_push frames of
         stream s as (k_s, 1, H, W) on a HIP device or None, and returns a list of num_streams dicts, dict s being what
@@ -265,7 +271,10 @@ class CausalAnomalyDetector(nn.Module):
         allocation, made at the first push, which also fixes the frame size.  ``g.frames_seen[s]`` /
         ``g.windows_emitted[s]`` count per stream; ``g.reset(s=None)`` restarts one stream or all.  ValueError, before
         any device work, as for open_stream, and at a push for a sequence of another length, k_s > max_push, a
-        channel count other than 1, a frame size other than the group's, or no frame at all."""
+        channel count other than 1, a frame size other than the group's, or no frame at all.  ``g.push_u8(frames)``
+        takes uint8 frames (k_s, Hs, Ws) or (k_s, 1, Hs, Ws) instead, every camera at its own source size, on the
+        device or in host memory: one launch resizes them all to frame_size = (H, W), normalises them as
+        (u8 - 0.5) / 0.5 and writes the padding, then push's body runs."""
         from . import stream_group as _group
         return _group.CadStreamGroup(self, num_streams, window, stride, max_push=max_push, seed=seed, step=step,
-                                     clip0=clip0)
+                                     clip0=clip0, frame_size=frame_size)

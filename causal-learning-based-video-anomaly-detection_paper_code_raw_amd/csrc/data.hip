@@ -10,6 +10,9 @@
 //                     (the scheme of cv2.resize INTER_LINEAR on u8 images that UCSDped2Dataset.__getitem__ calls,
 //                     cad:88-89; restated from its published algorithm, cv2 itself is absent here: parity unpinned
 //                     except for the identity case, which UCSD Ped2's native 360x240 frames hit)
+//   vad_ingest_u8 / vad_ingest_u8_table: the scoring side's ingest: u8 frames at the source's own size
+//                     and row pitch, in HBM or mapped host memory -> vad_resize_u8's pixel -> the normalisation ->
+//                     fp32 (nf, 1, dh, dw), in one launch; bit for bit the host routine followed by u8_pixel
 #include <math.h>
 
 #include <algorithm>
@@ -46,6 +49,135 @@ __global__ __launch_bounds__(256) void u8_to_clip_kernel(const uint8_t* __restri
     dst[i] = u8_pixel(src[i], mode);
 }
 
+
+// ---------------------------------------------------------------- ingest: resize + normalise in one launch
+// mode 2: the autoencoder dataset's /255 then clamp(0.001, 0.999) (cad1:110-114); modes 0 and 1 are u8_pixel's
+__device__ __forceinline__ float ingest_pixel(uint32_t u, int mode) {
+  return mode == 2 ? fminf(fmaxf((float)u / 255.f, 0.001f), 0.999f) : u8_pixel(u, mode);
+}
+
+constexpr int INGEST_ONE = 2048;      // vad_resize_u8's ONE
+constexpr int INGEST_MAX_DW = 4096;   // columns of the LDS column table (32 KB): the bound on dw
+constexpr int INGEST_MAX_ROWS = 32;   // output rows of one block
+constexpr int INGEST_ITEMS = 512;     // four-pixel groups a block aims at (two per thread)
+
+// One entry of vad_resize_u8's table(): the source index of destination index d and its two 11-bit weights, packed
+// c0 | c1 << 16 (both <= 2048).  The host rounds (d + 0.5) * scale and the subtraction separately; hipcc contracts
+// device code by default and an fma would round once, moving f by an ulp and a weight by one: contraction is off for
+// this block.  The double division is IEEE on gfx950, as on the host.
+__device__ __forceinline__ void resize_tap(int d, int sn, int dn, int& ofs, uint32_t& w) {
+#pragma clang fp contract(off)
+  const double scale = (double)sn / dn;
+  float f = (float)((d + 0.5) * scale - 0.5);
+  int s = (int)floorf(f);
+  f -= (float)s;
+  if (s < 0) {
+    f = 0.f;
+    s = 0;
+  }
+  if (s >= sn - 1) {
+    f = 0.f;
+    s = sn - 1;
+  }
+  ofs = s;
+  w = (uint32_t)(int)lrintf((1.f - f) * INGEST_ONE) | (uint32_t)(int)lrintf(f * INGEST_ONE) << 16;
+}
+
+// A block writes `rows` output rows of one frame: blockIdx.x = frame * strips + strip.  It builds the 256-entry pixel
+// table (the normalisation has 256 possible inputs: no division per pixel), the column table of all dw columns and
+// the row table of its rows in LDS, then each lane takes groups of four neighbouring pixels of a row.
+// TABLE: frame f reads (address, sh, sw, pitch) from row f of the device table, address 0 = a frame of zeros
+// (block-uniform: scalar loads); otherwise all frames share one size and lie frame_stride bytes apart.
+// Integer widths: the host's int64 is not needed -- a horizontal sum is at most 255 * 2049 (the two weights sum to
+// 2048, 2049 where both round up), the vertical one at most 2049 * 255 * 2048 + 2^21 = 1,072,169,984 < 2^31.
+// Stores: a row of dw floats starts 16-byte aligned only where dw (and for later frames dh * dw) allows, so a group
+// is stored as one f32x4 where its address is aligned and all four pixels exist, pixel by pixel otherwise.
+template <bool TABLE>
+__global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restrict__ src, int64_t frame_stride, int sh,
+                                                        int sw, int64_t pitch, const int64_t* __restrict__ table,
+                                                        int dh, int dw, int rows, int strips, int mode,
+                                                        float* __restrict__ dst) {
+  __shared__ float lut[256];
+  __shared__ int xofs[INGEST_MAX_DW];
+  __shared__ uint32_t xw[INGEST_MAX_DW];
+  __shared__ int yofs[INGEST_MAX_ROWS];
+  __shared__ uint32_t yw[INGEST_MAX_ROWS];
+  const int tid = threadIdx.x;
+  const int f = blockIdx.x / strips;
+  const int y0 = (blockIdx.x - f * strips) * rows;
+  const int nr = min(rows, dh - y0);
+  float* out = dst + ((int64_t)f * dh + y0) * dw;
+  if constexpr (TABLE) {
+    const int64_t* e = table + 4 * (int64_t)f;
+    src = reinterpret_cast<const uint8_t*>(e[0]);
+    sh = (int)e[1];
+    sw = (int)e[2];
+    pitch = e[3];
+    if (src == nullptr) {
+      for (int i = tid; i < nr * dw; i += 256) out[i] = 0.f;
+      return;
+    }
+  } else {
+    src += (int64_t)f * frame_stride;
+  }
+  lut[tid] = ingest_pixel((uint32_t)tid, mode);
+  for (int d = tid; d < dw; d += 256) resize_tap(d, sw, dw, xofs[d], xw[d]);
+  if (tid < nr) resize_tap(y0 + tid, sh, dh, yofs[tid], yw[tid]);
+  __syncthreads();
+  const int gpr = (dw + 3) >> 2;
+  for (int it = tid; it < nr * gpr; it += 256) {
+    const int r = it / gpr, x4 = (it - r * gpr) * 4;
+    const int sy = yofs[r], ya = (int)(yw[r] & 0xffffu), yb = (int)(yw[r] >> 16);
+    const uint8_t* s0 = src + (int64_t)sy * pitch;
+    const uint8_t* s1 = src + (int64_t)min(sy + 1, sh - 1) * pitch;
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int x = min(x4 + e, dw - 1);  // (a group past the row's end repeats its last pixel and stores none of it)
+      const int sx = xofs[x], xa = (int)(xw[x] & 0xffffu), xb = (int)(xw[x] >> 16);
+      const int h0 = sx + 1 < sw ? s0[sx] * xa + s0[sx + 1] * xb : s0[sx] * INGEST_ONE;
+      const int h1 = sx + 1 < sw ? s1[sx] * xa + s1[sx + 1] * xb : s1[sx] * INGEST_ONE;
+      const int v = (ya * h0 + yb * h1 + (1 << 21)) >> 22;
+      o[e] = lut[min(255, max(0, v))];
+    }
+    float* p = out + (int64_t)r * dw + x4;
+    if (x4 + 4 <= dw && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+      *reinterpret_cast<f32x4*>(p) = o;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (x4 + e < dw) p[e] = o[e];
+    }
+  }
+}
+
+// what both entry points ask of the output and the mode; returns the rows per block through `rows`
+static int ingest_check_output(const char* fn, int64_t nf, int dh, int dw, int mode, const float* dst, int& rows) {
+  const std::string name(fn);
+  VAD_CHECK(dst != nullptr, name + ": null dst");
+  VAD_CHECK(nf >= 1, name + ": nf must be >= 1");
+  VAD_CHECK(dh >= 1 && dw >= 1, name + ": dh and dw must be >= 1");
+  VAD_CHECK(dw <= INGEST_MAX_DW, name + ": dw must be at most " + std::to_string(INGEST_MAX_DW) +
+                                     " (the columns of the kernel's LDS table)");
+  VAD_CHECK(mode >= 0 && mode <= 2, name + ": mode 0 (Normalize 0.5/0.5), 1 (u8/255) or 2 (u8/255 clamped to "
+                                               "0.001..0.999)");
+  VAD_CHECK((reinterpret_cast<uintptr_t>(dst) & 15) == 0, name + ": dst must be 16-byte aligned");
+  VAD_CHECK(nf <= ((1ll << 31) - 1) / ((int64_t)dh * dw * 4), name + ": dst (nf * dh * dw * 4 bytes) is 2 GB or more");
+  rows = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(INGEST_MAX_ROWS, dh), INGEST_ITEMS / cdiv(dw, 4)));
+  return 0;
+}
+
+// one source frame; `who` names it in the error text ("" for the uniform entry, "entry 3 " for a table row)
+static int ingest_check_source(const char* fn, const std::string& who, int64_t sh, int64_t sw, int64_t pitch) {
+  const std::string name = std::string(fn) + ": " + who;
+  VAD_CHECK(sh >= 1 && sw >= 1, name + "sh and sw must be >= 1 (got sh = " + std::to_string(sh) + ", sw = " +
+                                    std::to_string(sw) + ")");
+  VAD_CHECK(pitch >= sw, name + "pitch " + std::to_string(pitch) + " is less than sw = " + std::to_string(sw));
+  VAD_CHECK(sh < (1ll << 31) && pitch < (1ll << 31) && sh * pitch < (1ll << 31),
+            name + "the frame (sh * pitch bytes) is 2 GB or more");
+  return 0;
+}
+
 }  // namespace vad
 
 using namespace vad;
@@ -60,6 +192,48 @@ int vad_u8_to_clip(const uint8_t* src, int64_t n, int mode, float* dst, void* st
   // (1024 blocks keep ~4 MB of 16-B requests in flight: enough for HBM, and for PCIe when src is mapped host memory)
   hipLaunchKernelGGL(u8_to_clip_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n / 16 + 1, 256), 1024)), dim3(256), 0,
                      (hipStream_t)stream, src, n, mode, dst);
+  VAD_LAUNCH_CHECK();
+  return 0;
+}
+
+int vad_ingest_u8(const uint8_t* src, int64_t nf, int sh, int sw, int64_t pitch, int64_t frame_stride, int dh, int dw,
+                  int mode, float* dst, void* stream) {
+  VAD_CHECK(src != nullptr, "vad_ingest_u8: null src");
+  int rows = 0;
+  VAD_TRY(ingest_check_output("vad_ingest_u8", nf, dh, dw, mode, dst, rows));
+  VAD_TRY(ingest_check_source("vad_ingest_u8", "", sh, sw, pitch));
+  VAD_CHECK(frame_stride >= 0, "vad_ingest_u8: frame_stride must be >= 0");
+  const int strips = (int)cdiv(dh, rows);
+  hipLaunchKernelGGL(ingest_u8_kernel<false>, dim3((unsigned)(nf * strips)), dim3(256), 0, (hipStream_t)stream, src,
+                     frame_stride, sh, sw, pitch, (const int64_t*)nullptr, dh, dw, rows, strips, mode, dst);
+  VAD_LAUNCH_CHECK();
+  return 0;
+}
+
+int64_t vad_ingest_table_bytes(int64_t nf) {
+  if (nf < 1 || nf > (1ll << 31)) {
+    vad::set_error("vad_ingest_table_bytes: nf must be >= 1");
+    return -1;
+  }
+  return nf * 32;
+}
+
+int vad_ingest_u8_table(const int64_t* host_table, int64_t nf, int dh, int dw, int mode, float* dst, void* dev_table,
+                        void* stream) {
+  VAD_CHECK(host_table && dev_table, "vad_ingest_u8_table: null table (host_table or dev_table)");
+  VAD_CHECK((reinterpret_cast<uintptr_t>(dev_table) & 15) == 0, "vad_ingest_u8_table: dev_table must be 16-B aligned");
+  int rows = 0;
+  VAD_TRY(ingest_check_output("vad_ingest_u8_table", nf, dh, dw, mode, dst, rows));
+  for (int64_t f = 0; f < nf; ++f) {
+    const int64_t* e = host_table + 4 * f;
+    if (e[0] == 0) continue;  // a frame of zeros: its sizes are not read
+    VAD_TRY(ingest_check_source("vad_ingest_u8_table", "entry " + std::to_string(f) + ": ", e[1], e[2], e[3]));
+  }
+  VAD_HIP(hipMemcpyAsync(dev_table, host_table, (size_t)nf * 32, hipMemcpyHostToDevice, (hipStream_t)stream));
+  const int strips = (int)cdiv(dh, rows);
+  hipLaunchKernelGGL(ingest_u8_kernel<true>, dim3((unsigned)(nf * strips)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint8_t*)nullptr, (int64_t)0, 0, 0, (int64_t)0, static_cast<const int64_t*>(dev_table), dh,
+                     dw, rows, strips, mode, dst);
   VAD_LAUNCH_CHECK();
   return 0;
 }

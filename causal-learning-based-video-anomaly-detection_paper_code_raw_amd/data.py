@@ -282,3 +282,198 @@ def prefetch(loader, stager: ClipStager, with_ready: bool = False):
         pending = issue(x, y)
         yield cur
     yield finish(*pending)
+
+
+# ---------------------------------------------------------------- scoring-side ingest
+INGEST_MODES = (0, 1, 2)  # (u8 - 0.5) / 0.5 (cad), u8 / 255 (mc, bbox), clamp(u8 / 255, 0.001, 0.999) (cad1:110-114)
+
+
+def check_u8_frames(frames, what="ingest_u8") -> torch.Tensor:
+    """The ValueErrors of a u8 source, raised before any device work: a uint8 tensor (k, Hs, Ws) or (k, 1, Hs, Ws)
+    with Hs, Ws >= 1.  Returns it as (k, Hs, Ws) (a view)."""
+    if not isinstance(frames, torch.Tensor) or frames.dim() not in (3, 4):
+        raise ValueError(f"{what}: uint8 frames of shape (k, Hs, Ws) or (k, 1, Hs, Ws), got "
+                         f"{tuple(getattr(frames, 'shape', ())) or type(frames).__name__}")
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"{what}: frames must be uint8, got {frames.dtype}")
+    if frames.dim() == 4:
+        if frames.shape[1] != 1:
+            raise ValueError(f"{what}: single-channel frames only, got {frames.shape[1]} channels")
+        frames = frames[:, 0]
+    if frames.shape[1] < 1 or frames.shape[2] < 1:
+        raise ValueError(f"{what}: empty frames {tuple(frames.shape)}")
+    return frames
+
+
+def _check_size_mode(size_hw, mode, what="ingest_u8"):
+    try:
+        h, w = (int(v) for v in size_hw)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: size_hw must be (H, W), got {size_hw!r}") from None
+    if h < 1 or w < 1 or (h, w) != tuple(size_hw):
+        raise ValueError(f"{what}: size_hw must be two integers >= 1, got {size_hw!r}")
+    if mode not in INGEST_MODES:
+        raise ValueError(f"{what}: mode 0 ((u8 - 0.5) / 0.5), 1 (u8 / 255) or 2 (u8 / 255 clamped to 0.001..0.999), "
+                         f"got {mode!r}")
+    return h, w
+
+
+def ingest_device(model, sources, what) -> torch.device:
+    """The device a push_u8 runs on: the model's, which must be a HIP device -- it reads host sources -- and the one
+    every device source is on (ValueError, before any device work)."""
+    dev = next(model.parameters()).device
+    for x in sources:
+        if dev.type != "cuda" or (x.is_cuda and x.device != dev):
+            raise ValueError(f"{what}: frames on {x.device}, but the model is on {dev} (host frames are read by the "
+                             "model's HIP device; device frames must be on it)")
+    return dev
+
+
+class U8Ingest:
+    """u8 frames at the source's own size -> fp32 (k, 1, H, W) on the device, resized as ``resize_u8`` resizes and
+    normalised, in one launch on the current stream (vad_ingest_u8 / vad_ingest_u8_table).  Holds what that needs
+    besides the kernel: a pinned slot for pageable sources, the device addresses of pinned sources it has seen, and --
+    once ``table`` is used -- the pinned frame table with its device copy.
+
+    A source may be on the device, in pinned host memory (read in place over PCIe: it must stay unchanged until the
+    work queued by the call has run) or in pageable host memory (copied through the slot, which waits for the launch
+    that last read it).  Rows may be strided; a source whose pixels within a row are not adjacent is made contiguous
+    first."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._slot = None   # pinned u8 bytes for pageable sources
+        self._done = None   # the event behind the last launch: it has read the slot and the device has the table
+        self._dptr = {}     # pinned host pointer -> its device address
+        self._h_table = self._d_table = None
+
+    def _address(self, host: torch.Tensor) -> int:
+        p = host.data_ptr()
+        d = self._dptr.get(p)
+        if d is None:
+            d = self._dptr[p] = nat.host_device_ptr(host)
+            if len(self._dptr) > 256:  # (caller-owned pinned frames come and go)
+                self._dptr.pop(next(iter(self._dptr)))
+        return d
+
+    def _wait(self):
+        if self._done is not None:
+            self._done.synchronize()
+
+    def _record(self):
+        if self._done is None:
+            self._done = torch.cuda.Event()
+        self._done.record(torch.cuda.current_stream(self.device))
+
+    def _sources(self, chunks):
+        """Per chunk (k, Hs, Ws): (address of frame 0, Hs, Ws, row pitch, frame stride), strides in bytes."""
+        def readable(x):  # rows of adjacent pixels, pitch >= Ws apart (not an expanded or transposed view)
+            return (x.shape[2] == 1 or x.stride(2) == 1) and (x.shape[1] == 1 or x.stride(1) >= x.shape[2])
+
+        chunks = [x if readable(x) else x.contiguous() for x in chunks]
+        pageable = [i for i, x in enumerate(chunks) if not x.is_cuda and not x.is_pinned()]
+        if pageable:
+            need = sum(chunks[i].numel() for i in pageable)
+            self._wait()
+            if self._slot is None or self._slot.numel() < need:
+                self._slot = torch.empty(need, dtype=torch.uint8, pin_memory=True)
+            off = 0
+            for i in pageable:
+                x = chunks[i]
+                view = self._slot[off:off + x.numel()].view(x.shape)
+                view.copy_(x)
+                chunks[i] = view
+                off += x.numel()
+        out = []
+        for x in chunks:
+            if x.is_cuda:
+                if x.device != self.device:
+                    raise ValueError(f"ingest_u8: frames on {x.device}, the ingest runs on {self.device}")
+                addr = x.data_ptr()
+            else:
+                addr = self._address(x)
+            k, hs, ws = x.shape
+            pitch = x.stride(1) if hs > 1 else ws
+            fstride = x.stride(0) if k > 1 else 0
+            out.append((addr, hs, ws, pitch, fstride))
+        return out
+
+    def _out(self, out, n, h, w):
+        if out is None:
+            return torch.empty(n, 1, h, w, dtype=torch.float32, device=self.device)
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n, 1, h, w)
+                or not out.is_contiguous() or out.device != self.device or out.data_ptr() % 16):
+            raise ValueError(f"ingest_u8: out must be a contiguous, 16-byte aligned float32 tensor ({n}, 1, {h}, {w}) "
+                             f"on {self.device}")
+        return out
+
+    def ingest(self, frames, size_hw, mode, out=None) -> torch.Tensor:
+        """frames: uint8 (k, Hs, Ws) or (k, 1, Hs, Ws), k >= 1 -> fp32 (k, 1, H, W), the uniform form."""
+        x = check_u8_frames(frames)
+        h, w = _check_size_mode(size_hw, mode)
+        if x.shape[0] < 1:
+            raise ValueError("ingest_u8: no frame")
+        nat.require_hip(torch.empty(0, device=self.device))
+        out = self._out(out, x.shape[0], h, w)
+        (addr, hs, ws, pitch, fstride), = self._sources([x])
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().vad_ingest_u8(addr, x.shape[0], hs, ws, pitch, fstride, h, w, mode, out.data_ptr(),
+                                              nat.stream_of(self.device)))
+        self._record()
+        return out
+
+    def table(self, chunks, n, size_hw, mode, out=None, capacity=None) -> torch.Tensor:
+        """chunks: uint8 tensors (k_i, Hs_i, Ws_i), each of its own size -> fp32 (n, 1, H, W): their frames in order,
+        then n - sum(k_i) frames of zeros, in one table-form launch.  capacity: the largest n this object will see
+        (the tables are allocated once)."""
+        h, w = _check_size_mode(size_hw, mode)
+        chunks = [check_u8_frames(x) for x in chunks]
+        total = sum(x.shape[0] for x in chunks)
+        if total < 1 or total > n:
+            raise ValueError(f"ingest_u8: {total} frames for a batch of {n}")
+        nat.require_hip(torch.empty(0, device=self.device))
+        L = nat.lib()
+        out = self._out(out, n, h, w)
+        cap = max(n, capacity or 0)
+        if self._h_table is None or self._h_table.shape[0] < cap:
+            nb = L.vad_ingest_table_bytes(cap)
+            if nb < 0:
+                nat.check(1)
+            self._wait()
+            self._h_table = torch.zeros(cap, 4, dtype=torch.int64).pin_memory()
+            self._d_table = torch.zeros(nb // 8, dtype=torch.int64, device=self.device)
+        srcs = self._sources(chunks)
+        rows = [(addr + j * fstride, hs, ws, pitch) for x, (addr, hs, ws, pitch, fstride) in zip(chunks, srcs)
+                for j in range(x.shape[0])]
+        rows += [(0, 0, 0, 0)] * (n - total)
+        self._wait()  # (the device has the table of the launch before)
+        self._h_table[:n] = torch.tensor(rows, dtype=torch.int64)
+        with torch.cuda.device(self.device):
+            nat.check(L.vad_ingest_u8_table(self._h_table.data_ptr(), n, h, w, mode, out.data_ptr(),
+                                            self._d_table.data_ptr(), nat.stream_of(self.device)))
+        self._record()
+        return out
+
+
+_INGESTS = {}
+
+
+def ingest_u8(frames, size_hw, mode, *, out=None) -> torch.Tensor:
+    """uint8 frames (k, Hs, Ws) or (k, 1, Hs, Ws) -> fp32 (k, 1, H, W) on the device, each frame resized to
+    size_hw = (H, W) exactly as ``resize_u8`` resizes it and normalised (mode 0: (u8 - 0.5) / 0.5, 1: u8 / 255,
+    2: u8 / 255 clamped to 0.001..0.999), by one kernel on the current stream.  frames on the HIP device, in pinned
+    host memory (read in place) or in pageable host memory (through a pinned slot); host frames go to ``out``'s
+    device, else the current one.  ``score_video(ingest_u8(video_u8, (H, W), 0))`` scores a u8 video.  The state
+    lives in one U8Ingest per device; a stream owns its own."""
+    x = check_u8_frames(frames)
+    if x.is_cuda:
+        dev = x.device
+    elif out is not None:
+        dev = out.device
+    else:
+        nat.require_hip(torch.empty(0, device="cuda"))
+        dev = torch.device("cuda", torch.cuda.current_device())
+    ing = _INGESTS.get(dev)
+    if ing is None:
+        ing = _INGESTS[dev] = U8Ingest(dev)
+    return ing.ingest(x, size_hw, mode, out=out)

@@ -66,12 +66,35 @@ def check_push(model, frames, max_push, frame_size) -> torch.Tensor:
     return frames
 
 
+def check_push_u8(model, frames, max_push, what="push_u8") -> torch.Tensor:
+    """The ValueErrors of a stream's push_u8, raised before any device work; returns the frames as (k, Hs, Ws)."""
+    from .data import check_u8_frames
+    x = check_u8_frames(frames, what)
+    k = x.shape[0]
+    if k < 1 or k > max_push:
+        raise ValueError(f"{what}: between 1 and max_push = {max_push} frames per push, got {k}")
+    return x
+
+
+def check_frame_size(frame_size, what="open_stream"):
+    if frame_size is None:
+        return None
+    try:
+        size = tuple(int(v) for v in frame_size)
+        ok = len(size) == 2 and size == tuple(frame_size) and min(size) >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: frame_size must be None or (H, W), two integers >= 1, got {frame_size!r}")
+    return size
+
+
 class CadStream:
     """CausalAnomalyDetector.open_stream's result.  All state is the ring and three counters; the model's plans are
     borrowed for the duration of a push only, so clip forwards, score_video calls and optimizer steps may run between
     pushes (a weight change makes later frames use the new weights)."""
 
-    def __init__(self, model, window=16, stride=1, *, max_push=1, seed=0, step=0, clip0=0):
+    def __init__(self, model, window=16, stride=1, *, max_push=1, seed=0, step=0, clip0=0, frame_size=None):
         self.window = _positive_int("window", window)
         self.stride = _positive_int("stride", stride)
         self.max_push = _positive_int("max_push", max_push)
@@ -79,8 +102,10 @@ class CadStream:
         self.model = model
         self.cap = self.window + self.max_push - 1
         self.seed, self.step, self.clip0 = int(seed), int(step), int(clip0)
-        self.frame_size = None
+        # (H, W) of the frames the model sees: given, or fixed by the first push (a u8 push: its source size)
+        self.frame_size = check_frame_size(frame_size)
         self._ring = None
+        self._ingest = self._u8 = None  # push_u8's U8Ingest and its fp32 buffer of max_push frames
         self.frames_seen = 0
         self.windows_emitted = 0
 
@@ -93,7 +118,26 @@ class CadStream:
         """frames: (k, 1, H, W) or (1, k, 1, H, W) on the device, 1 <= k <= max_push.  Runs the per-frame stage on
         them and every window they complete; returns score_video's keys for exactly those windows (window_starts
         absolute; detections: the k pushed frames; empty tensors when no window completes)."""
-        x = check_push(self.model, frames, self.max_push, self.frame_size)
+        return self._push(check_push(self.model, frames, self.max_push, self.frame_size))
+
+    def push_u8(self, frames) -> dict:
+        """frames: the next 1 <= k <= max_push frames as uint8 (k, Hs, Ws) or (k, 1, Hs, Ws) at any source size, on
+        the device, in pinned host memory (read in place) or in pageable host memory.  One launch resizes them to the
+        stream's frame size as data.resize_u8 does and normalises them as (u8 - 0.5) / 0.5 into a buffer the stream
+        owns (data.U8Ingest); the rest is push: push_u8(u8) returns what push returns for the same frames converted
+        on the host.  Without frame_size the first push fixes it to the source size."""
+        from .data import U8Ingest, ingest_device
+        check_model(self.model)
+        x = check_push_u8(self.model, frames, self.max_push)
+        dev = ingest_device(self.model, [x], "push_u8")
+        size = self.frame_size or tuple(x.shape[1:])
+        if self._ingest is None:
+            self._ingest = U8Ingest(dev)
+            self._u8 = torch.empty(self.max_push, 1, *size, dtype=torch.float32, device=dev)
+        return self._push(self._ingest.ingest(x, size, 0, out=self._u8[:x.shape[0]]))
+
+    def _push(self, x) -> dict:
+        """push's body: x (k, 1, H, W), checked."""
         model, T, stride, cap = self.model, self.window, self.stride, self.cap
         eng = model.engine()
         nat.require_hip(x)

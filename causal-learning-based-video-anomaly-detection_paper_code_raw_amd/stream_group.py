@@ -23,7 +23,7 @@ from __future__ import annotations
 import torch
 
 from . import _native as nat
-from .stream import _positive_int, check_model, stream_schedule
+from .stream import _positive_int, check_frame_size, check_model, stream_schedule
 from .video import MAX_DET, NUM_FACTORS, cache_field
 
 
@@ -85,12 +85,39 @@ def check_group_push(model, frames, num_streams, max_push, frame_size):
     return chunks, ks, frame_size
 
 
+def check_group_push_u8(model, frames, num_streams, max_push, check_model=check_model):
+    """The ValueErrors of a group's push_u8, raised before any device work.  Returns (chunks, ks): per stream the
+    frames as uint8 (k_s, Hs_s, Ws_s), each stream at its own source size, or None where k_s = 0."""
+    from .data import check_u8_frames
+    check_model(model)
+    if not isinstance(frames, (list, tuple)) or len(frames) != num_streams:
+        got = f"{len(frames)} entries" if isinstance(frames, (list, tuple)) else type(frames).__name__
+        raise ValueError(f"push_u8: a list or tuple of num_streams = {num_streams} entries (uint8 frames (k, Hs, Ws) "
+                         f"or (k, 1, Hs, Ws), or None), got {got}")
+    chunks, ks = [], []
+    for s, x in enumerate(frames):
+        if x is None:
+            chunks.append(None)
+            ks.append(0)
+            continue
+        x = check_u8_frames(x, f"push_u8: stream {s}")
+        k = x.shape[0]
+        if k > max_push:
+            raise ValueError(f"push_u8: stream {s}: at most max_push = {max_push} frames per push, got {k}")
+        chunks.append(x if k > 0 else None)
+        ks.append(k)
+    if sum(ks) == 0:
+        raise ValueError("push_u8: no stream brought a frame")
+    return chunks, ks
+
+
 class CadStreamGroup:
     """CausalAnomalyDetector.open_stream_group's result: num_streams rings in one cache, two counters per stream, one
     device table and its pinned host image.  As with CadStream the model's plans are borrowed for the duration of a
     push only."""
 
-    def __init__(self, model, num_streams, window=16, stride=1, *, max_push=1, seed=0, step=0, clip0=0):
+    def __init__(self, model, num_streams, window=16, stride=1, *, max_push=1, seed=0, step=0, clip0=0,
+                 frame_size=None):
         self.num_streams = _positive_int("num_streams", num_streams)
         self.window = _positive_int("window", window)
         self.stride = _positive_int("stride", stride)
@@ -106,8 +133,10 @@ class CadStreamGroup:
         if len(clip0) != self.num_streams:
             raise ValueError(f"open_stream_group: clip0 must be an int or {self.num_streams} ints, got {len(clip0)}")
         self.clip0 = [int(c) for c in clip0]
-        self.frame_size = None
+        # (H, W) of the frames the model sees: given, or fixed by the first push (a u8 push: its first source's size)
+        self.frame_size = check_frame_size(frame_size, "open_stream_group")
         self._ring = None
+        self._ingest = self._u8 = None  # push_u8's U8Ingest and its fp32 buffer of max_frames frames
         self.frames_seen = [0] * self.num_streams
         self.windows_emitted = [0] * self.num_streams
 
@@ -135,11 +164,42 @@ class CadStreamGroup:
         (k_s, 1, H, W) on the device, or None.  Returns one CadStream.push dict per stream: empty tensors where the
         stream completed no window, no detections where it pushed nothing."""
         chunks, ks, size = check_group_push(self.model, frames, self.num_streams, self.max_push, self.frame_size)
-        model, T, stride, cap, S = self.model, self.window, self.stride, self.cap, self.num_streams
-        eng = model.engine()
         live = [x for x in chunks if x is not None]
         for x in live:
             nat.require_hip(x)
+        F = sum(ks)
+        P = padded_frames(F, self.max_frames)
+        # the frames of all streams and the padding, in one copy
+        parts = [x.float() for x in live]
+        if P > F:
+            parts.append(torch.zeros(P - F, 1, *size, dtype=torch.float32, device=live[0].device))
+        x = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
+        return self._push(x, ks, size)
+
+    def push_u8(self, frames) -> list:
+        """frames: a sequence of num_streams entries, entry s the next 0 <= k_s <= max_push frames of camera s as uint8
+        (k_s, Hs, Ws) or (k_s, 1, Hs, Ws), or None; cameras may differ in source size and in where their frames lie
+        (device, pinned host memory read in place, pageable host memory).  One table-form launch resizes every frame
+        to the group's frame size as data.resize_u8 does, normalises it as (u8 - 0.5) / 0.5 and writes the zero
+        padding, into a buffer the group owns (data.U8Ingest.table); the rest is push: push_u8 returns what push
+        returns for the same frames converted on the host.  Without frame_size the first push fixes it to the size of
+        its first source."""
+        from .data import U8Ingest, ingest_device
+        chunks, ks = check_group_push_u8(self.model, frames, self.num_streams, self.max_push)
+        live = [x for x in chunks if x is not None]
+        dev = ingest_device(self.model, live, "push_u8")
+        size = self.frame_size or tuple(live[0].shape[1:])
+        if self._ingest is None:
+            self._ingest = U8Ingest(dev)
+            self._u8 = torch.empty(self.max_frames, 1, *size, dtype=torch.float32, device=dev)
+        P = padded_frames(sum(ks), self.max_frames)
+        x = self._ingest.table(live, P, size, 0, out=self._u8[:P], capacity=self.max_frames)
+        return self._push(x, ks, size)
+
+    def _push(self, x, ks, size) -> list:
+        """push's body: x (P, 1, H, W), the sum(ks) frames in stream order, then zeros."""
+        model, T, stride, cap, S = self.model, self.window, self.stride, self.cap, self.num_streams
+        eng = model.engine()
         L = nat.lib()
         dev = eng.device
         stream = nat.stream_of(dev)
@@ -147,15 +207,9 @@ class CadStreamGroup:
             self._allocate(L, dev)
             self.frame_size = size
         ring, H, W = self._ring, size[0], size[1]
-        F = sum(ks)
-        P = padded_frames(F, self.max_frames)
+        F, P = sum(ks), x.shape[0]
         dst, rows = group_schedule(self.frames_seen, self.windows_emitted, ks, T, stride, cap=cap, clip0=self.clip0)
         nw = len(rows)
-        # the frames of all streams and the padding, in one copy
-        parts = [x.float() for x in live]
-        if P > F:
-            parts.append(torch.zeros(P - F, 1, H, W, dtype=torch.float32, device=dev))
-        x = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
         self._h_dst[:P] = torch.tensor(dst + [-1] * (P - F), dtype=torch.int32)
         # a forward armed for another input must not outlive this call (CadEngine.input_ready)
         armed, eng._armed = getattr(eng, "_armed", None), None

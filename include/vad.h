@@ -610,6 +610,24 @@ int vad_u8_to_clip(const uint8_t* src, int64_t n, int mode, float* dst, void* st
 int vad_host_device_ptr(const void* host, void** dev);
 int vad_resize_u8(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw);
 
+/* Ingest for scoring: u8 frames at the source's own size -> fp32 (nf, 1, dh, dw) contiguous at dst, in
+ * one launch.  Every output pixel is vad_resize_u8's pixel pushed through the normalisation, bit for bit: mode 0 and 1
+ * as vad_u8_to_clip, mode 2: fminf(fmaxf(u8 / 255, 0.001), 0.999) (the autoencoder's dataset, cad1:110-114).  Sources
+ * lie in HBM or in pinned host memory at the address vad_host_device_ptr gives; rows are pitch >= sw bytes apart and
+ * need no alignment.  Any sh, sw, dh >= 1; 1 <= dw <= 4096 (the kernel's LDS column table); a source frame (sh * pitch
+ * bytes) and dst (nf * dh * dw * 4 bytes) stay below 2 GB; dst 16-byte aligned.
+ * vad_ingest_u8: nf frames of one size, frame f at src + f * frame_stride bytes.
+ * vad_ingest_u8_table: frame f is row f of host_table, four int64 (device address, sh, sw, pitch); address 0 writes a
+ *   frame of zeros and its sizes are not read.  Every row is validated first (an error names the entry and nothing is
+ *   queued), then the table is copied with one hipMemcpyAsync into dev_table -- caller-owned device memory, 16-byte
+ *   aligned, of at least vad_ingest_table_bytes(nf) bytes -- and the kernel reads it there.  host_table must stay
+ *   unchanged until that copy has run (pinned memory: the copy is asynchronous). */
+int vad_ingest_u8(const uint8_t* src, int64_t nf, int sh, int sw, int64_t pitch, int64_t frame_stride, int dh, int dw,
+                  int mode, float* dst, void* stream);
+int64_t vad_ingest_table_bytes(int64_t nf);
+int vad_ingest_u8_table(const int64_t* host_table, int64_t nf, int dh, int dw, int mode, float* dst, void* dev_table,
+                        void* stream);
+
 /* Plan options.  "conv_bf16" (0/1): the 3x3 convs of the backbone run on bf16 operands with fp32 accumulation
  * (BASELINE config 4's bf16 compute; BN, pooling, heads, losses and the optimizer stay fp32).  Default 0: fp32
  * numerics (split-bf16 products).  "stem_grad" (0/1): backbone.conv1 / bn1 train (the module without
