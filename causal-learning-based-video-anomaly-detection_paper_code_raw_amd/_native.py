@@ -75,6 +75,9 @@ _SIGS = {
     "vad_ingest_u8": (_I, [_P, _I64, _I, _I, _I64, _I64, _I, _I, _I, _P, _P]),
     "vad_ingest_table_bytes": (_I64, [_I64]),
     "vad_ingest_u8_table": (_I, [_P, _I64, _I, _I, _I, _P, _P, _P]),
+    "vad_luma_u8": (_I, [_P, _I, _I, _I64, _I, _P]),
+    "vad_ingest_u8_color": (_I, [_P, _I64, _I, _I, _I64, _I64, _I, _I, _I, _I, _I, _P, _P]),
+    "vad_ingest_u8_color_table": (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vad_debug_d2h": (_I, [_P, _P, _I64]),
     "vad_cad_profile": (_I, [_P, _I, ctypes.c_char_p]),
     "vad_cad_profile_read": (_I, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I), _I]),
@@ -155,6 +158,7 @@ _SIGS = {
     "vad_bbox_workspace_bytes": (_I64, [_P]),
     "vad_bbox_bind": (_I, [_P, _P, _P]),
     "vad_bbox_forward": (_I, [_P, _P, _P, _P, _P, _P]),
+    "vad_bbox_windows_forward": (_I, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
     "vad_bbox_head_forward": (_I, [_P, _P, _P, _P, _P]),
     "vad_bbox_debug_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(_I64)]),
     # cad1 memory autoencoder (causal_anomaly_detection1.py)

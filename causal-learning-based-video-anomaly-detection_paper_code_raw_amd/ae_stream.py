@@ -91,20 +91,21 @@ class AeStream:
         frame_features: the k pushed frames, a copy; empty tensors when no window completes)."""
         return self._push(check_push(self.model, frames, self.max_push))
 
-    def push_u8(self, frames) -> dict:
+    def push_u8(self, frames, color=None) -> dict:
         """frames: the next 1 <= k <= max_push frames as uint8 (k, Hs, Ws) or (k, 1, Hs, Ws) at any source size, on
         the device, in pinned host memory (read in place) or in pageable host memory.  One launch resizes them to
         64x64 as data.resize_u8 does and normalises them as the reference's dataset does, u8 / 255 clamped to
         0.001..0.999 (cad1:110-114), into a buffer the stream owns (data.U8Ingest); the rest is push: push_u8(u8)
-        returns what push returns for the same frames converted on the host."""
+        returns what push returns for the same frames converted on the host.  With color ("rgb", "bgr", "rgbx" or "bgrx") the frames are packed colour pixels, uint8
+        (k, Hs, Ws, 3) or (k, Hs, Ws, 4), and the same launch takes their grey first (data.luma_u8, PIL's convert("L"))."""
         from .data import U8Ingest, ingest_device
         check_model(self.model)
-        x = check_push_u8(self.model, frames, self.max_push)
+        x = check_push_u8(self.model, frames, self.max_push, color=color)
         dev = ingest_device(self.model, [x], "push_u8")
         if self._ingest is None:
             self._ingest = U8Ingest(dev)
             self._u8 = torch.empty(self.max_push, 1, HW, HW, dtype=torch.float32, device=dev)
-        return self._push(self._ingest.ingest(x, (HW, HW), 2, out=self._u8[:x.shape[0]]))
+        return self._push(self._ingest.ingest(x, (HW, HW), 2, out=self._u8[:x.shape[0]], color=color))
 
     def _push(self, x) -> dict:
         """push's body: x (k, 1, 64, 64), checked."""

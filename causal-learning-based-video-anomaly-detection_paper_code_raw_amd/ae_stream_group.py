@@ -124,22 +124,24 @@ class AeStreamGroup:
         x = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
         return self._push(x, ks)
 
-    def push_u8(self, frames) -> list:
+    def push_u8(self, frames, color=None) -> list:
         """frames: a sequence of num_streams entries, entry s the next 0 <= k_s <= max_push frames of camera s as uint8
         (k_s, Hs, Ws) or (k_s, 1, Hs, Ws), or None; cameras may differ in source size and in where their frames lie
         (device, pinned host memory read in place, pageable host memory).  One table-form launch resizes every frame
         to 64x64 as data.resize_u8 does, normalises it as u8 / 255 clamped to 0.001..0.999 (cad1:110-114) and writes
         the zero padding, into a buffer the group owns (data.U8Ingest.table); the rest is push: push_u8 returns what
-        push returns for the same frames converted on the host."""
+        push returns for the same frames converted on the host.  With color ("rgb", "bgr", "rgbx" or "bgrx") every camera brings packed colour pixels,
+        uint8 (k_s, Hs, Ws, 3) or (k_s, Hs, Ws, 4) -- one format for the whole call -- and the same launch takes their
+        grey first (data.luma_u8, PIL's convert("L"))."""
         from .data import U8Ingest, ingest_device
-        chunks, ks = check_group_push_u8(self.model, frames, self.num_streams, self.max_push, check_model)
+        chunks, ks = check_group_push_u8(self.model, frames, self.num_streams, self.max_push, check_model, color)
         live = [x for x in chunks if x is not None]
         dev = ingest_device(self.model, live, "push_u8")
         if self._ingest is None:
             self._ingest = U8Ingest(dev)
             self._u8 = torch.empty(self.max_frames, 1, HW, HW, dtype=torch.float32, device=dev)
         P = padded_frames(sum(ks), self.max_frames)
-        x = self._ingest.table(live, P, (HW, HW), 2, out=self._u8[:P], capacity=self.max_frames)
+        x = self._ingest.table(live, P, (HW, HW), 2, out=self._u8[:P], capacity=self.max_frames, color=color)
         return self._push(x, ks)
 
     def _push(self, x, ks) -> list:

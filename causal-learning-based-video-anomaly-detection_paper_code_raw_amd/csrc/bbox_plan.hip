@@ -34,10 +34,15 @@ static const FlatLayout& bb_layout() {
 // LDS once; lane (i, j) of every wave computes the 2 x 2 x 2 conv outputs under pooled voxel (i, j) for the wave's 8
 // output channels (wave-uniform: the weights are scalar operands, wT[ci][tap][32]) and keeps relu(max + bias)
 // (= max of relu(conv + bias): fl(a + b) and relu are monotone in a).
+// WIN: x is a video, frame-major planar (N, 3, H, W), and clip b is its window of frames first + b * stride + d,
+// d = 0 .. T-1 (vad_bbox_windows_forward): only the address of the staging loop differs -- the zero padding at d < 0
+// and d >= T is the window's, as for a clip, so neighbouring frames of the video are never read in its place.
+template <bool WIN>
 __global__ __launch_bounds__(256) void bbox_conv1_pool_kernel(const float* __restrict__ x, int T, int H, int W,
                                                               const float* __restrict__ wT,
                                                               const float* __restrict__ bias, int T2, int H2,
-                                                              int W2, int tiles_w, float* __restrict__ pooled) {
+                                                              int W2, int tiles_w, float* __restrict__ pooled,
+                                                              int64_t first, int64_t stride) {
   constexpr int PW = 18, PH = 18, PD = 4, CI = 3;
   __shared__ float xs[CI][PD][PH][PW + 1];
   const int tid = threadIdx.x;
@@ -52,7 +57,12 @@ __global__ __launch_bounds__(256) void bbox_conv1_pool_kernel(const float* __res
     const int xx = i % PW, yy = (i / PW) % PH, dd = (i / (PW * PH)) % PD, ci = i / (PW * PH * PD);
     const int d = d0 + dd, y = y0 + yy, xw = x0 + xx;
     float v = 0.f;
-    if (d >= 0 && d < T && y >= 0 && y < H && xw >= 0 && xw < W) v = xb[(((int64_t)ci * T + d) * H + y) * W + xw];
+    if (d >= 0 && d < T && y >= 0 && y < H && xw >= 0 && xw < W) {
+      if constexpr (WIN)
+        v = x[(((first + b * stride + d) * CI + ci) * H + y) * W + xw];
+      else
+        v = xb[(((int64_t)ci * T + d) * H + y) * W + xw];
+    }
     xs[ci][dd][yy][xx] = v;
   }
   __syncthreads();
@@ -163,12 +173,14 @@ struct BbPlanImpl {
     w3 = w.take<float>(64 * 32 * 27);
   }
 
-  // x -> feature rows f (B, 1024)
-  int encoder(const float* x, float* f, hipStream_t st) {
+  // x -> feature rows f (B, 1024); x: the B clips, or with win a video whose windows first + b * stride they are
+  int encoder(const float* x, float* f, hipStream_t st, bool win = false, int64_t first = 0, int64_t stride = 0) {
     DenseAct relu;
     relu.relu = 1;
     if (g_bbox_im2col) {  // (knob "bbox_im2col": the round-2 path -- im2col columns + f32 MFMA GEMMs)
-      VAD_TRY(im2col3d(x, ncdhw_strides(g1.in), g1, nullptr, nullptr, 0, cols1, st));
+      const int64_t hw = (int64_t)H * W;  // (a window is a strided view of the video: clip b, channel c, depth d)
+      const Strides5 sx = win ? Strides5{stride * 3 * hw, hw, 3 * hw, W, 1} : ncdhw_strides(g1.in);
+      VAD_TRY(im2col3d(x + (win ? first * 3 * hw : 0), sx, g1, nullptr, nullptr, 0, cols1, st));
       VAD_TRY(dense_fwd(cols1, (int)g1.rows(), g1.K(), P(0), P(1), 32, y1, relu, scratch, scratch_floats, st));
       VAD_TRY(maxpool3d_fwd(y1, nullptr, 0, g1.out(), 2, 2, 2, pooled, st));
       VAD_TRY(im2col3d(pooled, ndhwc_strides(pool_vol), g2, nullptr, nullptr, 0, cols2, st));
@@ -183,8 +195,12 @@ struct BbPlanImpl {
       const Vol5& pv = pool_vol;
       if (pv.D > 0 && pv.H > 0 && pv.W > 0) {
         const int tiles_w = (int)cdiv(pv.W, 8), tiles = (int)cdiv(pv.H, 8) * tiles_w;
-        hipLaunchKernelGGL(bbox_conv1_pool_kernel, dim3(pv.D * tiles, B), dim3(256), 0, st, x, T, H, W, wT1, P(1),
-                           pv.D, pv.H, pv.W, tiles_w, pooled);
+        if (win)
+          hipLaunchKernelGGL(bbox_conv1_pool_kernel<true>, dim3(pv.D * tiles, B), dim3(256), 0, st, x, T, H, W, wT1,
+                             P(1), pv.D, pv.H, pv.W, tiles_w, pooled, first, stride);
+        else
+          hipLaunchKernelGGL(bbox_conv1_pool_kernel<false>, dim3(pv.D * tiles, B), dim3(256), 0, st, x, T, H, W, wT1,
+                             P(1), pv.D, pv.H, pv.W, tiles_w, pooled, (int64_t)0, (int64_t)0);
         VAD_LAUNCH_CHECK();
       }
       VAD_TRY(conv3d_x3_fwd(B, pv.D, pv.H, pv.W, 32, 64, pooled, w3, P(3), y2, st));
@@ -208,6 +224,13 @@ struct BbPlanImpl {
   int forward(const float* x, float* scores, float* adj, float* features, hipStream_t st) {
     float* f = features ? features : feats;
     VAD_TRY(encoder(x, f, st));
+    return head(f, scores, adj, st);
+  }
+
+  int forward_windows(const float* frames, int64_t first, int64_t stride, float* scores, float* adj, float* features,
+                      hipStream_t st) {
+    float* f = features ? features : feats;
+    VAD_TRY(encoder(frames, f, st, true, first, stride));
     return head(f, scores, adj, st);
   }
 };
@@ -253,6 +276,21 @@ int vad_bbox_forward(vad_bbox_plan* plan, const float* x, float* scores, float* 
   VAD_CHECK(plan && x && scores && adj, "vad_bbox_forward: null argument");
   VAD_CHECK(plan->impl.params != nullptr, "vad_bbox_forward: plan not bound");
   return plan->impl.forward(x, scores, adj, features, (hipStream_t)stream);
+}
+
+int vad_bbox_windows_forward(vad_bbox_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
+                             float* scores, float* adj, float* features, void* stream) {
+  VAD_CHECK(plan && frames && scores && adj, "vad_bbox_windows_forward: null argument");
+  VAD_CHECK(stride >= 1, "vad_bbox_windows_forward: stride must be >= 1, got " + std::to_string(stride));
+  VAD_CHECK(first >= 0, "vad_bbox_windows_forward: first must be >= 0, got " + std::to_string(first));
+  const int64_t B = plan->impl.B, T = plan->impl.T;
+  // first + (B - 1) * stride + T <= n_frames, without a product that could overflow
+  VAD_CHECK(n_frames >= T && first <= n_frames - T && (B == 1 || stride <= (n_frames - T - first) / (B - 1)),
+            "vad_bbox_windows_forward: " + std::to_string(B) + " windows of " + std::to_string(T) + " frames from frame " +
+                std::to_string(first) + " at stride " + std::to_string(stride) + " end past the video's " +
+                std::to_string(n_frames) + " frames");
+  VAD_CHECK(plan->impl.params != nullptr, "vad_bbox_windows_forward: plan not bound");
+  return plan->impl.forward_windows(frames, first, stride, scores, adj, features, (hipStream_t)stream);
 }
 
 int vad_bbox_head_forward(vad_bbox_plan* plan, const float* features, float* scores, float* adj, void* stream) {

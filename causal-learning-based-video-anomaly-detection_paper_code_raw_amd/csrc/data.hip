@@ -13,6 +13,9 @@
 //   vad_ingest_u8 / vad_ingest_u8_table: the scoring side's ingest: u8 frames at the source's own size
 //                     and row pitch, in HBM or mapped host memory -> vad_resize_u8's pixel -> the normalisation ->
 //                     fp32 (nf, 1, dh, dw), in one launch; bit for bit the host routine followed by u8_pixel
+//   vad_ingest_u8_color / _table: the same launch on packed colour pixels: PIL's luma of every source
+//                     tap (grey out), or the three channels as planes R, G, B (the bbox scorer's input)
+//   vad_luma_u8     : that luma on the host, the other side of the equality
 #include <math.h>
 
 #include <algorithm>
@@ -56,6 +59,15 @@ __device__ __forceinline__ float ingest_pixel(uint32_t u, int mode) {
   return mode == 2 ? fminf(fmaxf((float)u / 255.f, 0.001f), 0.999f) : u8_pixel(u, mode);
 }
 
+// packed colour formats: 0 rgb, 1 bgr (3 bytes a pixel), 2 rgbx, 3 bgrx (4 bytes, X never read); G is byte 1 in all
+__host__ __device__ __forceinline__ int ingest_step(int fmt) { return fmt >= 2 ? 4 : 3; }
+__host__ __device__ __forceinline__ int ingest_r(int fmt) { return (fmt & 1) ? 2 : 0; }
+__host__ __device__ __forceinline__ int ingest_b(int fmt) { return (fmt & 1) ? 0 : 2; }
+// PIL's convert("L") (ITU-R 601-2 in 16-bit fixed point; the coefficients sum to 65536)
+__host__ __device__ __forceinline__ int luma_u8(int r, int g, int b) {
+  return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16;
+}
+
 constexpr int INGEST_ONE = 2048;      // vad_resize_u8's ONE
 constexpr int INGEST_MAX_DW = 4096;   // columns of the LDS column table (32 KB): the bound on dw
 constexpr int INGEST_MAX_ROWS = 32;   // output rows of one block
@@ -92,11 +104,18 @@ __device__ __forceinline__ void resize_tap(int d, int sn, int dn, int& ofs, uint
 // 2048, 2049 where both round up), the vertical one at most 2049 * 255 * 2048 + 2^21 = 1,072,169,984 < 2^31.
 // Stores: a row of dw floats starts 16-byte aligned only where dw (and for later frames dh * dw) allows, so a group
 // is stored as one f32x4 where its address is aligned and all four pixels exist, pixel by pixel otherwise.
-template <bool TABLE>
+// PLANES 0: grey source bytes, the form above.  PLANES 1 and 3: packed colour pixels of fmt (ingest_step bytes each, R
+// and B at ingest_r / ingest_b, G at 1; an X byte is never loaded), read byte by byte -- rows have no alignment and a
+// pixel of 3 bytes none either.  1: each of the four taps becomes its luma first, then the grey blend runs on the four
+// luma values (a blend of the channels followed by one luma is other integers).  3: the blend per channel, written to
+// planes R, G, B of frame f (dst frame f holds PLANES planes; a frame of zeros is zero in all of them).  The luma is at
+// most 255 * 65536 + 32768 < 2^24; the sums stay those of the grey form.
+template <bool TABLE, int PLANES = 0>
 __global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restrict__ src, int64_t frame_stride, int sh,
                                                         int sw, int64_t pitch, const int64_t* __restrict__ table,
                                                         int dh, int dw, int rows, int strips, int mode,
-                                                        float* __restrict__ dst) {
+                                                        float* __restrict__ dst, int fmt) {
+  constexpr int NP = PLANES == 3 ? 3 : 1;
   __shared__ float lut[256];
   __shared__ int xofs[INGEST_MAX_DW];
   __shared__ uint32_t xw[INGEST_MAX_DW];
@@ -106,7 +125,7 @@ __global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restric
   const int f = blockIdx.x / strips;
   const int y0 = (blockIdx.x - f * strips) * rows;
   const int nr = min(rows, dh - y0);
-  float* out = dst + ((int64_t)f * dh + y0) * dw;
+  float* out = dst + ((int64_t)f * NP * dh + y0) * dw;
   if constexpr (TABLE) {
     const int64_t* e = table + 4 * (int64_t)f;
     src = reinterpret_cast<const uint8_t*>(e[0]);
@@ -114,7 +133,9 @@ __global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restric
     sw = (int)e[2];
     pitch = e[3];
     if (src == nullptr) {
-      for (int i = tid; i < nr * dw; i += 256) out[i] = 0.f;
+#pragma unroll
+      for (int c = 0; c < NP; ++c)
+        for (int i = tid; i < nr * dw; i += 256) out[(int64_t)c * dh * dw + i] = 0.f;
       return;
     }
   } else {
@@ -130,23 +151,58 @@ __global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restric
     const int sy = yofs[r], ya = (int)(yw[r] & 0xffffu), yb = (int)(yw[r] >> 16);
     const uint8_t* s0 = src + (int64_t)sy * pitch;
     const uint8_t* s1 = src + (int64_t)min(sy + 1, sh - 1) * pitch;
-    f32x4 o;
+    f32x4 o[NP];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int x = min(x4 + e, dw - 1);  // (a group past the row's end repeats its last pixel and stores none of it)
       const int sx = xofs[x], xa = (int)(xw[x] & 0xffffu), xb = (int)(xw[x] >> 16);
-      const int h0 = sx + 1 < sw ? s0[sx] * xa + s0[sx + 1] * xb : s0[sx] * INGEST_ONE;
-      const int h1 = sx + 1 < sw ? s1[sx] * xa + s1[sx + 1] * xb : s1[sx] * INGEST_ONE;
-      const int v = (ya * h0 + yb * h1 + (1 << 21)) >> 22;
-      o[e] = lut[min(255, max(0, v))];
-    }
-    float* p = out + (int64_t)r * dw + x4;
-    if (x4 + 4 <= dw && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-      *reinterpret_cast<f32x4*>(p) = o;
-    } else {
+      if constexpr (PLANES == 0) {
+        const int h0 = sx + 1 < sw ? s0[sx] * xa + s0[sx + 1] * xb : s0[sx] * INGEST_ONE;
+        const int h1 = sx + 1 < sw ? s1[sx] * xa + s1[sx + 1] * xb : s1[sx] * INGEST_ONE;
+        const int v = (ya * h0 + yb * h1 + (1 << 21)) >> 22;
+        o[0][e] = lut[min(255, max(0, v))];
+      } else {
+        // the right-hand tap of the last column is the column itself (always in bounds) and its weight unused
+        const bool two = sx + 1 < sw;
+        const int step = ingest_step(fmt), ka = sx * step, kb = (two ? sx + 1 : sx) * step;
+        const int cofs[3] = {ingest_r(fmt), 1, ingest_b(fmt)};
+        int t[4][3];  // taps (row 0 left, row 0 right, row 1 left, row 1 right) x (R, G, B)
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (x4 + e < dw) p[e] = o[e];
+        for (int c = 0; c < 3; ++c) {
+          t[0][c] = s0[ka + cofs[c]];
+          t[1][c] = s0[kb + cofs[c]];
+          t[2][c] = s1[ka + cofs[c]];
+          t[3][c] = s1[kb + cofs[c]];
+        }
+        if constexpr (PLANES == 1) {
+          int l[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) l[q] = luma_u8(t[q][0], t[q][1], t[q][2]);
+          const int h0 = two ? l[0] * xa + l[1] * xb : l[0] * INGEST_ONE;
+          const int h1 = two ? l[2] * xa + l[3] * xb : l[2] * INGEST_ONE;
+          const int v = (ya * h0 + yb * h1 + (1 << 21)) >> 22;
+          o[0][e] = lut[min(255, max(0, v))];
+        } else {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int h0 = two ? t[0][c] * xa + t[1][c] * xb : t[0][c] * INGEST_ONE;
+            const int h1 = two ? t[2][c] * xa + t[3][c] * xb : t[2][c] * INGEST_ONE;
+            const int v = (ya * h0 + yb * h1 + (1 << 21)) >> 22;
+            o[c][e] = lut[min(255, max(0, v))];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+      float* p = out + ((int64_t)c * dh + r) * dw + x4;
+      if (x4 + 4 <= dw && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        *reinterpret_cast<f32x4*>(p) = o[c];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (x4 + e < dw) p[e] = o[c][e];
+      }
     }
   }
 }
@@ -168,13 +224,31 @@ static int ingest_check_output(const char* fn, int64_t nf, int dh, int dw, int m
 }
 
 // one source frame; `who` names it in the error text ("" for the uniform entry, "entry 3 " for a table row)
-static int ingest_check_source(const char* fn, const std::string& who, int64_t sh, int64_t sw, int64_t pitch) {
+// (step: bytes per pixel, 1 for grey)
+static int ingest_check_source(const char* fn, const std::string& who, int64_t sh, int64_t sw, int64_t pitch,
+                               int step = 1) {
   const std::string name = std::string(fn) + ": " + who;
   VAD_CHECK(sh >= 1 && sw >= 1, name + "sh and sw must be >= 1 (got sh = " + std::to_string(sh) + ", sw = " +
                                     std::to_string(sw) + ")");
-  VAD_CHECK(pitch >= sw, name + "pitch " + std::to_string(pitch) + " is less than sw = " + std::to_string(sw));
+  if (step == 1) {
+    VAD_CHECK(pitch >= sw, name + "pitch " + std::to_string(pitch) + " is less than sw = " + std::to_string(sw));
+  } else {
+    VAD_CHECK(sw < (1ll << 31) && pitch >= step * sw,
+              name + "pitch " + std::to_string(pitch) + " is less than " + std::to_string(step) + " * sw = " +
+                  std::to_string(step * sw) + " (sw = " + std::to_string(sw) + ")");
+  }
   VAD_CHECK(sh < (1ll << 31) && pitch < (1ll << 31) && sh * pitch < (1ll << 31),
             name + "the frame (sh * pitch bytes) is 2 GB or more");
+  return 0;
+}
+
+// what the colour entry points ask beyond the grey ones: the format, the planes and the larger output
+static int ingest_check_color(const char* fn, int64_t nf, int fmt, int planes, int dh, int dw) {
+  const std::string name(fn);
+  VAD_CHECK(fmt >= 0 && fmt <= 3, name + ": fmt 0 (rgb), 1 (bgr), 2 (rgbx) or 3 (bgrx), got " + std::to_string(fmt));
+  VAD_CHECK(planes == 1 || planes == 3, name + ": planes 1 (grey) or 3 (planar RGB), got " + std::to_string(planes));
+  VAD_CHECK(nf <= ((1ll << 31) - 1) / ((int64_t)planes * dh * dw * 4),
+            name + ": dst (nf * planes * dh * dw * 4 bytes) is 2 GB or more");
   return 0;
 }
 
@@ -205,7 +279,27 @@ int vad_ingest_u8(const uint8_t* src, int64_t nf, int sh, int sw, int64_t pitch,
   VAD_CHECK(frame_stride >= 0, "vad_ingest_u8: frame_stride must be >= 0");
   const int strips = (int)cdiv(dh, rows);
   hipLaunchKernelGGL(ingest_u8_kernel<false>, dim3((unsigned)(nf * strips)), dim3(256), 0, (hipStream_t)stream, src,
-                     frame_stride, sh, sw, pitch, (const int64_t*)nullptr, dh, dw, rows, strips, mode, dst);
+                     frame_stride, sh, sw, pitch, (const int64_t*)nullptr, dh, dw, rows, strips, mode, dst, 0);
+  VAD_LAUNCH_CHECK();
+  return 0;
+}
+
+int vad_ingest_u8_color(const uint8_t* src, int64_t nf, int sh, int sw, int64_t pitch, int64_t frame_stride, int fmt,
+                        int planes, int dh, int dw, int mode, float* dst, void* stream) {
+  VAD_CHECK(src != nullptr, "vad_ingest_u8_color: null src");
+  int rows = 0;
+  VAD_TRY(ingest_check_output("vad_ingest_u8_color", nf, dh, dw, mode, dst, rows));
+  VAD_TRY(ingest_check_color("vad_ingest_u8_color", nf, fmt, planes, dh, dw));
+  VAD_TRY(ingest_check_source("vad_ingest_u8_color", "", sh, sw, pitch, ingest_step(fmt)));
+  VAD_CHECK(frame_stride >= 0, "vad_ingest_u8_color: frame_stride must be >= 0");
+  const int strips = (int)cdiv(dh, rows);
+  const dim3 grid((unsigned)(nf * strips));
+  if (planes == 1)
+    hipLaunchKernelGGL((ingest_u8_kernel<false, 1>), grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, sh, sw,
+                       pitch, (const int64_t*)nullptr, dh, dw, rows, strips, mode, dst, fmt);
+  else
+    hipLaunchKernelGGL((ingest_u8_kernel<false, 3>), grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, sh, sw,
+                       pitch, (const int64_t*)nullptr, dh, dw, rows, strips, mode, dst, fmt);
   VAD_LAUNCH_CHECK();
   return 0;
 }
@@ -233,8 +327,49 @@ int vad_ingest_u8_table(const int64_t* host_table, int64_t nf, int dh, int dw, i
   const int strips = (int)cdiv(dh, rows);
   hipLaunchKernelGGL(ingest_u8_kernel<true>, dim3((unsigned)(nf * strips)), dim3(256), 0, (hipStream_t)stream,
                      (const uint8_t*)nullptr, (int64_t)0, 0, 0, (int64_t)0, static_cast<const int64_t*>(dev_table), dh,
-                     dw, rows, strips, mode, dst);
+                     dw, rows, strips, mode, dst, 0);
   VAD_LAUNCH_CHECK();
+  return 0;
+}
+
+int vad_ingest_u8_color_table(const int64_t* host_table, int64_t nf, int fmt, int planes, int dh, int dw, int mode,
+                              float* dst, void* dev_table, void* stream) {
+  const char* fn = "vad_ingest_u8_color_table";
+  VAD_CHECK(host_table && dev_table, std::string(fn) + ": null table (host_table or dev_table)");
+  VAD_CHECK((reinterpret_cast<uintptr_t>(dev_table) & 15) == 0, std::string(fn) + ": dev_table must be 16-B aligned");
+  int rows = 0;
+  VAD_TRY(ingest_check_output(fn, nf, dh, dw, mode, dst, rows));
+  VAD_TRY(ingest_check_color(fn, nf, fmt, planes, dh, dw));
+  for (int64_t f = 0; f < nf; ++f) {
+    const int64_t* e = host_table + 4 * f;
+    if (e[0] == 0) continue;  // a frame of zeros: its sizes are not read
+    VAD_TRY(ingest_check_source(fn, "entry " + std::to_string(f) + ": ", e[1], e[2], e[3], ingest_step(fmt)));
+  }
+  VAD_HIP(hipMemcpyAsync(dev_table, host_table, (size_t)nf * 32, hipMemcpyHostToDevice, (hipStream_t)stream));
+  const int strips = (int)cdiv(dh, rows);
+  const dim3 grid((unsigned)(nf * strips));
+  const int64_t* tab = static_cast<const int64_t*>(dev_table);
+  if (planes == 1)
+    hipLaunchKernelGGL((ingest_u8_kernel<true, 1>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)nullptr,
+                       (int64_t)0, 0, 0, (int64_t)0, tab, dh, dw, rows, strips, mode, dst, fmt);
+  else
+    hipLaunchKernelGGL((ingest_u8_kernel<true, 3>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)nullptr,
+                       (int64_t)0, 0, 0, (int64_t)0, tab, dh, dw, rows, strips, mode, dst, fmt);
+  VAD_LAUNCH_CHECK();
+  return 0;
+}
+
+int vad_luma_u8(const uint8_t* src, int sh, int sw, int64_t pitch, int fmt, uint8_t* dst) {
+  VAD_CHECK(src && dst && sh > 0 && sw > 0, "vad_luma_u8: bad arguments");
+  VAD_CHECK(fmt >= 0 && fmt <= 3, "vad_luma_u8: fmt 0 (rgb), 1 (bgr), 2 (rgbx) or 3 (bgrx), got " + std::to_string(fmt));
+  const int step = ingest_step(fmt), ro = ingest_r(fmt), bo = ingest_b(fmt);
+  VAD_CHECK(pitch >= (int64_t)step * sw, "vad_luma_u8: pitch " + std::to_string(pitch) + " is less than " +
+                                             std::to_string(step) + " * sw = " + std::to_string((int64_t)step * sw));
+  for (int y = 0; y < sh; ++y) {
+    const uint8_t* s = src + (int64_t)y * pitch;
+    uint8_t* d = dst + (int64_t)y * sw;
+    for (int x = 0; x < sw; ++x, s += step) d[x] = (uint8_t)luma_u8(s[ro], s[1], s[bo]);
+  }
   return 0;
 }
 

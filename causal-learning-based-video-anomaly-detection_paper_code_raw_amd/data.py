@@ -41,6 +41,38 @@ def _decode_gray(path: str, size_hw: tuple[int, int] | None, pil_resize: bool = 
     return np.ascontiguousarray(a)
 
 
+COLOR_FORMATS = ("rgb", "bgr", "rgbx", "bgrx")  # packed pixel layouts; the index is the library's fmt
+
+
+def _color_format(color, what):
+    """(fmt, bytes per pixel) of a packed colour format name (ValueError for anything else)."""
+    if not isinstance(color, str) or color not in COLOR_FORMATS:
+        raise ValueError(f"{what}: color must be None or one of {COLOR_FORMATS}, got {color!r}")
+    fmt = COLOR_FORMATS.index(color)
+    return fmt, 4 if fmt >= 2 else 3
+
+
+def luma_u8(frames, color: str) -> np.ndarray:
+    """Grey of packed colour frames, uint8 (k, Hs, Ws, C) or (Hs, Ws, C) with C = 3 (rgb, bgr) or 4 (rgbx, bgrx; the
+    fourth byte is not read) -> (k, Hs, Ws) or (Hs, Ws): L = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16, PIL's
+    convert("L") (native vad_luma_u8).  ``ingest_u8(frames, size, mode, color=color)`` equals luma_u8 -> resize_u8 ->
+    the mode's float32 expression."""
+    fmt, step = _color_format(color, "luma_u8")
+    a = frames.numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+    if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.shape[-1] != step or a.shape[-2] < 1 or a.shape[-3] < 1:
+        raise ValueError(f"luma_u8: uint8 frames (k, Hs, Ws, {step}) or (Hs, Ws, {step}) for color={color!r}, got "
+                         f"{a.dtype} {tuple(a.shape)}")
+    hs, ws = a.shape[-3:-1]
+    if a.strides[-1] != 1 or a.strides[-2] != step or (hs > 1 and a.strides[-3] < step * ws):
+        a = np.ascontiguousarray(a)  # (rows may be strided; pixels and channels must be packed)
+    pitch = a.strides[-3] if hs > 1 else step * ws
+    out = np.empty(a.shape[:-1], dtype=np.uint8)
+    L = nat.lib()
+    for src, dst in zip(a if a.ndim == 4 else [a], out if a.ndim == 4 else [out]):
+        nat.check(L.vad_luma_u8(src.ctypes.data, hs, ws, pitch, fmt, dst.ctypes.data))
+    return out
+
+
 def resize_u8(img: np.ndarray, h: int, w: int) -> np.ndarray:
     """Bilinear resize of a (H, W) uint8 image (native vad_resize_u8)."""
     src = np.ascontiguousarray(img, dtype=np.uint8)
@@ -288,9 +320,23 @@ def prefetch(loader, stager: ClipStager, with_ready: bool = False):
 INGEST_MODES = (0, 1, 2)  # (u8 - 0.5) / 0.5 (cad), u8 / 255 (mc, bbox), clamp(u8 / 255, 0.001, 0.999) (cad1:110-114)
 
 
-def check_u8_frames(frames, what="ingest_u8") -> torch.Tensor:
+def check_u8_frames(frames, what="ingest_u8", color=None) -> torch.Tensor:
     """The ValueErrors of a u8 source, raised before any device work: a uint8 tensor (k, Hs, Ws) or (k, 1, Hs, Ws)
-    with Hs, Ws >= 1.  Returns it as (k, Hs, Ws) (a view)."""
+    with Hs, Ws >= 1.  Returns it as (k, Hs, Ws) (a view).  With a colour format: a uint8 tensor (k, Hs, Ws, C) of
+    packed pixels, C = 3 (rgb, bgr) or 4 (rgbx, bgrx), returned as it is."""
+    if color is not None:
+        _, step = _color_format(color, what)
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+            raise ValueError(f"{what}: color={color!r} takes uint8 frames of shape (k, Hs, Ws, {step}), got "
+                             f"{tuple(getattr(frames, 'shape', ())) or type(frames).__name__}")
+        if frames.dtype != torch.uint8:
+            raise ValueError(f"{what}: frames must be uint8, got {frames.dtype}")
+        if frames.shape[3] != step:
+            raise ValueError(f"{what}: color={color!r} has {step} bytes per pixel, but the last dimension of the "
+                             f"frames {tuple(frames.shape)} is {frames.shape[3]}")
+        if frames.shape[1] < 1 or frames.shape[2] < 1:
+            raise ValueError(f"{what}: empty frames {tuple(frames.shape)}")
+        return frames
     if not isinstance(frames, torch.Tensor) or frames.dim() not in (3, 4):
         raise ValueError(f"{what}: uint8 frames of shape (k, Hs, Ws) or (k, 1, Hs, Ws), got "
                          f"{tuple(getattr(frames, 'shape', ())) or type(frames).__name__}")
@@ -318,6 +364,14 @@ def _check_size_mode(size_hw, mode, what="ingest_u8"):
     return h, w
 
 
+def _check_planes(planes, color, what="ingest_u8") -> int:
+    if isinstance(planes, bool) or planes not in (1, 3):
+        raise ValueError(f"{what}: planes must be 1 (grey) or 3 (planar RGB), got {planes!r}")
+    if planes == 3 and color is None:
+        raise ValueError(f"{what}: planes=3 needs colour frames (color= one of {COLOR_FORMATS})")
+    return int(planes)
+
+
 def ingest_device(model, sources, what) -> torch.device:
     """The device a push_u8 runs on: the model's, which must be a HIP device -- it reads host sources -- and the one
     every device source is on (ValueError, before any device work)."""
@@ -331,14 +385,16 @@ def ingest_device(model, sources, what) -> torch.device:
 
 class U8Ingest:
     """u8 frames at the source's own size -> fp32 (k, 1, H, W) on the device, resized as ``resize_u8`` resizes and
-    normalised, in one launch on the current stream (vad_ingest_u8 / vad_ingest_u8_table).  Holds what that needs
+    normalised, in one launch on the current stream (vad_ingest_u8 / vad_ingest_u8_table; packed colour frames
+    (k, Hs, Ws, C) with ``color``: vad_ingest_u8_color / _table, grey by ``luma_u8`` or, with planes=3, the planes
+    R, G, B as (k, 3, H, W)).  Holds what that needs
     besides the kernel: a pinned slot for pageable sources, the device addresses of pinned sources it has seen, and --
     once ``table`` is used -- the pinned frame table with its device copy.
 
     A source may be on the device, in pinned host memory (read in place over PCIe: it must stay unchanged until the
     work queued by the call has run) or in pageable host memory (copied through the slot, which waits for the launch
-    that last read it).  Rows may be strided; a source whose pixels within a row are not adjacent is made contiguous
-    first."""
+    that last read it).  Rows may be strided; a source whose pixels within a row are not adjacent (colour: whose
+    pixels are not ``step`` bytes apart with the channels packed) is made contiguous first."""
 
     def __init__(self, device):
         self.device = torch.device(device)
@@ -365,10 +421,13 @@ class U8Ingest:
             self._done = torch.cuda.Event()
         self._done.record(torch.cuda.current_stream(self.device))
 
-    def _sources(self, chunks):
-        """Per chunk (k, Hs, Ws): (address of frame 0, Hs, Ws, row pitch, frame stride), strides in bytes."""
+    def _sources(self, chunks, step=1):
+        """Per chunk (k, Hs, Ws), with step > 1 (k, Hs, Ws, step): (address of frame 0, Hs, Ws, row pitch, frame
+        stride), strides in bytes."""
         def readable(x):  # rows of adjacent pixels, pitch >= Ws apart (not an expanded or transposed view)
-            return (x.shape[2] == 1 or x.stride(2) == 1) and (x.shape[1] == 1 or x.stride(1) >= x.shape[2])
+            if step > 1 and x.stride(3) != 1:
+                return False
+            return (x.shape[2] == 1 or x.stride(2) == step) and (x.shape[1] == 1 or x.stride(1) >= step * x.shape[2])
 
         chunks = [x if readable(x) else x.contiguous() for x in chunks]
         pageable = [i for i, x in enumerate(chunks) if not x.is_cuda and not x.is_pinned()]
@@ -392,48 +451,58 @@ class U8Ingest:
                 addr = x.data_ptr()
             else:
                 addr = self._address(x)
-            k, hs, ws = x.shape
-            pitch = x.stride(1) if hs > 1 else ws
+            k, hs, ws = x.shape[:3]
+            pitch = x.stride(1) if hs > 1 else step * ws
             fstride = x.stride(0) if k > 1 else 0
             out.append((addr, hs, ws, pitch, fstride))
         return out
 
-    def _out(self, out, n, h, w):
+    def _out(self, out, n, h, w, planes=1):
         if out is None:
-            return torch.empty(n, 1, h, w, dtype=torch.float32, device=self.device)
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n, 1, h, w)
+            return torch.empty(n, planes, h, w, dtype=torch.float32, device=self.device)
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n, planes, h, w)
                 or not out.is_contiguous() or out.device != self.device or out.data_ptr() % 16):
-            raise ValueError(f"ingest_u8: out must be a contiguous, 16-byte aligned float32 tensor ({n}, 1, {h}, {w}) "
-                             f"on {self.device}")
+            raise ValueError(f"ingest_u8: out must be a contiguous, 16-byte aligned float32 tensor ({n}, {planes}, {h}, "
+                             f"{w}) on {self.device}")
         return out
 
-    def ingest(self, frames, size_hw, mode, out=None) -> torch.Tensor:
-        """frames: uint8 (k, Hs, Ws) or (k, 1, Hs, Ws), k >= 1 -> fp32 (k, 1, H, W), the uniform form."""
-        x = check_u8_frames(frames)
+    def ingest(self, frames, size_hw, mode, out=None, color=None, planes=1) -> torch.Tensor:
+        """frames: uint8 (k, Hs, Ws) or (k, 1, Hs, Ws), k >= 1 -> fp32 (k, 1, H, W), the uniform form.  With
+        color (one of COLOR_FORMATS): packed pixels (k, Hs, Ws, C) -> (k, planes, H, W)."""
+        x = check_u8_frames(frames, color=color)
+        planes = _check_planes(planes, color)
         h, w = _check_size_mode(size_hw, mode)
         if x.shape[0] < 1:
             raise ValueError("ingest_u8: no frame")
         nat.require_hip(torch.empty(0, device=self.device))
-        out = self._out(out, x.shape[0], h, w)
-        (addr, hs, ws, pitch, fstride), = self._sources([x])
+        out = self._out(out, x.shape[0], h, w, planes)
+        fmt, step = (0, 1) if color is None else _color_format(color, "ingest_u8")
+        (addr, hs, ws, pitch, fstride), = self._sources([x], step)
         with torch.cuda.device(self.device):
-            nat.check(nat.lib().vad_ingest_u8(addr, x.shape[0], hs, ws, pitch, fstride, h, w, mode, out.data_ptr(),
-                                              nat.stream_of(self.device)))
+            if color is None:
+                nat.check(nat.lib().vad_ingest_u8(addr, x.shape[0], hs, ws, pitch, fstride, h, w, mode, out.data_ptr(),
+                                                  nat.stream_of(self.device)))
+            else:
+                nat.check(nat.lib().vad_ingest_u8_color(addr, x.shape[0], hs, ws, pitch, fstride, fmt, planes, h, w,
+                                                        mode, out.data_ptr(), nat.stream_of(self.device)))
         self._record()
         return out
 
-    def table(self, chunks, n, size_hw, mode, out=None, capacity=None) -> torch.Tensor:
+    def table(self, chunks, n, size_hw, mode, out=None, capacity=None, color=None, planes=1) -> torch.Tensor:
         """chunks: uint8 tensors (k_i, Hs_i, Ws_i), each of its own size -> fp32 (n, 1, H, W): their frames in order,
         then n - sum(k_i) frames of zeros, in one table-form launch.  capacity: the largest n this object will see
-        (the tables are allocated once)."""
+        (the tables are allocated once).  With color: chunks (k_i, Hs_i, Ws_i, C), all of that one format ->
+        (n, planes, H, W)."""
         h, w = _check_size_mode(size_hw, mode)
-        chunks = [check_u8_frames(x) for x in chunks]
+        planes = _check_planes(planes, color)
+        chunks = [check_u8_frames(x, color=color) for x in chunks]
         total = sum(x.shape[0] for x in chunks)
         if total < 1 or total > n:
             raise ValueError(f"ingest_u8: {total} frames for a batch of {n}")
         nat.require_hip(torch.empty(0, device=self.device))
         L = nat.lib()
-        out = self._out(out, n, h, w)
+        out = self._out(out, n, h, w, planes)
+        fmt, step = (0, 1) if color is None else _color_format(color, "ingest_u8")
         cap = max(n, capacity or 0)
         if self._h_table is None or self._h_table.shape[0] < cap:
             nb = L.vad_ingest_table_bytes(cap)
@@ -442,15 +511,20 @@ class U8Ingest:
             self._wait()
             self._h_table = torch.zeros(cap, 4, dtype=torch.int64).pin_memory()
             self._d_table = torch.zeros(nb // 8, dtype=torch.int64, device=self.device)
-        srcs = self._sources(chunks)
+        srcs = self._sources(chunks, step)
         rows = [(addr + j * fstride, hs, ws, pitch) for x, (addr, hs, ws, pitch, fstride) in zip(chunks, srcs)
                 for j in range(x.shape[0])]
         rows += [(0, 0, 0, 0)] * (n - total)
         self._wait()  # (the device has the table of the launch before)
         self._h_table[:n] = torch.tensor(rows, dtype=torch.int64)
         with torch.cuda.device(self.device):
-            nat.check(L.vad_ingest_u8_table(self._h_table.data_ptr(), n, h, w, mode, out.data_ptr(),
-                                            self._d_table.data_ptr(), nat.stream_of(self.device)))
+            if color is None:
+                nat.check(L.vad_ingest_u8_table(self._h_table.data_ptr(), n, h, w, mode, out.data_ptr(),
+                                                self._d_table.data_ptr(), nat.stream_of(self.device)))
+            else:
+                nat.check(L.vad_ingest_u8_color_table(self._h_table.data_ptr(), n, fmt, planes, h, w, mode,
+                                                      out.data_ptr(), self._d_table.data_ptr(),
+                                                      nat.stream_of(self.device)))
         self._record()
         return out
 
@@ -458,14 +532,20 @@ class U8Ingest:
 _INGESTS = {}
 
 
-def ingest_u8(frames, size_hw, mode, *, out=None) -> torch.Tensor:
+def ingest_u8(frames, size_hw, mode, *, out=None, color=None, planes=1) -> torch.Tensor:
     """uint8 frames (k, Hs, Ws) or (k, 1, Hs, Ws) -> fp32 (k, 1, H, W) on the device, each frame resized to
     size_hw = (H, W) exactly as ``resize_u8`` resizes it and normalised (mode 0: (u8 - 0.5) / 0.5, 1: u8 / 255,
     2: u8 / 255 clamped to 0.001..0.999), by one kernel on the current stream.  frames on the HIP device, in pinned
     host memory (read in place) or in pageable host memory (through a pinned slot); host frames go to ``out``'s
     device, else the current one.  ``score_video(ingest_u8(video_u8, (H, W), 0))`` scores a u8 video.  The state
-    lives in one U8Ingest per device; a stream owns its own."""
-    x = check_u8_frames(frames)
+    lives in one U8Ingest per device; a stream owns its own.
+
+    color ("rgb", "bgr", "rgbx" or "bgrx"): frames are packed colour pixels, uint8 (k, Hs, Ws, 3) or (k, Hs, Ws, 4)
+    (the X byte is never read).  planes=1 -> (k, 1, H, W): ``luma_u8`` of the source, then the above.  planes=3 ->
+    (k, 3, H, W): the planes R, G, B, each ``resize_u8`` of its channel and normalised --
+    ``bbox_model.score_video(ingest_u8(video_u8, (64, 64), 1, color="bgr", planes=3))``."""
+    x = check_u8_frames(frames, color=color)
+    _check_planes(planes, color)
     if x.is_cuda:
         dev = x.device
     elif out is not None:
@@ -476,4 +556,4 @@ def ingest_u8(frames, size_hw, mode, *, out=None) -> torch.Tensor:
     ing = _INGESTS.get(dev)
     if ing is None:
         ing = _INGESTS[dev] = U8Ingest(dev)
-    return ing.ingest(x, size_hw, mode, out=out)
+    return ing.ingest(x, size_hw, mode, out=out, color=color, planes=planes)

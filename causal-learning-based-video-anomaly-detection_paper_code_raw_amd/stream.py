@@ -66,10 +66,11 @@ def check_push(model, frames, max_push, frame_size) -> torch.Tensor:
     return frames
 
 
-def check_push_u8(model, frames, max_push, what="push_u8") -> torch.Tensor:
-    """The ValueErrors of a stream's push_u8, raised before any device work; returns the frames as (k, Hs, Ws)."""
+def check_push_u8(model, frames, max_push, what="push_u8", color=None) -> torch.Tensor:
+    """The ValueErrors of a stream's push_u8, raised before any device work; returns the frames as (k, Hs, Ws), with a
+    colour format as (k, Hs, Ws, C)."""
     from .data import check_u8_frames
-    x = check_u8_frames(frames, what)
+    x = check_u8_frames(frames, what, color)
     k = x.shape[0]
     if k < 1 or k > max_push:
         raise ValueError(f"{what}: between 1 and max_push = {max_push} frames per push, got {k}")
@@ -120,21 +121,22 @@ class CadStream:
         absolute; detections: the k pushed frames; empty tensors when no window completes)."""
         return self._push(check_push(self.model, frames, self.max_push, self.frame_size))
 
-    def push_u8(self, frames) -> dict:
+    def push_u8(self, frames, color=None) -> dict:
         """frames: the next 1 <= k <= max_push frames as uint8 (k, Hs, Ws) or (k, 1, Hs, Ws) at any source size, on
         the device, in pinned host memory (read in place) or in pageable host memory.  One launch resizes them to the
         stream's frame size as data.resize_u8 does and normalises them as (u8 - 0.5) / 0.5 into a buffer the stream
         owns (data.U8Ingest); the rest is push: push_u8(u8) returns what push returns for the same frames converted
-        on the host.  Without frame_size the first push fixes it to the source size."""
+        on the host.  Without frame_size the first push fixes it to the source size.  With color ("rgb", "bgr", "rgbx" or "bgrx") the frames are packed colour pixels, uint8
+        (k, Hs, Ws, 3) or (k, Hs, Ws, 4), and the same launch takes their grey first (data.luma_u8, PIL's convert("L"))."""
         from .data import U8Ingest, ingest_device
         check_model(self.model)
-        x = check_push_u8(self.model, frames, self.max_push)
+        x = check_push_u8(self.model, frames, self.max_push, color=color)
         dev = ingest_device(self.model, [x], "push_u8")
-        size = self.frame_size or tuple(x.shape[1:])
+        size = self.frame_size or tuple(x.shape[1:3])
         if self._ingest is None:
             self._ingest = U8Ingest(dev)
             self._u8 = torch.empty(self.max_push, 1, *size, dtype=torch.float32, device=dev)
-        return self._push(self._ingest.ingest(x, size, 0, out=self._u8[:x.shape[0]]))
+        return self._push(self._ingest.ingest(x, size, 0, out=self._u8[:x.shape[0]], color=color))
 
     def _push(self, x) -> dict:
         """push's body: x (k, 1, H, W), checked."""

@@ -85,9 +85,10 @@ def check_group_push(model, frames, num_streams, max_push, frame_size):
     return chunks, ks, frame_size
 
 
-def check_group_push_u8(model, frames, num_streams, max_push, check_model=check_model):
+def check_group_push_u8(model, frames, num_streams, max_push, check_model=check_model, color=None):
     """The ValueErrors of a group's push_u8, raised before any device work.  Returns (chunks, ks): per stream the
-    frames as uint8 (k_s, Hs_s, Ws_s), each stream at its own source size, or None where k_s = 0."""
+    frames as uint8 (k_s, Hs_s, Ws_s) -- with a colour format (k_s, Hs_s, Ws_s, C) -- each stream at its own source
+    size, or None where k_s = 0."""
     from .data import check_u8_frames
     check_model(model)
     if not isinstance(frames, (list, tuple)) or len(frames) != num_streams:
@@ -100,7 +101,7 @@ def check_group_push_u8(model, frames, num_streams, max_push, check_model=check_
             chunks.append(None)
             ks.append(0)
             continue
-        x = check_u8_frames(x, f"push_u8: stream {s}")
+        x = check_u8_frames(x, f"push_u8: stream {s}", color)
         k = x.shape[0]
         if k > max_push:
             raise ValueError(f"push_u8: stream {s}: at most max_push = {max_push} frames per push, got {k}")
@@ -176,24 +177,26 @@ class CadStreamGroup:
         x = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
         return self._push(x, ks, size)
 
-    def push_u8(self, frames) -> list:
+    def push_u8(self, frames, color=None) -> list:
         """frames: a sequence of num_streams entries, entry s the next 0 <= k_s <= max_push frames of camera s as uint8
         (k_s, Hs, Ws) or (k_s, 1, Hs, Ws), or None; cameras may differ in source size and in where their frames lie
         (device, pinned host memory read in place, pageable host memory).  One table-form launch resizes every frame
         to the group's frame size as data.resize_u8 does, normalises it as (u8 - 0.5) / 0.5 and writes the zero
         padding, into a buffer the group owns (data.U8Ingest.table); the rest is push: push_u8 returns what push
         returns for the same frames converted on the host.  Without frame_size the first push fixes it to the size of
-        its first source."""
+        its first source.  With color ("rgb", "bgr", "rgbx" or "bgrx") every camera brings packed colour pixels,
+        uint8 (k_s, Hs, Ws, 3) or (k_s, Hs, Ws, 4) -- one format for the whole call -- and the same launch takes their
+        grey first (data.luma_u8, PIL's convert("L"))."""
         from .data import U8Ingest, ingest_device
-        chunks, ks = check_group_push_u8(self.model, frames, self.num_streams, self.max_push)
+        chunks, ks = check_group_push_u8(self.model, frames, self.num_streams, self.max_push, color=color)
         live = [x for x in chunks if x is not None]
         dev = ingest_device(self.model, live, "push_u8")
-        size = self.frame_size or tuple(live[0].shape[1:])
+        size = self.frame_size or tuple(live[0].shape[1:3])
         if self._ingest is None:
             self._ingest = U8Ingest(dev)
             self._u8 = torch.empty(self.max_frames, 1, *size, dtype=torch.float32, device=dev)
         P = padded_frames(sum(ks), self.max_frames)
-        x = self._ingest.table(live, P, size, 0, out=self._u8[:P], capacity=self.max_frames)
+        x = self._ingest.table(live, P, size, 0, out=self._u8[:P], capacity=self.max_frames, color=color)
         return self._push(x, ks, size)
 
     def _push(self, x, ks, size) -> list:

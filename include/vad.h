@@ -448,6 +448,12 @@ int64_t vad_bbox_workspace_bytes(const vad_bbox_plan* plan);
 int vad_bbox_bind(vad_bbox_plan* plan, void* workspace, const float* params);
 /* scores (B,), adj (B,16,16), features (B,1024, nullable) */
 int vad_bbox_forward(vad_bbox_plan* plan, const float* x, float* scores, float* adj, float* features, void* stream);
+/* The plan's B clips as windows of a video: frames (n_frames, 3, H, W) fp32 frame-major planar, window b
+ * = frames first + b * stride .. + T - 1, read in place by the first layer (its temporal zero padding is per window, as
+ * for a clip); the rest of the forward is vad_bbox_forward's.  Refused before any launch: a null pointer, stride < 1,
+ * first < 0, first + (B - 1) * stride + T > n_frames, an unbound plan. */
+int vad_bbox_windows_forward(vad_bbox_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
+                             float* scores, float* adj, float* features, void* stream);
 /* Test seams.  vad_bbox_forward is encoder (x -> features) then head (features -> scores, adj);
  * vad_bbox_head_forward runs the head alone -- the causal_net and classifier GEMMs and the sigmoid tail -- on feature
  * rows (B, 1024) the caller chose.  vad_bbox_debug_buffer hands out the workspace arrays of the last forward:
@@ -627,6 +633,24 @@ int vad_ingest_u8(const uint8_t* src, int64_t nf, int sh, int sw, int64_t pitch,
 int64_t vad_ingest_table_bytes(int64_t nf);
 int vad_ingest_u8_table(const int64_t* host_table, int64_t nf, int dh, int dw, int mode, float* dst, void* dev_table,
                         void* stream);
+
+/* Colour ingest: packed colour pixels of step bytes with R, G, B at fixed byte offsets --
+ * fmt 0 rgb, 1 bgr (step 3), 2 rgbx, 3 bgrx (step 4; the fourth byte is never read) -- rows pitch >= step * sw bytes
+ * apart, no alignment; everything else as the grey pair above, whose checks these take over.
+ * planes 1: fp32 (nf, 1, dh, dw), grey.  Luma L = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16 (PIL's
+ *   convert("L")) of each of a pixel's four source taps, then vad_resize_u8's blend of the four luma values and the
+ *   mode's pixel function: bit for bit vad_luma_u8 at the source size -> vad_resize_u8 -> the normalisation.
+ * planes 3: fp32 (nf, 3, dh, dw), planes R, G, B whatever the source order; each plane is vad_resize_u8 of that channel
+ *   and the mode's pixel function (mode 1: the bbox scorer's cv2.resize -> BGR2RGB -> / 255, bbox:399-411).
+ * dst (nf * planes * dh * dw * 4 bytes) stays below 2 GB.  The table form reads the grey form's rows (address, sh, sw,
+ * pitch; vad_ingest_table_bytes); address 0 writes zeros to all planes of the frame.  fmt and planes hold for the whole
+ * launch.
+ * vad_luma_u8 (host): the same luma of one (sh, sw) frame of packed pixels into dst (sh, sw), contiguous. */
+int vad_luma_u8(const uint8_t* src, int sh, int sw, int64_t pitch, int fmt, uint8_t* dst);
+int vad_ingest_u8_color(const uint8_t* src, int64_t nf, int sh, int sw, int64_t pitch, int64_t frame_stride, int fmt,
+                        int planes, int dh, int dw, int mode, float* dst, void* stream);
+int vad_ingest_u8_color_table(const int64_t* host_table, int64_t nf, int fmt, int planes, int dh, int dw, int mode,
+                              float* dst, void* dev_table, void* stream);
 
 /* Plan options.  "conv_bf16" (0/1): the 3x3 convs of the backbone run on bf16 operands with fp32 accumulation
  * (BASELINE config 4's bf16 compute; BN, pooling, heads, losses and the optimizer stay fp32).  Default 0: fp32
