@@ -7,7 +7,7 @@ start of the stream, lives in slot ``g mod cap`` -- and scores, at every push, t
 re-reads the window's raw frames, so the ring holds them too: lat [cap][64], gx [cap][256] and pix [cap][4096], 17.25
 KB per slot.
 
-Why cap slots are enough is stream.py's argument; the schedule is its stream_schedule.
+Why cap slots are enough is stream.py's argument; the schedule is stream_util.stream_schedule.
 
 Window w (frames ``w * stride .. w * stride + window - 1``) returns what score_video returns for it: the same stream
 pushed in any chunking gives the results of score_video on the same frames.
@@ -18,7 +18,7 @@ import torch
 
 from . import _native as nat
 from .ae_video import HW, LATENT
-from .stream import _positive_int, check_push_u8, stream_schedule
+from .stream_util import _positive_int, check_push_u8, stream_schedule, u8_buffer
 
 _RING_FIELDS = {"lat": (0, LATENT), "gx": (1, 4 * LATENT), "pix": (2, HW * HW)}
 
@@ -98,14 +98,12 @@ class AeStream:
         0.001..0.999 (cad1:110-114), into a buffer the stream owns (data.U8Ingest); the rest is push: push_u8(u8)
         returns what push returns for the same frames converted on the host.  With color ("rgb", "bgr", "rgbx" or "bgrx") the frames are packed colour pixels, uint8
         (k, Hs, Ws, 3) or (k, Hs, Ws, 4), and the same launch takes their grey first (data.luma_u8, PIL's convert("L"))."""
-        from .data import U8Ingest, ingest_device
+        from .data import ingest_device
         check_model(self.model)
         x = check_push_u8(self.model, frames, self.max_push, color=color)
         dev = ingest_device(self.model, [x], "push_u8")
-        if self._ingest is None:
-            self._ingest = U8Ingest(dev)
-            self._u8 = torch.empty(self.max_push, 1, HW, HW, dtype=torch.float32, device=dev)
-        return self._push(self._ingest.ingest(x, (HW, HW), 2, out=self._u8[:x.shape[0]], color=color))
+        ingest, buf = u8_buffer(self, dev, self.max_push, (HW, HW))
+        return self._push(ingest.ingest(x, (HW, HW), 2, out=buf[:x.shape[0]], color=color))
 
     def _push(self, x) -> dict:
         """push's body: x (k, 1, 64, 64), checked."""

@@ -9,12 +9,13 @@ vad_ae_windows_forward_group).
 Memory is one ring allocation of ``num_streams * cap`` slots, cap = window + max_push - 1 (ae_stream.py's three arrays
 lat, gx and pix over that many slots): ring s occupies slots ``s * cap .. (s + 1) * cap - 1`` of each array and frame
 g of stream s lives in slot ``s * cap + g mod cap``; stream.py's argument for why cap slots suffice holds per stream.
-Where a frame goes and which slots a window reads are tables built on the host (stream_group.group_schedule, whose
-key column is not used here), validated by the library and copied to the device once per stage.
+Where a frame goes and which slots a window reads are tables built on the host (stream_util.group_schedule, whose
+key column is not used here, held in a stream_util.GroupTables), validated by the library (csrc/group_table.h) and
+copied to the device once per stage.
 
 The ``F = sum of k_s`` frames of a push are zero-padded to the next power of two (at most num_streams * max_push), the
 padding frames being stored nowhere, so a group creates at most ``ceil(log2(num_streams * max_push)) + 1`` plans
-instead of one per distinct F (stream_group.padded_frames).
+instead of one per distinct F (stream_util.padded_frames).
 
 Stream s returns what ``model.open_stream(window, stride, max_push=max_push, return_reconstructions=...)`` returns
 for the same history of frames.
@@ -26,36 +27,23 @@ import torch
 from . import _native as nat
 from .ae_stream import check_model, ring_field
 from .ae_video import HW, LATENT
-from .stream import _positive_int, stream_schedule
-from .stream_group import check_group_push_u8, group_schedule, padded_frames
+from .stream_util import (GroupTables, _positive_int, gather_padded, group_schedule, padded_frames,  # noqa: F401
+                          per_stream, stream_schedule, u8_buffer, walk_group_frames, walk_group_frames_u8)
 
 
 def check_group_push(model, frames, num_streams, max_push):
     """The ValueErrors of AeStreamGroup.push, raised before any device work.  Returns (chunks, ks): per stream the
     frames as (k_s, 1, 64, 64), or None where k_s = 0."""
     check_model(model)
-    if not isinstance(frames, (list, tuple)) or len(frames) != num_streams:
-        got = f"{len(frames)} entries" if isinstance(frames, (list, tuple)) else type(frames).__name__
-        raise ValueError(f"push: a list or tuple of num_streams = {num_streams} entries (frames (k, 1, 64, 64) or "
-                         f"None), got {got}")
-    chunks, ks = [], []
-    for s, x in enumerate(frames):
-        if x is None:
-            chunks.append(None)
-            ks.append(0)
-            continue
+
+    def check_one(s, x):
         if not isinstance(x, torch.Tensor) or x.dim() != 4 or tuple(x.shape[1:]) != (1, HW, HW):
             raise ValueError(f"push: stream {s}: frames of shape (k, 1, 64, 64) or None (the encoder's "
                              "Linear(128*4*4) fixes 64x64 single-channel frames, cad1:151), got "
                              f"{tuple(getattr(x, 'shape', ()))}")
-        k = x.shape[0]
-        if k > max_push:
-            raise ValueError(f"push: stream {s}: at most max_push = {max_push} frames per push, got {k}")
-        chunks.append(x if k > 0 else None)
-        ks.append(k)
-    if sum(ks) == 0:
-        raise ValueError("push: no stream brought a frame")
-    return chunks, ks
+        return x
+
+    return walk_group_frames(frames, num_streams, max_push, "push", check_one, "frames (k, 1, 64, 64) or None")
 
 
 class AeStreamGroup:
@@ -94,17 +82,14 @@ class AeStreamGroup:
 
     def _allocate(self, L, dev):
         nfl = L.vad_ae_ring_floats(self.total_slots)
-        nb = L.vad_ae_group_table_bytes(self.max_frames, self.max_frames)
-        if nfl < 0 or nb < 0:
+        if nfl < 0:
             nat.check(1)
         self._ring = torch.zeros(nfl, dtype=torch.float32, device=dev)
-        # the device table (destinations as int32 from byte 0) and the pinned host tables the library copies from.
+        # the device table and the pinned host tables the library copies from (stream_util.GroupTables).
         # Unlike CadStreamGroup.push, a push here ends with no host read, so it may return -- and the next push begin
         # -- before the device has copied the tables: _copied is recorded on the stream behind the last table copy of
         # a push, and the next push waits for it before it writes the host tables again (it has normally passed)
-        self._table = torch.zeros((nb + 3) // 4, dtype=torch.int32, device=dev)
-        self._h_dst = torch.empty(self.max_frames, dtype=torch.int32).pin_memory()
-        self._h_win = torch.empty(self.max_frames, 2, dtype=torch.int64).pin_memory()
+        self._tables = GroupTables(L.vad_ae_group_table_bytes, self.max_frames, 2, dev)
         self._copied = torch.cuda.Event()
 
     def push(self, frames) -> list:
@@ -116,13 +101,7 @@ class AeStreamGroup:
         for x in live:
             nat.require_hip(x)
         F = sum(ks)
-        P = padded_frames(F, self.max_frames)
-        # the frames of all streams and the padding, in one copy
-        parts = [x.to(torch.float32) for x in live]
-        if P > F:
-            parts.append(torch.zeros(P - F, 1, HW, HW, dtype=torch.float32, device=live[0].device))
-        x = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
-        return self._push(x, ks)
+        return self._push(gather_padded(live, F, padded_frames(F, self.max_frames), (1, HW, HW)), ks)
 
     def push_u8(self, frames, color=None) -> list:
         """frames: a sequence of num_streams entries, entry s the next 0 <= k_s <= max_push frames of camera s as uint8
@@ -133,66 +112,59 @@ class AeStreamGroup:
         push returns for the same frames converted on the host.  With color ("rgb", "bgr", "rgbx" or "bgrx") every camera brings packed colour pixels,
         uint8 (k_s, Hs, Ws, 3) or (k_s, Hs, Ws, 4) -- one format for the whole call -- and the same launch takes their
         grey first (data.luma_u8, PIL's convert("L"))."""
-        from .data import U8Ingest, ingest_device
-        chunks, ks = check_group_push_u8(self.model, frames, self.num_streams, self.max_push, check_model, color)
+        from .data import ingest_device
+        check_model(self.model)
+        chunks, ks = walk_group_frames_u8(frames, self.num_streams, self.max_push, color)
         live = [x for x in chunks if x is not None]
         dev = ingest_device(self.model, live, "push_u8")
-        if self._ingest is None:
-            self._ingest = U8Ingest(dev)
-            self._u8 = torch.empty(self.max_frames, 1, HW, HW, dtype=torch.float32, device=dev)
+        ingest, buf = u8_buffer(self, dev, self.max_frames, (HW, HW))
         P = padded_frames(sum(ks), self.max_frames)
-        x = self._ingest.table(live, P, (HW, HW), 2, out=self._u8[:P], capacity=self.max_frames, color=color)
+        x = ingest.table(live, P, (HW, HW), 2, out=buf[:P], capacity=self.max_frames, color=color)
         return self._push(x, ks)
 
     def _push(self, x, ks) -> list:
         """push's body: x (P, 1, 64, 64), the sum(ks) frames in stream order, then zeros."""
-        T, stride, cap, S = self.window, self.stride, self.cap, self.num_streams
+        T, stride, cap = self.window, self.stride, self.cap
         eng = self.model.engine()
         L = nat.lib()
         dev = eng.device
         stream = eng.stream()
         if self._ring is None:
             self._allocate(L, dev)
-        ring = self._ring
+        ring, tables = self._ring, self._tables
         F, P = sum(ks), x.shape[0]
         dst, rows = group_schedule(self.frames_seen, self.windows_emitted, ks, T, stride, cap=cap)
         nw = len(rows)
         self._copied.synchronize()  # (see _allocate: the device has the tables of the push before)
-        self._h_dst[:P] = torch.tensor(dst + [-1] * (P - F), dtype=torch.int32)
+        tables.fill_dst(dst, P)
         pl = eng.plan(P, 1)
         nat.check(L.vad_ae_frames_forward_group(pl.h, x.data_ptr(), self.total_slots, ring.data_ptr(),
-                                                self._h_dst.data_ptr(), self._table.data_ptr(), stream))
+                                                tables.h_dst.data_ptr(), tables.dev.data_ptr(), stream))
         o = dict(seq=torch.empty(nw, LATENT, device=dev), err=torch.empty(nw, device=dev),
                  mem=torch.empty(nw, device=dev), score=torch.empty(nw, device=dev))
         recon = torch.empty(nw, 1, HW, HW, device=dev) if self.return_reconstructions else None
         try:
             if nw > 0:
-                self._h_win[:nw] = torch.tensor([r[:2] for r in rows], dtype=torch.int64)
+                tables.fill_windows([r[:2] for r in rows])
                 nat.check(L.vad_ae_windows_forward_group(
-                    pl.h, ring.data_ptr(), self.total_slots, cap, T, self._h_win.data_ptr(), nw,
-                    self._table.data_ptr(), o["seq"].data_ptr(), o["err"].data_ptr(), o["mem"].data_ptr(),
+                    pl.h, ring.data_ptr(), self.total_slots, cap, T, tables.h_win.data_ptr(), nw,
+                    tables.dev.data_ptr(), o["seq"].data_ptr(), o["err"].data_ptr(), o["mem"].data_ptr(),
                     o["score"].data_ptr(), nat.ptr(recon), stream))
         finally:
             self._copied.record(torch.cuda.current_stream(dev))
         # the pushed frames' latents, gathered through the destinations the device table already holds
-        lat = ring_field(ring, self.total_slots, "lat").index_select(0, self._table[:F])
-        outs, f0, r0 = [], 0, 0
-        for s in range(S):
-            _, widx0, n = stream_schedule(self.frames_seen[s], self.windows_emitted[s], ks[s], T, stride)
-            r1 = r0 + n
+        lat = ring_field(ring, self.total_slots, "lat").index_select(0, tables.dev[:F])
+        outs = []
+        for s, f0, f1, r0, r1, widx0, n in per_stream(self.frames_seen, self.windows_emitted, ks, T, stride):
             out = {
                 "anomaly_scores": o["score"][r0:r1],
                 "recon_errors": o["err"][r0:r1],
                 "memory_scores": o["mem"][r0:r1],
                 "sequence_features": o["seq"][r0:r1],
-                "frame_features": lat[f0:f0 + ks[s]],
+                "frame_features": lat[f0:f1],
                 "window_starts": (widx0 + torch.arange(n, dtype=torch.int64)) * stride,
             }
             if recon is not None:
                 out["reconstructed"] = recon[r0:r1]
             outs.append(out)
-            self.frames_seen[s] += ks[s]
-            self.windows_emitted[s] = widx0 + n
-            f0 += ks[s]
-            r0 = r1
         return outs

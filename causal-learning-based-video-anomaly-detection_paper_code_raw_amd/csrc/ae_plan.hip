@@ -45,6 +45,7 @@
 #include "../../include/vad.h"
 #include "backbone.h"
 #include "conv3d.h"
+#include "group_table.h"
 #include "optim.h"
 #include "plan_util.h"
 
@@ -1701,17 +1702,10 @@ int vad_ae_windows_forward_ring(vad_ae_plan* plan, const float* ring, int64_t ca
                            score, recon, (hipStream_t)stream);
 }
 
-// A group of streams.  The device table of one push: the plan's B destination slots (int32) from byte 0, the window
-// rows (2 int64 each: base, first) from the next multiple of 16 bytes.  Both calls validate their host table entry by
-// entry before anything is queued: the kernels trust what they read.
-static int64_t ae_group_window_table_offset(int64_t nf) { return (nf * 4 + 15) & ~15ll; }
-
+// A group of streams.  The device table of one push (group_table.h, which also validates it): the plan's B destination
+// slots, then the window rows of 2 int64 each (base, first).
 int64_t vad_ae_group_table_bytes(int64_t nf, int64_t nw) {
-  if (nf < 1 || nw < 0 || nf > (1ll << 31) || nw > (1ll << 31)) {
-    vad::set_error("vad_ae_group_table_bytes: nf must be >= 1 and nw >= 0");
-    return -1;
-  }
-  return ae_group_window_table_offset(nf) + nw * 16;
+  return group_table_bytes("vad_ae_group_table_bytes", nf, nw, 16);
 }
 
 int vad_ae_frames_forward_group(vad_ae_plan* plan, const float* frames_chunk, int64_t total_slots, float* ring,
@@ -1729,23 +1723,8 @@ int vad_ae_frames_forward_group(vad_ae_plan* plan, const float* frames_chunk, in
             "vad_ae_frames_forward_group: dev_table must be a 16-byte aligned device pointer");
   VAD_CHECK(total_slots >= 1 && total_slots <= AE_RING_MAX,
             "vad_ae_frames_forward_group: total_slots must be in 1..2^24");
-  std::vector<int32_t> seen;
-  for (int f = 0; f < c.NF; ++f) {
-    const int32_t d = host_dst[f];
-    if (d < -1 || d >= total_slots) {
-      vad::set_error("vad_ae_frames_forward_group: dst[" + std::to_string(f) + "] = " + std::to_string(d) +
-                     " is outside -1 .. total_slots - 1 = " + std::to_string(total_slots - 1));
-      return 1;
-    }
-    if (d >= 0) seen.push_back(d);
-  }
-  std::sort(seen.begin(), seen.end());
-  for (size_t i = 1; i < seen.size(); ++i)
-    if (seen[i] == seen[i - 1]) {
-      vad::set_error("vad_ae_frames_forward_group: two entries of dst name slot " + std::to_string(seen[i]));
-      return 1;
-    }
-  VAD_HIP(hipMemcpyAsync(dev_table, host_dst, (size_t)c.NF * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+  VAD_TRY(check_and_copy_dst_table("vad_ae_frames_forward_group", host_dst, c.NF, total_slots, dev_table,
+                                   (hipStream_t)stream));
   return c.frames_forward_group(frames_chunk, ring, total_slots, static_cast<const int*>(dev_table),
                                 (hipStream_t)stream);
 }
@@ -1771,22 +1750,10 @@ int vad_ae_windows_forward_group(vad_ae_plan* plan, const float* ring, int64_t t
   VAD_CHECK(T <= 4096, "vad_ae_windows_forward_group: T must be at most 4096");
   VAD_CHECK(nw >= 1 && nw <= c.B,
             "vad_ae_windows_forward_group: nw must be in 1..B of the plan (its per-clip buffers)");
-  for (int i = 0; i < nw; ++i) {
-    const int64_t base = host_windows[2 * i], s0 = host_windows[2 * i + 1];
-    const char* what = nullptr;
-    if (base < 0 || base % cap != 0) what = "base must be a non-negative multiple of cap";
-    else if (base + cap > total_slots) what = "base + cap exceeds total_slots";
-    else if (s0 < 0 || s0 >= cap) what = "first must be in 0..cap - 1";
-    if (what) {
-      vad::set_error("vad_ae_windows_forward_group: window " + std::to_string(i) + " (base " + std::to_string(base) +
-                     ", first " + std::to_string(s0) + "): " + what);
-      return 1;
-    }
-  }
-  int64_t* tab = reinterpret_cast<int64_t*>(static_cast<char*>(dev_table) + ae_group_window_table_offset(c.NF));
-  VAD_HIP(hipMemcpyAsync(tab, host_windows, (size_t)nw * 16, hipMemcpyHostToDevice, (hipStream_t)stream));
+  VAD_TRY(check_and_copy_window_rows("vad_ae_windows_forward_group", host_windows, 2, nw, cap, total_slots, dev_table,
+                                     c.NF, (hipStream_t)stream));
   return c.windows_forward(ring, nullptr, total_slots, AeWindows::Group, T, 1, 0, nw, seq, recon_err, mem_score, score,
-                           recon, (hipStream_t)stream, tab, cap);
+                           recon, (hipStream_t)stream, group_window_rows(dev_table, c.NF), cap);
 }
 
 int vad_ae_debug_buffer(vad_ae_plan* plan, const char* name, int idx, void** ptr, int64_t* nfloats) {

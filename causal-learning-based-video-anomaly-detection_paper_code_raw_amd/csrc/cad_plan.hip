@@ -8,6 +8,7 @@
 
 #include "../../include/vad.h"
 #include "backbone.h"
+#include "group_table.h"
 #include "head.h"
 #include "mlp.h"
 #include "plan_util.h"
@@ -1536,17 +1537,10 @@ int vad_cad_windows_forward_ring(vad_cad_plan* plan, const float* cache, int64_t
                            adj, nmax, (hipStream_t)stream);
 }
 
-// A group of streams.  The device table of one push: the plan's B*T destination slots (int32) from byte 0, the window
-// rows (3 int64 each) from the next multiple of 16 bytes.  Both calls validate their host table entry by entry before
-// anything is queued: the kernels trust what they read.
-static int64_t group_window_table_offset(int64_t nf) { return (nf * 4 + 15) & ~15ll; }
-
+// A group of streams.  The device table of one push (group_table.h, which also validates it): the plan's B*T
+// destination slots, then the window rows of 3 int64 each (base, first, key).
 int64_t vad_cad_group_table_bytes(int64_t nf, int64_t nw) {
-  if (nf < 1 || nw < 0 || nf > (1ll << 31) || nw > (1ll << 31)) {
-    vad::set_error("vad_cad_group_table_bytes: nf must be >= 1 and nw >= 0");
-    return -1;
-  }
-  return group_window_table_offset(nf) + nw * 24;
+  return group_table_bytes("vad_cad_group_table_bytes", nf, nw, 24);
 }
 
 int vad_cad_frames_forward_group(vad_cad_plan* plan, const float* x, int64_t total_slots, float* cache,
@@ -1560,23 +1554,8 @@ int vad_cad_frames_forward_group(vad_cad_plan* plan, const float* x, int64_t tot
   VAD_CHECK(total_slots >= 1, "vad_cad_frames_forward_group: total_slots must be >= 1");
   VAD_CHECK((int64_t)c.NF * c.H * c.W * 4 < (1ll << 31), "vad_cad_frames_forward_group: x is 2 GB or more");
   VAD_CHECK(FrameCache(total_slots).total * 4 < (1ll << 31), "vad_cad_frames_forward_group: cache is 2 GB or more");
-  std::vector<int32_t> seen;
-  for (int f = 0; f < c.NF; ++f) {
-    const int32_t d = host_dst[f];
-    if (d < -1 || d >= total_slots) {
-      vad::set_error("vad_cad_frames_forward_group: dst[" + std::to_string(f) + "] = " + std::to_string(d) +
-                     " is outside -1 .. total_slots - 1 = " + std::to_string(total_slots - 1));
-      return 1;
-    }
-    if (d >= 0) seen.push_back(d);
-  }
-  std::sort(seen.begin(), seen.end());
-  for (size_t i = 1; i < seen.size(); ++i)
-    if (seen[i] == seen[i - 1]) {
-      vad::set_error("vad_cad_frames_forward_group: two entries of dst name slot " + std::to_string(seen[i]));
-      return 1;
-    }
-  VAD_HIP(hipMemcpyAsync(dev_table, host_dst, (size_t)c.NF * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+  VAD_TRY(check_and_copy_dst_table("vad_cad_frames_forward_group", host_dst, c.NF, total_slots, dev_table,
+                                   (hipStream_t)stream));
   return c.frames_forward(x, total_slots, cache, 0, false, (hipStream_t)stream, static_cast<const int*>(dev_table));
 }
 
@@ -1597,25 +1576,13 @@ int vad_cad_windows_forward_group(vad_cad_plan* plan, const float* cache, int64_
   VAD_CHECK(nw >= 1 && nw <= c.B,
             "vad_cad_windows_forward_group: nw must be in 1..the plan's B (one per-clip scratch row per window)");
   VAD_CHECK(FrameCache(total_slots).total * 4 < (1ll << 31), "vad_cad_windows_forward_group: cache is 2 GB or more");
-  for (int i = 0; i < nw; ++i) {
-    const int64_t base = host_windows[3 * i], s0 = host_windows[3 * i + 1];
-    const char* what = nullptr;
-    if (base < 0 || base % cap != 0) what = "base must be a non-negative multiple of cap";
-    else if (base + cap > total_slots) what = "base + cap exceeds total_slots";
-    else if (s0 < 0 || s0 >= cap) what = "first must be in 0..cap - 1";
-    if (what) {
-      vad::set_error("vad_cad_windows_forward_group: window " + std::to_string(i) + " (base " + std::to_string(base) +
-                     ", first " + std::to_string(s0) + "): " + what);
-      return 1;
-    }
-  }
-  int64_t* tab = reinterpret_cast<int64_t*>(static_cast<char*>(dev_table) + group_window_table_offset(c.NF));
-  VAD_HIP(hipMemcpyAsync(tab, host_windows, (size_t)nw * 24, hipMemcpyHostToDevice, (hipStream_t)stream));
+  VAD_TRY(check_and_copy_window_rows("vad_cad_windows_forward_group", host_windows, 3, nw, cap, total_slots, dev_table,
+                                     c.NF, (hipStream_t)stream));
   c.seed = seed;
   c.step = step;
   c.clip0 = 0;
   return c.windows_forward(cache, total_slots, true, T, 1, 0, 0, nw, final_scores, probs, causal, kl, z, adj, nmax,
-                           (hipStream_t)stream, tab, cap);
+                           (hipStream_t)stream, group_window_rows(dev_table, c.NF), cap);
 }
 
 int vad_cad_backward(vad_cad_plan* plan, int use_loss, const float* d_final, const float* d_probs,

@@ -252,6 +252,43 @@ static int ingest_check_color(const char* fn, int64_t nf, int fmt, int planes, i
   return 0;
 }
 
+// The body of the four ingest entry points.  table: the nf rows (address, sh, sw, pitch) of host_table are validated
+// and copied to dev_table; otherwise the uniform form, nf frames of sh x sw at src, frame_stride bytes apart.  color:
+// packed colour pixels of fmt into `planes` planes; otherwise grey source bytes (fmt and planes are not read).
+static int ingest_launch(const char* fn, bool table, const int64_t* host_table, void* dev_table, const uint8_t* src,
+                         int sh, int sw, int64_t pitch, int64_t frame_stride, int64_t nf, bool color, int fmt,
+                         int planes, int dh, int dw, int mode, float* dst, hipStream_t stream) {
+  const std::string name(fn);
+  VAD_CHECK(table || src != nullptr, name + ": null src");
+  VAD_CHECK(!table || (host_table && dev_table), name + ": null table (host_table or dev_table)");
+  VAD_CHECK((reinterpret_cast<uintptr_t>(dev_table) & 15) == 0, name + ": dev_table must be 16-B aligned");
+  int rows = 0;
+  VAD_TRY(ingest_check_output(fn, nf, dh, dw, mode, dst, rows));
+  if (color) VAD_TRY(ingest_check_color(fn, nf, fmt, planes, dh, dw));
+  const int step = color ? ingest_step(fmt) : 1;
+  if (table) {
+    for (int64_t f = 0; f < nf; ++f) {
+      const int64_t* e = host_table + 4 * f;
+      if (e[0] == 0) continue;  // a frame of zeros: its sizes are not read
+      VAD_TRY(ingest_check_source(fn, "entry " + std::to_string(f) + ": ", e[1], e[2], e[3], step));
+    }
+    VAD_HIP(hipMemcpyAsync(dev_table, host_table, (size_t)nf * 32, hipMemcpyHostToDevice, stream));
+  } else {
+    VAD_TRY(ingest_check_source(fn, "", sh, sw, pitch, step));
+    VAD_CHECK(frame_stride >= 0, name + ": frame_stride must be >= 0");
+  }
+  // [uniform, table form][grey, colour to 1 plane, colour to 3 planes]
+  static constexpr decltype(&ingest_u8_kernel<false, 0>) kernels[2][3] = {
+      {ingest_u8_kernel<false, 0>, ingest_u8_kernel<false, 1>, ingest_u8_kernel<false, 3>},
+      {ingest_u8_kernel<true, 0>, ingest_u8_kernel<true, 1>, ingest_u8_kernel<true, 3>}};
+  const auto kernel = kernels[table][!color ? 0 : planes == 1 ? 1 : 2];
+  const int strips = (int)cdiv(dh, rows);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(nf * strips)), dim3(256), 0, stream, src, frame_stride, sh, sw, pitch,
+                     static_cast<const int64_t*>(dev_table), dh, dw, rows, strips, mode, dst, color ? fmt : 0);
+  VAD_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace vad
 
 using namespace vad;
@@ -272,36 +309,14 @@ int vad_u8_to_clip(const uint8_t* src, int64_t n, int mode, float* dst, void* st
 
 int vad_ingest_u8(const uint8_t* src, int64_t nf, int sh, int sw, int64_t pitch, int64_t frame_stride, int dh, int dw,
                   int mode, float* dst, void* stream) {
-  VAD_CHECK(src != nullptr, "vad_ingest_u8: null src");
-  int rows = 0;
-  VAD_TRY(ingest_check_output("vad_ingest_u8", nf, dh, dw, mode, dst, rows));
-  VAD_TRY(ingest_check_source("vad_ingest_u8", "", sh, sw, pitch));
-  VAD_CHECK(frame_stride >= 0, "vad_ingest_u8: frame_stride must be >= 0");
-  const int strips = (int)cdiv(dh, rows);
-  hipLaunchKernelGGL(ingest_u8_kernel<false>, dim3((unsigned)(nf * strips)), dim3(256), 0, (hipStream_t)stream, src,
-                     frame_stride, sh, sw, pitch, (const int64_t*)nullptr, dh, dw, rows, strips, mode, dst, 0);
-  VAD_LAUNCH_CHECK();
-  return 0;
+  return ingest_launch("vad_ingest_u8", false, nullptr, nullptr, src, sh, sw, pitch, frame_stride, nf, false, 0, 0, dh,
+                       dw, mode, dst, (hipStream_t)stream);
 }
 
 int vad_ingest_u8_color(const uint8_t* src, int64_t nf, int sh, int sw, int64_t pitch, int64_t frame_stride, int fmt,
                         int planes, int dh, int dw, int mode, float* dst, void* stream) {
-  VAD_CHECK(src != nullptr, "vad_ingest_u8_color: null src");
-  int rows = 0;
-  VAD_TRY(ingest_check_output("vad_ingest_u8_color", nf, dh, dw, mode, dst, rows));
-  VAD_TRY(ingest_check_color("vad_ingest_u8_color", nf, fmt, planes, dh, dw));
-  VAD_TRY(ingest_check_source("vad_ingest_u8_color", "", sh, sw, pitch, ingest_step(fmt)));
-  VAD_CHECK(frame_stride >= 0, "vad_ingest_u8_color: frame_stride must be >= 0");
-  const int strips = (int)cdiv(dh, rows);
-  const dim3 grid((unsigned)(nf * strips));
-  if (planes == 1)
-    hipLaunchKernelGGL((ingest_u8_kernel<false, 1>), grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, sh, sw,
-                       pitch, (const int64_t*)nullptr, dh, dw, rows, strips, mode, dst, fmt);
-  else
-    hipLaunchKernelGGL((ingest_u8_kernel<false, 3>), grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, sh, sw,
-                       pitch, (const int64_t*)nullptr, dh, dw, rows, strips, mode, dst, fmt);
-  VAD_LAUNCH_CHECK();
-  return 0;
+  return ingest_launch("vad_ingest_u8_color", false, nullptr, nullptr, src, sh, sw, pitch, frame_stride, nf, true, fmt,
+                       planes, dh, dw, mode, dst, (hipStream_t)stream);
 }
 
 int64_t vad_ingest_table_bytes(int64_t nf) {
@@ -314,49 +329,14 @@ int64_t vad_ingest_table_bytes(int64_t nf) {
 
 int vad_ingest_u8_table(const int64_t* host_table, int64_t nf, int dh, int dw, int mode, float* dst, void* dev_table,
                         void* stream) {
-  VAD_CHECK(host_table && dev_table, "vad_ingest_u8_table: null table (host_table or dev_table)");
-  VAD_CHECK((reinterpret_cast<uintptr_t>(dev_table) & 15) == 0, "vad_ingest_u8_table: dev_table must be 16-B aligned");
-  int rows = 0;
-  VAD_TRY(ingest_check_output("vad_ingest_u8_table", nf, dh, dw, mode, dst, rows));
-  for (int64_t f = 0; f < nf; ++f) {
-    const int64_t* e = host_table + 4 * f;
-    if (e[0] == 0) continue;  // a frame of zeros: its sizes are not read
-    VAD_TRY(ingest_check_source("vad_ingest_u8_table", "entry " + std::to_string(f) + ": ", e[1], e[2], e[3]));
-  }
-  VAD_HIP(hipMemcpyAsync(dev_table, host_table, (size_t)nf * 32, hipMemcpyHostToDevice, (hipStream_t)stream));
-  const int strips = (int)cdiv(dh, rows);
-  hipLaunchKernelGGL(ingest_u8_kernel<true>, dim3((unsigned)(nf * strips)), dim3(256), 0, (hipStream_t)stream,
-                     (const uint8_t*)nullptr, (int64_t)0, 0, 0, (int64_t)0, static_cast<const int64_t*>(dev_table), dh,
-                     dw, rows, strips, mode, dst, 0);
-  VAD_LAUNCH_CHECK();
-  return 0;
+  return ingest_launch("vad_ingest_u8_table", true, host_table, dev_table, nullptr, 0, 0, 0, 0, nf, false, 0, 0, dh, dw,
+                       mode, dst, (hipStream_t)stream);
 }
 
 int vad_ingest_u8_color_table(const int64_t* host_table, int64_t nf, int fmt, int planes, int dh, int dw, int mode,
                               float* dst, void* dev_table, void* stream) {
-  const char* fn = "vad_ingest_u8_color_table";
-  VAD_CHECK(host_table && dev_table, std::string(fn) + ": null table (host_table or dev_table)");
-  VAD_CHECK((reinterpret_cast<uintptr_t>(dev_table) & 15) == 0, std::string(fn) + ": dev_table must be 16-B aligned");
-  int rows = 0;
-  VAD_TRY(ingest_check_output(fn, nf, dh, dw, mode, dst, rows));
-  VAD_TRY(ingest_check_color(fn, nf, fmt, planes, dh, dw));
-  for (int64_t f = 0; f < nf; ++f) {
-    const int64_t* e = host_table + 4 * f;
-    if (e[0] == 0) continue;  // a frame of zeros: its sizes are not read
-    VAD_TRY(ingest_check_source(fn, "entry " + std::to_string(f) + ": ", e[1], e[2], e[3], ingest_step(fmt)));
-  }
-  VAD_HIP(hipMemcpyAsync(dev_table, host_table, (size_t)nf * 32, hipMemcpyHostToDevice, (hipStream_t)stream));
-  const int strips = (int)cdiv(dh, rows);
-  const dim3 grid((unsigned)(nf * strips));
-  const int64_t* tab = static_cast<const int64_t*>(dev_table);
-  if (planes == 1)
-    hipLaunchKernelGGL((ingest_u8_kernel<true, 1>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)nullptr,
-                       (int64_t)0, 0, 0, (int64_t)0, tab, dh, dw, rows, strips, mode, dst, fmt);
-  else
-    hipLaunchKernelGGL((ingest_u8_kernel<true, 3>), grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)nullptr,
-                       (int64_t)0, 0, 0, (int64_t)0, tab, dh, dw, rows, strips, mode, dst, fmt);
-  VAD_LAUNCH_CHECK();
-  return 0;
+  return ingest_launch("vad_ingest_u8_color_table", true, host_table, dev_table, nullptr, 0, 0, 0, 0, nf, true, fmt,
+                       planes, dh, dw, mode, dst, (hipStream_t)stream);
 }
 
 int vad_luma_u8(const uint8_t* src, int sh, int sw, int64_t pitch, int fmt, uint8_t* dst) {

@@ -14,28 +14,16 @@ what vad_cad_windows_forward_ring asks of a batch.
 
 Window w returns what ``model.eval(); model(clip_w, seed=seed, step=step, clip0=clip0 + w)`` returns, which is also
 score_video's definition: the same stream pushed in any chunking gives the results of score_video on the same frames.
+
+stream_schedule and the checks that no model enters are stream_util.py's, shared with the other three stream classes.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _native as nat
+from .stream_util import _positive_int, check_frame_size, check_push_u8, stream_schedule, u8_buffer  # noqa: F401
 from .video import MAX_DET, NUM_FACTORS, cache_field
-
-
-def stream_schedule(frames_seen: int, windows_emitted: int, k: int, window: int, stride: int):
-    """The windows a push of k frames completes, for a stream that has taken frames_seen frames and emitted
-    windows_emitted windows: (first_frame, widx0, nw) -- nw windows, window i of the batch being window widx0 + i of
-    the stream, frames first_frame + i * stride + t.  Window w is complete once frame w * stride + window - 1 is in."""
-    total = frames_seen + k
-    complete = (total - window) // stride + 1 if total >= window else 0
-    return windows_emitted * stride, windows_emitted, complete - windows_emitted
-
-
-def _positive_int(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or v < 1:
-        raise ValueError(f"open_stream: {name} must be an integer >= 1, got {v!r}")
-    return int(v)
 
 
 def check_model(model):
@@ -64,30 +52,6 @@ def check_push(model, frames, max_push, frame_size) -> torch.Tensor:
     if frame_size is not None and tuple(frames.shape[2:]) != tuple(frame_size):
         raise ValueError(f"push: frame size {tuple(frames.shape[2:])} differs from the stream's {tuple(frame_size)}")
     return frames
-
-
-def check_push_u8(model, frames, max_push, what="push_u8", color=None) -> torch.Tensor:
-    """The ValueErrors of a stream's push_u8, raised before any device work; returns the frames as (k, Hs, Ws), with a
-    colour format as (k, Hs, Ws, C)."""
-    from .data import check_u8_frames
-    x = check_u8_frames(frames, what, color)
-    k = x.shape[0]
-    if k < 1 or k > max_push:
-        raise ValueError(f"{what}: between 1 and max_push = {max_push} frames per push, got {k}")
-    return x
-
-
-def check_frame_size(frame_size, what="open_stream"):
-    if frame_size is None:
-        return None
-    try:
-        size = tuple(int(v) for v in frame_size)
-        ok = len(size) == 2 and size == tuple(frame_size) and min(size) >= 1
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{what}: frame_size must be None or (H, W), two integers >= 1, got {frame_size!r}")
-    return size
 
 
 class CadStream:
@@ -128,15 +92,13 @@ class CadStream:
         owns (data.U8Ingest); the rest is push: push_u8(u8) returns what push returns for the same frames converted
         on the host.  Without frame_size the first push fixes it to the source size.  With color ("rgb", "bgr", "rgbx" or "bgrx") the frames are packed colour pixels, uint8
         (k, Hs, Ws, 3) or (k, Hs, Ws, 4), and the same launch takes their grey first (data.luma_u8, PIL's convert("L"))."""
-        from .data import U8Ingest, ingest_device
+        from .data import ingest_device
         check_model(self.model)
         x = check_push_u8(self.model, frames, self.max_push, color=color)
         dev = ingest_device(self.model, [x], "push_u8")
         size = self.frame_size or tuple(x.shape[1:3])
-        if self._ingest is None:
-            self._ingest = U8Ingest(dev)
-            self._u8 = torch.empty(self.max_push, 1, *size, dtype=torch.float32, device=dev)
-        return self._push(self._ingest.ingest(x, size, 0, out=self._u8[:x.shape[0]], color=color))
+        ingest, buf = u8_buffer(self, dev, self.max_push, size)
+        return self._push(ingest.ingest(x, size, 0, out=buf[:x.shape[0]], color=color))
 
     def _push(self, x) -> dict:
         """push's body: x (k, 1, H, W), checked."""
