@@ -95,7 +95,7 @@ struct BnBwdFuse {
 };
 int conv3_dgrad(const Conv3Layer& L, const float* dY, const float* wd, float* dX, hipStream_t st,
                 const BnBwdFuse* f = nullptr, const __bf16* w3 = nullptr);
-// direct LDS-patch kernels (conv_patch.hip) for stride-1 layers; conv3_fwd / conv3_dgrad route there by default
+// direct f32 LDS-patch kernels (conv_patch.hip)
 bool conv3_patch_supported(const Conv3Layer& L, bool fwd);
 int64_t conv3_patch_blocks(int NF, int OH, int OW);  // BN partial blocks of a patch forward
 int conv3_patch_fwd(const Conv3Layer& L, const float* src, const float* src_stats, const float* wf, const float* bias,
@@ -156,12 +156,16 @@ int bfc_dgrad(const Conv3Layer& L, const __bf16* dY, const __bf16* wdb, __bf16* 
 bool bfc_wgrad_supported(const Conv3Layer& L);
 int bfc_wgrad(const Conv3Layer& L, const __bf16* dY, const __bf16* src, const float* src_stats, float* slab,
               int* nsplit, int64_t partial_cap, hipStream_t st);
-// which kernel family conv3_fwd (kind 0) / conv3_dgrad (1) / conv3_wgrad (2) dispatches to for this layer under the
-// current knobs: 6 = split-bf16 (six bf16 products per K step), 2 = native bf16 (conv_bf.hip), 1 = bf16 operands on the
-// split kernels, 0 = f32 MFMA kernels
+// The kernel family conv3_fwd / conv3_dgrad / conv3_wgrad launch for this layer under the current knobs and the
+// calling thread's modes: conv_bf.hip, conv_x3.hip (SplitS2: its stride-2 parity-class input gradient), conv_x3w.hip,
+// conv_patch.hip, the implicit GEMM.  None: nothing takes the pass, *why (nullable) gets the error text.
+enum class Conv3Pass { Fwd, Dgrad, Wgrad };  // (= the kind of conv3_path)
+enum class Conv3Kernel { BfNative, SplitX3, SplitS2, SplitTr, PatchF32, GemmF32, None };
+Conv3Kernel conv3_choose(const Conv3Layer& L, Conv3Pass pass, const char** why = nullptr);
+// the same as the instruction mix it runs: 6 = split-bf16 (six bf16 products per K step), 2 = native bf16, 1 = bf16
+// operands on the split kernels, 0 = f32 MFMA kernels
 int conv3_path(const Conv3Layer& L, int kind);
-// every pass of this layer (forward, input gradient when dgrad, weight gradient) runs on a split kernel under the
-// current knobs, i.e. can take bf16 activations
+// under bf16 activation storage every pass of this layer (input gradient: when dgrad) has a kernel
 bool conv3_act_bf16_ok(const Conv3Layer& L, bool dgrad);
 // alone: nothing else runs beside this weight gradient (the last layer's): the grid fills every CU
 int conv3_wgrad(const Conv3Layer& L, const float* dY, const float* src, const float* src_stats, float* partial,

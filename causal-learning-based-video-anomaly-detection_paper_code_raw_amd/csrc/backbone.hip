@@ -951,6 +951,46 @@ __global__ void conv3_prep_all_kernel(const PrepTab t) {
   }
 }
 
+// The one rule for which kernel family a pass of a layer runs on, in order of preference.  The
+// launchers switch on it; conv3_path, conv3_act_bf16_ok, conv3_dgrad_w3_wanted and the prep table's classes are read
+// off it.  The f32 families take no bf16 activations: under bf16 storage a pass nothing else takes has no kernel.
+Conv3Kernel conv3_choose(const Conv3Layer& L, Conv3Pass pass, const char** why) {
+  using K = Conv3Kernel;
+  const bool f32 = !g_act_bf16;
+  const char* no_f32 = nullptr;
+  auto none = [&](const char* reason) { if (why) *why = reason; return K::None; };
+  switch (pass) {
+    case Conv3Pass::Fwd:
+      if (bfc_supported(L, true)) return K::BfNative;
+      if (L.Ci % 32 != 0) return none("conv3_fwd: Ci must be a multiple of 32");
+      no_f32 = "conv3_fwd: bf16 activations need the split kernels";
+      // (the patch grid may exceed ceil(M/64) BN partial blocks on tiny images: those stay on the GEMM path)
+      if (!g_conv_patch || conv3_patch_blocks(L.NF, L.OH, L.OW) > cdiv((int64_t)L.NF * L.OH * L.OW, 64)) break;
+      if (conv3_x3_supported(L, true)) return K::SplitX3;
+      if (f32 && conv3_patch_supported(L, true)) return K::PatchF32;
+      break;
+    case Conv3Pass::Dgrad:
+      if (L.Co % 32 != 0) return none("conv3_dgrad: Co must be a multiple of 32");
+      if (bfc_supported(L, false)) return K::BfNative;
+      no_f32 = "conv3_dgrad: bf16 activations need the split kernels";
+      if (!g_conv_patch) break;
+      if (conv3_x3_supported(L, false)) return K::SplitX3;
+      if (!conv3_patch_supported(L, false)) break;  // (stride 2: the split kernel too)
+      if (conv3_x3_dgrad_s2_supported(L)) return K::SplitS2;
+      if (f32) return K::PatchF32;
+      break;
+    case Conv3Pass::Wgrad:
+      if (bfc_wgrad_supported(L)) return K::BfNative;
+      no_f32 = "conv3_wgrad: bf16 activations need the split kernels";
+      if (!g_conv_wgrad_patch) break;
+      if (x3_wgrad_tr_supported(L)) return K::SplitTr;
+      if (conv3_wgrad_x3_supported(L)) return K::SplitX3;
+      if (f32 && conv3_wgrad_patch_supported(L) && (L.stride == 1 || g_conv_wgrad_patch == 2)) return K::PatchF32;
+      break;
+  }
+  return f32 ? K::GemmF32 : none(no_f32);
+}
+
 int conv3_prep_table(int n, const float* const* w, const Conv3Layer* L, float* const* wf, float* const* wd,
                      __bf16* const* w3, PrepTab* out) {
   VAD_CHECK(n >= 1 && n <= 8, "conv3_prep_weights_all: 1..8 layers");
@@ -966,7 +1006,7 @@ int conv3_prep_table(int n, const float* const* w, const Conv3Layer* L, float* c
     VAD_CHECK(!t.w3[l] || L[l].Co % 16 == 0, "conv3_prep_weights_all: pre-split Wd needs Co % 16 == 0");
     t.Ci[l] = L[l].Ci;
     t.Co[l] = L[l].Co;
-    t.classes[l] = L[l].stride == 2 && !(g_conv_patch && conv3_patch_supported(L[l], false));
+    t.classes[l] = L[l].stride == 2 && conv3_choose(L[l], Conv3Pass::Dgrad) == Conv3Kernel::GemmF32;
     acc += (int64_t)L[l].Co * L[l].Ci * 9;
     t.end[l] = acc;
   }
@@ -996,20 +1036,18 @@ int conv3_prep_weights(const float* w, const Conv3Layer& L, float* wf, float* wd
 int conv3_fwd(const Conv3Layer& L, const float* src, const float* src_stats, const float* wf, const float* bias,
               float* y, float* partials, int* nparts, hipStream_t st, int* parts_cm) {
   if (parts_cm) *parts_cm = 0;
-  if (bfc_supported(L, true)) {  // native bf16 kernels (config 4): column-major partials
-    if (parts_cm) *parts_cm = 1;
-    return bfc_fwd(L, reinterpret_cast<const __bf16*>(src), src_stats, conv3_bf16_image(wf, L), bias,
-                   reinterpret_cast<__bf16*>(y), partials, conv3_patch_blocks(L.NF, L.OH, L.OW) * 2 * L.Co, nparts, st);
+  const char* why = nullptr;
+  switch (conv3_choose(L, Conv3Pass::Fwd, &why)) {
+    case Conv3Kernel::BfNative:  // (config 4): column-major partials
+      if (parts_cm) *parts_cm = 1;
+      return bfc_fwd(L, reinterpret_cast<const __bf16*>(src), src_stats, conv3_bf16_image(wf, L), bias,
+                     reinterpret_cast<__bf16*>(y), partials, conv3_patch_blocks(L.NF, L.OH, L.OW) * 2 * L.Co, nparts,
+                     st);
+    case Conv3Kernel::SplitX3: return conv3_x3_fwd(L, src, src_stats, wf, bias, y, partials, nparts, st, parts_cm);
+    case Conv3Kernel::PatchF32: return conv3_patch_fwd(L, src, src_stats, wf, bias, y, partials, nparts, st);
+    case Conv3Kernel::GemmF32: break;
+    default: VAD_CHECK(false, why ? why : "conv3: no kernel for this pass");
   }
-  VAD_CHECK(L.Ci % 32 == 0, "conv3_fwd: Ci must be a multiple of 32");
-  // (the patch grid may exceed ceil(M/64) BN partial blocks on tiny images: those stay on the GEMM path)
-  if (g_conv_patch && conv3_patch_blocks(L.NF, L.OH, L.OW) <= cdiv((int64_t)L.NF * L.OH * L.OW, 64)) {
-    if (conv3_x3_supported(L, true))
-      return conv3_x3_fwd(L, src, src_stats, wf, bias, y, partials, nparts, st, parts_cm);
-    VAD_CHECK(!g_act_bf16, "conv3_fwd: bf16 activations need the split kernels");
-    if (conv3_patch_supported(L, true)) return conv3_patch_fwd(L, src, src_stats, wf, bias, y, partials, nparts, st);
-  }
-  VAD_CHECK(!g_act_bf16, "conv3_fwd: bf16 activations need the split kernels");
   ConvGeom g{L.NF, L.OH, L.OW, L.stride, L.stride, L.IH, L.IW, L.Ci};
   TapTable taps;
   fwd_taps(taps);
@@ -1030,19 +1068,19 @@ int conv3_fwd(const Conv3Layer& L, const float* src, const float* src_stats, con
 
 int conv3_dgrad(const Conv3Layer& L, const float* dY, const float* wd, float* dX, hipStream_t st,
                 const BnBwdFuse* f, const __bf16* w3) {
-  VAD_CHECK(L.Co % 32 == 0, "conv3_dgrad: Co must be a multiple of 32");
   const int N = L.Ci;
   if (f) *f->nparts = 0;
-  if (bfc_supported(L, false))
-    return bfc_dgrad(L, reinterpret_cast<const __bf16*>(dY), conv3_bf16_image(wd, L), reinterpret_cast<__bf16*>(dX), st,
-                     f);
-  if (g_conv_patch && conv3_x3_supported(L, false))
-    return conv3_x3_dgrad(L, dY, wd, dX, st, f);
-  // (the split kernel reads the plain Wd layout, which the prep writes exactly when the f32 patch kernel is usable)
-  if (g_conv_patch && conv3_patch_supported(L, false) && conv3_x3_dgrad_s2_supported(L))
-    return conv3_x3_dgrad_s2(L, dY, wd, dX, st, f, w3);
-  VAD_CHECK(!g_act_bf16, "conv3_dgrad: bf16 activations need the split kernels");
-  if (g_conv_patch && conv3_patch_supported(L, false)) return conv3_patch_dgrad(L, dY, wd, dX, st);
+  const char* why = nullptr;
+  switch (conv3_choose(L, Conv3Pass::Dgrad, &why)) {
+    case Conv3Kernel::BfNative:
+      return bfc_dgrad(L, reinterpret_cast<const __bf16*>(dY), conv3_bf16_image(wd, L), reinterpret_cast<__bf16*>(dX),
+                       st, f);
+    case Conv3Kernel::SplitX3: return conv3_x3_dgrad(L, dY, wd, dX, st, f);
+    case Conv3Kernel::SplitS2: return conv3_x3_dgrad_s2(L, dY, wd, dX, st, f, w3);
+    case Conv3Kernel::PatchF32: return conv3_patch_dgrad(L, dY, wd, dX, st);
+    case Conv3Kernel::GemmF32: break;  // (stride 2: the per-class Wd image, conv3_prep_table)
+    default: VAD_CHECK(false, why ? why : "conv3: no kernel for this pass");
+  }
   if (L.stride == 1) {
     ConvGeom g{L.NF, L.IH, L.IW, 1, 1, L.OH, L.OW, L.Co};
     TapTable taps;
@@ -1076,33 +1114,21 @@ int conv3_dgrad(const Conv3Layer& L, const float* dY, const float* wd, float* dX
 }
 
 bool conv3_act_bf16_ok(const Conv3Layer& L, bool dgrad) {
-  {
-    ActStorage abf(1);  // (the native bf16 kernels exist for bf16 storage only)
-    if (bfc_supported(L, true) && (!dgrad || bfc_supported(L, false) || conv3_x3_dgrad_s2_supported(L)) &&
-        (bfc_wgrad_supported(L) || (g_conv_wgrad_patch && conv3_wgrad_x3_supported(L))))
-      return true;
-  }
-  const bool fwd = g_conv_patch && conv3_patch_blocks(L.NF, L.OH, L.OW) <= cdiv((int64_t)L.NF * L.OH * L.OW, 64) &&
-                   conv3_x3_supported(L, true);
-  const bool dg = !dgrad || (g_conv_patch && (conv3_x3_supported(L, false) ||
-                                              (conv3_patch_supported(L, false) && conv3_x3_dgrad_s2_supported(L))));
-  const bool wg = g_conv_wgrad_patch && conv3_wgrad_x3_supported(L);
-  return fwd && dg && wg;
+  ActStorage abf(1);  // (under bf16 storage the chooser offers only the families that take it)
+  return conv3_choose(L, Conv3Pass::Fwd) != Conv3Kernel::None &&
+         (!dgrad || conv3_choose(L, Conv3Pass::Dgrad) != Conv3Kernel::None) &&
+         conv3_choose(L, Conv3Pass::Wgrad) != Conv3Kernel::None;
+}
+
+bool conv3_dgrad_w3_wanted(const Conv3Layer& L) {
+  return g_dgrad_s2_w3 && !g_conv_bf16 && conv3_choose(L, Conv3Pass::Dgrad) == Conv3Kernel::SplitS2;
 }
 
 int conv3_path(const Conv3Layer& L, int kind) {
-  if (kind < 2 ? bfc_supported(L, kind == 0) : bfc_wgrad_supported(L)) return 2;
-  bool x3 = false;
-  if (kind == 1 && L.stride == 2)  // stride-2 input gradients: the parity-class split kernel when supported
-    x3 = g_conv_patch && conv3_patch_supported(L, false) && conv3_x3_dgrad_s2_supported(L);
-  else if (kind == 0)
-    x3 = g_conv_patch && conv3_patch_blocks(L.NF, L.OH, L.OW) <= cdiv((int64_t)L.NF * L.OH * L.OW, 64) &&
-         conv3_x3_supported(L, true);
-  else if (kind == 1)
-    x3 = g_conv_patch && conv3_x3_supported(L, false);
-  else
-    x3 = g_conv_wgrad_patch && (x3_wgrad_tr_supported(L) || conv3_wgrad_x3_supported(L));
-  return x3 ? (g_conv_bf16 ? 1 : 6) : 0;
+  const Conv3Kernel k = conv3_choose(L, Conv3Pass(kind));
+  if (k == Conv3Kernel::BfNative) return 2;
+  const bool split = k == Conv3Kernel::SplitX3 || k == Conv3Kernel::SplitS2 || k == Conv3Kernel::SplitTr;
+  return split ? (g_conv_bf16 ? 1 : 6) : 0;  // 0: the f32 families (and None: nothing runs)
 }
 
 // target grid of a weight gradient nothing else runs beside (the last layer's; 512 / 1024 measured no faster)
@@ -1110,17 +1136,21 @@ constexpr int WGRAD_ALONE_BLOCKS = 448;
 
 int conv3_wgrad(const Conv3Layer& L, const float* dY, const float* src, const float* src_stats, float* partial,
                 int* nsplit, int64_t partial_cap, hipStream_t st, bool alone) {
-  if (bfc_wgrad_supported(L))
-    return bfc_wgrad(L, reinterpret_cast<const __bf16*>(dY), reinterpret_cast<const __bf16*>(src), src_stats, partial,
-                     nsplit, partial_cap, st);
-  if (g_conv_wgrad_patch && x3_wgrad_tr_supported(L))
-    return x3_wgrad_tr(L, dY, src, src_stats, partial, nsplit, partial_cap, alone ? WGRAD_ALONE_BLOCKS : 0, st);
-  if (g_conv_wgrad_patch && conv3_wgrad_x3_supported(L))
-    return conv3_wgrad_x3(L, dY, src, src_stats, partial, nsplit, partial_cap,
-                          alone ? WGRAD_ALONE_BLOCKS : g_conv_wgrad_patch_blocks, st);
-  VAD_CHECK(!g_act_bf16, "conv3_wgrad: bf16 activations need the split kernels");
-  if (g_conv_wgrad_patch && conv3_wgrad_patch_supported(L) && (L.stride == 1 || g_conv_wgrad_patch == 2))
-    return conv3_wgrad_patch(L, dY, src, src_stats, partial, nsplit, partial_cap, g_conv_wgrad_patch_blocks, st);
+  const char* why = nullptr;
+  switch (conv3_choose(L, Conv3Pass::Wgrad, &why)) {
+    case Conv3Kernel::BfNative:
+      return bfc_wgrad(L, reinterpret_cast<const __bf16*>(dY), reinterpret_cast<const __bf16*>(src), src_stats,
+                       partial, nsplit, partial_cap, st);
+    case Conv3Kernel::SplitTr:
+      return x3_wgrad_tr(L, dY, src, src_stats, partial, nsplit, partial_cap, alone ? WGRAD_ALONE_BLOCKS : 0, st);
+    case Conv3Kernel::SplitX3:
+      return conv3_wgrad_x3(L, dY, src, src_stats, partial, nsplit, partial_cap,
+                            alone ? WGRAD_ALONE_BLOCKS : g_conv_wgrad_patch_blocks, st);
+    case Conv3Kernel::PatchF32:
+      return conv3_wgrad_patch(L, dY, src, src_stats, partial, nsplit, partial_cap, g_conv_wgrad_patch_blocks, st);
+    case Conv3Kernel::GemmF32: break;
+    default: VAD_CHECK(false, why ? why : "conv3: no kernel for this pass");
+  }
   const int M = L.Co, N = 9 * L.Ci, K = L.NF * L.OH * L.OW;
   return with_tile(pick_wgrad_tile(M, N), [&](auto cfg) -> int {
     using C = decltype(cfg);

@@ -1218,10 +1218,6 @@ bool conv3_x3_dgrad_s2_supported(const Conv3Layer& L) {
          L.OH == (L.IH - 1) / 2 + 1 && L.OW == (L.IW - 1) / 2 + 1;
 }
 
-bool conv3_dgrad_w3_wanted(const Conv3Layer& L) {
-  return g_dgrad_s2_w3 && !g_conv_bf16 && conv3_x3_dgrad_s2_supported(L);
-}
-
 int conv3_x3_dgrad_s2(const Conv3Layer& L, const float* dY, const float* wd, float* dX, hipStream_t st,
                       const BnBwdFuse* f, const __bf16* w3) {
   VAD_CHECK(conv3_x3_dgrad_s2_supported(L), "conv3_x3_dgrad_s2: unsupported layer");

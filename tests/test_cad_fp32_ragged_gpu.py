@@ -4,8 +4,8 @@ fp32 twin of test_cad_bf16_ragged_gpu.py, on the same machinery (tests/golden_ut
 
 Instantiations (the fp32 launchers restated by tile_plan below and checked by
 test_cases_reach_every_ragged_instantiation).  fwd: "pipe" conv3x3_x3p_kernel<NI,TH,TW> (WCH = 2: 32 input channels,
-the weights resident in LDS), "x3" conv3x3_x3_kernel<S,NI,TH,TW,NT>, or path 0 -- conv3_fwd leaves the patch kernels
-for the implicit GEMM where conv3_patch_blocks exceeds NF OH OW / 64; dgrad: stride 1 "x3" conv3x3_x3_kernel with
+the weights resident in LDS), "x3" conv3x3_x3_kernel<S,NI,TH,TW,NT>, or path 0 -- conv3_choose (backbone.hip) leaves
+the patch kernels for the implicit GEMM where conv3_patch_blocks exceeds NF OH OW / 64; dgrad: stride 1 "x3" conv3x3_x3_kernel with
 FWD = false, "fused" where the BnBwdFuse arm (the BatchNorm-backward sums of the layer below) is taken, stride 2 "s2"
 conv3x3_dgrad_s2x3_kernel, one frame and 16x16 written pixels per block; wgrad: "tr" x3_wgrad_tr_kernel<S,1,TH,TW,NCO>.
 "r:" names the dimensions the map leaves partly empty (h, w; f: the last NI-frame group).  Layer 0 has no input
@@ -141,7 +141,7 @@ def _x3_tile(h, w):
 
 
 def tile_plan(NF, H, W):
-    """The fp32 launchers restated (conv3_fwd / conv3_dgrad / conv3_wgrad of backbone.hip, dispatch_x3 / dispatch_pipe
+    """The fp32 launchers restated (the family: conv3_choose of backbone.hip; within it dispatch_x3 / dispatch_pipe
     / conv3_x3_dgrad / conv3_x3_dgrad_s2 of conv_x3.hip, x3_wgrad_tr of conv_x3w.hip, default knobs).  Per layer:
       "fwd":   (kernel, S, NI, TH, TW, NT, WCH), kernel "pipe" (conv3x3_x3p_kernel) or "x3" (conv3x3_x3_kernel);
       "dgrad": None under the frozen stem's layer 0, else (kernel, S, NI, TH, TW, NT, WCH, fused) in pixels of the map
