@@ -6,4 +6,5 @@ HIP kernels for gfx950 (libvadhip.so, C ABI in include/vad.h).  Import through t
 from .cad import (CausalAnomalyDetector, CausalFactorExtractor, CausalStructureLearner, DynamicsPredictor,  # noqa
                   EnhancedAnomalyScorer, ResNetBackbone, SimplePedestrianDetector, TrajectoryEncoder,
                   TrajectoryTracker)
+from .clip_stream import ClipStream  # noqa: F401
 from .train import CadTrainer, apply_memory_efficient_training, test_model, train_model  # noqa: F401

@@ -124,6 +124,7 @@ _SIGS = {
     "vad_mc_workspace_bytes": (_I64, [_P]),
     "vad_mc_bind": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vad_mc_forward": (_I, [_P, _P, _I, _U64, _U64, _I64, _P, _P, _P, _P, _P]),
+    "vad_mc_windows_forward": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _P, _P]),
     "vad_mc_backward": (_I, [_P, _P, _P]),
     "vad_mc_optimizer_step": (_I, [_P, _F, _F, _F, _F, _F, _F, _F, _P]),
     # the minicausal classifier and BCE alone (kernel unit tests; saved / dz are host ctypes arrays of device pointers)
@@ -140,6 +141,7 @@ _SIGS = {
     "vad_a2_workspace_bytes": (_I64, [_P]),
     "vad_a2_bind": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "vad_a2_forward": (_I, [_P, _P, _I, _U64, _U64, _I64, _I, _P, _P, _P, _P, _P]),
+    "vad_a2_windows_forward": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _P, _P, _P, _P]),
     "vad_a2_loss": (_I, [_P, _U64, _U64, _I64, _P, _P]),
     "vad_a2_loss_grads": (_I, [_P, _P, _P, _P]),
     "vad_a2_backward": (_I, [_P, _P, _P, _P, _P]),
@@ -159,6 +161,7 @@ _SIGS = {
     "vad_bbox_bind": (_I, [_P, _P, _P]),
     "vad_bbox_forward": (_I, [_P, _P, _P, _P, _P, _P]),
     "vad_bbox_windows_forward": (_I, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "vad_bbox_ring_forward": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "vad_bbox_head_forward": (_I, [_P, _P, _P, _P, _P]),
     "vad_bbox_debug_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(_I64)]),
     # cad1 memory autoencoder (causal_anomaly_detection1.py)

@@ -83,6 +83,32 @@ class CausalAnomalyDetector(nn.Module):
         params = [p for _, p in self.named_parameters()]
         return _A2Function.apply(x, e, self.training, seed, step, clip0, *params)
 
+    def scoring_engine(self, device) -> "A2Engine":
+        """The engine on `device`, made if need be, without choosing a clip plan (score_video, open_stream)."""
+        e = self._engine
+        if e is None or e.device != device:
+            e = self._engine = A2Engine(self, device)
+        return e
+
+    def score_video(self, frames, window=8, stride=4, batch=64) -> dict:
+        """Score every full window ``range(0, N - window + 1, stride)`` of a video: frames fp32 (N, 3, H, W) on the
+        device, planar RGB (``data.ingest_u8(u8, (64, 64), 1, color=..., planes=3)`` builds them from camera bytes).
+        Windows run ``batch`` at a time and are never copied into clips: conv3d_1 reads window b's frames in place
+        (``vad_a2_windows_forward``).  Returns anomaly_scores (W,), causal_graphs (W, 16, 16), features
+        (W, 16) -- for the windows of one batch what ``model(clips)`` returns in eval mode for those windows gathered
+        into (3, T, H, W) clips, a single window as ``model(torch.stack([clip, clip]))`` row 0 -- and window_starts (W,)
+        int64 on the host.  Eval mode only; runs on plans of its own, so a pending backward is not disturbed."""
+        from .clip_stream import check_score_video, score_video
+        x = check_score_video("a2", self, frames, window, stride, batch)
+        nat.require_hip(x)
+        return score_video(self.scoring_engine(x.device), x.float().contiguous(), int(window), int(stride), int(batch))
+
+    def open_stream(self, window=8, stride=1, *, max_push=1, frame_size=None):
+        """A clip_stream.ClipStream on this model: push frames (k, 3, H, W) as they arrive, get score_video's keys for
+        the windows they complete, read from a ring of window + max_push - 1 raw frames."""
+        from .clip_stream import ClipStream
+        return ClipStream(self, "a2", window, stride, max_push=max_push, frame_size=frame_size)
+
 
 class _A2Function(torch.autograd.Function):
     @staticmethod
@@ -116,8 +142,8 @@ class _A2LossFunction(torch.autograd.Function):
 
 
 class _A2Plan(FlatPlan):
-    def __init__(self, e, B, C, T, H, W):
-        super().__init__(e, B, C, T, H, W)
+    def __init__(self, e, B, C, T, H, W, *tag):  # tag ("windows",): a scoring plan, apart from the clip plan of its shape
+        super().__init__(e, B, C, T, H, W, *tag)
         self.B = B
         f = dict(dtype=torch.float32, device=e.device)
         self.scores, self.adj, self.feats = torch.zeros(B, **f), torch.zeros(B, 16, 16, **f), torch.zeros(B, 16, **f)
@@ -125,7 +151,7 @@ class _A2Plan(FlatPlan):
         self.borrow = False
 
     @staticmethod
-    def create_args(B, C, T, H, W):
+    def create_args(B, C, T, H, W, *tag):
         return B, T, H, W
 
 
@@ -155,6 +181,21 @@ class A2Engine(FlatEngine):
                                            nat.ptr(p.scores), nat.ptr(p.adj), nat.ptr(p.feats),
                                            nat.ptr(self.losses) if with_loss else None, self.stream()))
         return p.scores, p.adj, p.feats
+
+    WINDOW_KEYS = ("anomaly_scores", "causal_graphs", "features")
+
+    def window_outputs(self, n):
+        f = dict(dtype=torch.float32, device=self.device)
+        return torch.empty(n, **f), torch.empty(n, 16, 16, **f), torch.empty(n, 16, **f)
+
+    def windows_forward(self, frames, first, stride, ring, nw, T, B, out):
+        """nw <= B windows of frames (n, 3, H, W) -- a video (ring 0) or a ring of `ring` slots -- into the tensors
+        out (window_outputs' order).  The plan holds max(B, 2) clips (vad_a2_create) and is a scoring plan: no clip
+        forward runs on it, so no backward can be pending on the activations it overwrites."""
+        n, _, H, W = frames.shape
+        p = self.plan(max(B, 2), 3, T, H, W, "windows")
+        nat.check(nat.lib().vad_a2_windows_forward(p.h, nat.ptr(frames), n, first, stride, ring, nw, *map(nat.ptr, out),
+                                                   self.stream()))
 
     def set_host_losses(self, buf):
         """Let the current plan's forward also write its 10 loss words into `buf` (a pinned CPU tensor; None: stop)."""

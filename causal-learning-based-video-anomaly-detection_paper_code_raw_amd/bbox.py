@@ -68,6 +68,19 @@ class CausalAnomalyDetector(nn.Module):
             e = self._engine = BboxEngine(self, x.device)
         return e.score_video(x.float().contiguous(), window, stride, batch)
 
+    def scoring_engine(self, device) -> "BboxEngine":
+        e = self._engine
+        if e is None or e.device != device:
+            e = self._engine = BboxEngine(self, device)
+        return e
+
+    def open_stream(self, window=None, stride=1, *, max_push=1, frame_size=None):
+        """A clip_stream.ClipStream on this model: push frames (k, 3, H, W) as they arrive, get score_video's keys for
+        the windows they complete, read from a ring of window + max_push - 1 raw frames (``vad_bbox_ring_forward``)."""
+        from .clip_stream import ClipStream
+        window = self.num_frames if window is None else window
+        return ClipStream(self, "bbox", window, stride, max_push=max_push, frame_size=frame_size)
+
 
 def check_score_video(model, frames, window, stride, batch) -> torch.Tensor:
     """The ValueErrors of score_video, raised before any device work; returns the frames."""
@@ -118,6 +131,20 @@ class BboxEngine(FlatEngine):
         nat.check(nat.lib().vad_bbox_forward(p.h, nat.ptr(x), nat.ptr(s), nat.ptr(adj), nat.ptr(feats),
                                              nat.stream_of(self.device)))
         return s.view(B, 1), adj, feats
+
+    WINDOW_KEYS = ("anomaly_scores", "causal_graphs", "features")
+
+    def window_outputs(self, n):
+        f = dict(dtype=torch.float32, device=self.device)
+        return torch.empty(n, **f), torch.empty(n, 16, 16, **f), torch.empty(n, 1024, **f)
+
+    def windows_forward(self, frames, first, stride, ring, nw, T, B, out):
+        """nw windows of frames (n, 3, H, W) -- a video (ring 0) or a ring of `ring` slots -- into the tensors out
+        (window_outputs' order), on the plan of exactly nw clips (B, the most a caller will ask for, is not used)."""
+        n, _, H, W = frames.shape
+        p = self.plan(nw, 3, T, H, W)
+        nat.check(nat.lib().vad_bbox_ring_forward(p.h, nat.ptr(frames), n, first, stride, ring, *map(nat.ptr, out),
+                                                  nat.stream_of(self.device)))
 
     def score_video(self, x, window, stride, batch) -> dict:
         """x (N, 3, H, W) fp32 contiguous on the engine's device, checked."""

@@ -549,6 +549,26 @@ __device__ __forceinline__ void a2_stage_halo(float* xs, const float* __restrict
   }
 }
 
+// a2_stage_halo for a window source (the WIN form of a2_conv1_fwd_kernel): clip b is window b of ws, whose frames are
+// planar (3, H, W); the frame of each of the halo's A2H_D depth planes is resolved once (block-uniform), outside the
+// element loop.  Same xs layout and values as a2_stage_halo on the gathered clip.
+__device__ __forceinline__ void a2_stage_halo_win(float* xs, const WinSrc& ws, const A2Tiles& g, int64_t b, int d0,
+                                                  int h0, int w0) {
+#pragma unroll
+  for (int hd = 0; hd < A2H_D; ++hd) {
+    const int id = d0 - 1 + hd;
+    const bool in_t = id >= 0 && id < g.T;
+    const float* fr = in_t ? ws.frame(b, id) : nullptr;
+    for (int i = threadIdx.x; i < 3 * A2H_H * A2H_W; i += 256) {
+      const int hw = i % A2H_W, r = i / A2H_W, hh = r % A2H_H, ci = r / A2H_H;
+      const int ih = 2 * h0 - 1 + hh, iw = 2 * w0 - 1 + hw;
+      float v = 0.f;
+      if (in_t && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W) v = fr[((int64_t)ci * g.H + ih) * g.W + iw];
+      xs[((ci * A2H_D + hd) * A2H_H + hh) * A2H_W + hw] = v;
+    }
+  }
+}
+
 // The per-step weight images of the direct path in one launch: conv3d_2 / conv3d_3's GEMM and parity-class images
 // (conv3s2_prep_elem) and conv3d_1's [ci*27 + tap][co] rows + its bias (w1t: a2_conv1_fwd_kernel copies them into LDS
 // without transposing).
@@ -576,8 +596,11 @@ __global__ __launch_bounds__(256) void a2_prep_kernel(const A2Prep p) {
   }
 }
 
+// WIN: the B clips are the windows of win (x is not read; vad_a2_windows_forward); only the staging differs
+template <bool WIN>
 __global__ __launch_bounds__(256) void a2_conv1_fwd_kernel(const float* __restrict__ x, int B, int T, int H, int W,
-                                                           const float* __restrict__ w1t, float* __restrict__ y) {
+                                                           const float* __restrict__ w1t, float* __restrict__ y,
+                                                           const WinSrc win) {
   __shared__ __attribute__((aligned(16))) float ws[A2C1_TAPS + 1][16];  // [ci*27 + tap][co], then the bias row
   __shared__ float xs[3 * A2_HALO];
   __shared__ float os[256 * 17];
@@ -593,7 +616,10 @@ __global__ __launch_bounds__(256) void a2_conv1_fwd_kernel(const float* __restri
     const int64_t b = r / g.td;
     const int d0 = bd * A2T_D, h0 = bh * A2T_H, w0 = bw * A2T_W;
     __syncthreads();
-    a2_stage_halo(xs, x, g, b, d0, h0, w0);
+    if constexpr (WIN)
+      a2_stage_halo_win(xs, win, g, b, d0, h0, w0);
+    else
+      a2_stage_halo(xs, x, g, b, d0, h0, w0);
     __syncthreads();
     f32x4 acc[4];  // (voxels past the volume compute on zero halo and are not stored)
 #pragma unroll
@@ -761,6 +787,7 @@ struct A2PlanImpl {
   int training = 1, with_loss = 0;
   uint64_t seed = 0, step = 0;
   int64_t clip0 = 0;
+  bool win_dirty = false;  // the activations are a windows call's: no backward until the next clip forward
 
   A2PlanImpl(int B_, int T_, int H_, int W_) : B(B_), T(T_), H(H_), W(W_) {
     Vol5 in{B, 3, T, H, W};
@@ -850,7 +877,69 @@ struct A2PlanImpl {
     return a;
   }
 
+  // (a2_direct) the weight images of the three convs from the current parameters (a2_prep_kernel)
+  int prep_images(hipStream_t st) {
+    A2Prep pp{};
+    int64_t acc = 16 * (A2C1_TAPS + 1);
+    pp.end[0] = acc;
+    pp.w[0] = P(S_C1W);
+    pp.b1 = P(S_C1B);
+    pp.w1t = w1t;
+    for (int s = 1; s < 3; ++s) {
+      pp.w[s] = P(2 * s);
+      pp.wk[s] = wk3[s];
+      pp.wc[s] = wc3[s];
+      pp.Co[s] = A2_CO[s];
+      pp.Ci[s] = g[s].in.C;
+      acc += (int64_t)27 * g[s].in.C * A2_CO[s];
+      pp.end[s] = acc;
+    }
+    hipLaunchKernelGGL(a2_prep_kernel, dim3((unsigned)std::min<int64_t>(cdiv(acc, 256), 1024)), dim3(256), 0, st, pp);
+    VAD_LAUNCH_CHECK();
+    return 0;
+  }
+
+  // The first nw clips of the plan as windows of a video or ring (vad_a2_windows_forward): the forward below with
+  // eval semantics on nw clips, conv3d_1 reading the frames in place -- no copy into xin, borrow_input ignored, no
+  // dropout, no loss.  The plan's per-call state (training, seed, step, clip0, with_loss, xsrc) is left alone; its
+  // activations are overwritten, so a backward is refused until the next clip forward (win_dirty).
+  int forward_windows(const WinSrc& src, int nw, hipStream_t st) {
+    VAD_CHECK(direct, "vad_a2_windows_forward: windows are read by the direct first conv only (knob a2_direct = 1 when "
+                      "the plan was created); the im2col path has no windows form");
+    win_dirty = true;
+    VAD_TRY(prep_images(st));
+    const A2Tiles tl(nw, T, H, W);
+    hipLaunchKernelGGL(a2_conv1_fwd_kernel<true>, dim3((unsigned)std::min<int64_t>(tl.n, 4096)), dim3(256), 0, st,
+                       (const float*)nullptr, nw, T, H, W, w1t, y[0], src);
+    VAD_LAUNCH_CHECK();
+    for (int s3 = 1; s3 < 3; ++s3) {
+      const Vol5& in = g[s3].in;
+      VAD_TRY(conv3s2_fwd(y[s3 - 1], nw, in.D, in.H, in.W, in.C, wk3[s3], P(2 * s3 + 1), A2_CO[s3], 1, y[s3], st, scratch,
+                          scratch_floats));
+    }
+    Vol5 out = g[2].out();
+    out.N = nw;
+    VAD_TRY(adaptive_avgpool3d_fwd(y[2], nullptr, 0, out, 4, 4, 4, pooled, st));
+    A2HeadArgs ha = head_args();
+    ha.B = nw;
+    ha.training = 0;
+    ha.with_loss = 0;
+    if (g_a2_head_clip) {
+      ha.pooled = pooled;
+      hipLaunchKernelGGL(a2_head_fwd_clip_kernel, dim3((unsigned)nw), dim3(256), 0, st, ha);
+      VAD_LAUNCH_CHECK();
+    } else {
+      VAD_TRY(dense_fwd(pooled, nw, 4096, P(S_FCW), P(S_FCB), 16, f, DenseAct{}, scratch, scratch_floats, st));
+      for (int s = 0; s < 6; ++s) {
+        hipLaunchKernelGGL(a2_head_fwd_kernel, dim3((unsigned)cdiv(nw * A2_FWD_N[s], 256)), dim3(256), 0, st, ha, s);
+        VAD_LAUNCH_CHECK();
+      }
+    }
+    return 0;
+  }
+
   int forward(const float* x, hipStream_t st) {
+    win_dirty = false;
     for (int s3 = 0; s3 < 3; ++s3) {
       if (direct && s3 == 0) {
         const int64_t n = g[0].in.numel();
@@ -860,26 +949,10 @@ struct A2PlanImpl {
           VAD_HIP(hipMemcpyAsync(xin, x, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
           xsrc = xin;
         }
-        A2Prep pp{};
-        int64_t acc = 16 * (A2C1_TAPS + 1);
-        pp.end[0] = acc;
-        pp.w[0] = P(S_C1W);
-        pp.b1 = P(S_C1B);
-        pp.w1t = w1t;
-        for (int s = 1; s < 3; ++s) {
-          pp.w[s] = P(2 * s);
-          pp.wk[s] = wk3[s];
-          pp.wc[s] = wc3[s];
-          pp.Co[s] = A2_CO[s];
-          pp.Ci[s] = g[s].in.C;
-          acc += (int64_t)27 * g[s].in.C * A2_CO[s];
-          pp.end[s] = acc;
-        }
-        hipLaunchKernelGGL(a2_prep_kernel, dim3((unsigned)std::min<int64_t>(cdiv(acc, 256), 1024)), dim3(256), 0, st, pp);
-        VAD_LAUNCH_CHECK();
+        VAD_TRY(prep_images(st));
         const A2Tiles tl(B, T, H, W);
-        hipLaunchKernelGGL(a2_conv1_fwd_kernel, dim3((unsigned)std::min<int64_t>(tl.n, 4096)), dim3(256), 0, st, xsrc, B,
-                           T, H, W, w1t, y[0]);
+        hipLaunchKernelGGL(a2_conv1_fwd_kernel<false>, dim3((unsigned)std::min<int64_t>(tl.n, 4096)), dim3(256), 0, st,
+                           xsrc, B, T, H, W, w1t, y[0], WinSrc{});
         VAD_LAUNCH_CHECK();
         continue;
       }
@@ -943,6 +1016,8 @@ struct A2PlanImpl {
   }
 
   int backward(const float* ext_ds, const float* ext_dadj, const float* ext_df, hipStream_t st) {
+    VAD_CHECK(!win_dirty, "vad_a2_backward: vad_a2_windows_forward has overwritten this plan's activations since its "
+                          "last forward");
     VAD_TRY(backward_head(ext_ds, ext_dadj, ext_df, st));
     return backward_convs(st);
   }
@@ -1148,6 +1223,32 @@ int vad_a2_forward(vad_a2_plan* plan, const float* x, int training, uint64_t see
   plan->user_losses = losses;
   add(with_loss ? losses : nullptr, c.losses, 10);
   add(with_loss ? plan->host_losses : nullptr, c.losses, 10);
+  return a2_copies(cp, k, st);
+}
+
+int vad_a2_windows_forward(vad_a2_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
+                           int64_t ring, int nw, float* scores, float* adj, float* features, void* stream) {
+  VAD_CHECK(plan && frames, "vad_a2_windows_forward: null argument");
+  A2PlanImpl& c = plan->impl;
+  VAD_TRY(win_check("vad_a2_windows_forward", n_frames, first, stride, ring, nw, c.B, c.T));
+  VAD_CHECK(c.params != nullptr, "vad_a2_windows_forward: plan not bound");
+  hipStream_t st = (hipStream_t)stream;
+  // A single window runs as two copies of itself (stride 0), as a single clip does on the clip path -- a plan holds at
+  // least two clips, and the conv GEMMs choose their split of the reduction from the batch size -- and row 0 is kept.
+  const WinSrc ws{frames, 3ll * c.H * c.W, first, nw == 1 ? 0 : stride, ring};
+  VAD_TRY(c.forward_windows(ws, nw == 1 ? 2 : nw, st));
+  A2Copies cp{};
+  int k = 0;
+  auto add = [&](float* d, const float* s, int n) {
+    if (d) {
+      cp.dst[k] = d;
+      cp.src[k] = s;
+      cp.n[k++] = n;
+    }
+  };
+  add(scores, c.s, nw);
+  add(adj, c.adj, nw * 256);
+  add(features, c.f, nw * 16);
   return a2_copies(cp, k, st);
 }
 

@@ -36,13 +36,15 @@ static const FlatLayout& bb_layout() {
 // (= max of relu(conv + bias): fl(a + b) and relu are monotone in a).
 // WIN: x is a video, frame-major planar (N, 3, H, W), and clip b is its window of frames first + b * stride + d,
 // d = 0 .. T-1 (vad_bbox_windows_forward): only the address of the staging loop differs -- the zero padding at d < 0
-// and d >= T is the window's, as for a clip, so neighbouring frames of the video are never read in its place.
+// and d >= T is the window's, as for a clip, so neighbouring frames of the video are never read in its place.  The
+// source is a WinSrc (common.h): a linear video, or a ring of raw frames (vad_bbox_ring_forward); the frame of each of
+// the halo's 4 depth planes is resolved once, outside the element loop.
 template <bool WIN>
 __global__ __launch_bounds__(256) void bbox_conv1_pool_kernel(const float* __restrict__ x, int T, int H, int W,
                                                               const float* __restrict__ wT,
                                                               const float* __restrict__ bias, int T2, int H2,
                                                               int W2, int tiles_w, float* __restrict__ pooled,
-                                                              int64_t first, int64_t stride) {
+                                                              const WinSrc ws) {
   constexpr int PW = 18, PH = 18, PD = 4, CI = 3;
   __shared__ float xs[CI][PD][PH][PW + 1];
   const int tid = threadIdx.x;
@@ -52,18 +54,29 @@ __global__ __launch_bounds__(256) void bbox_conv1_pool_kernel(const float* __res
   const int b = blockIdx.y;
   const int py0 = (tr / tiles_w) * 8, px0 = (tr % tiles_w) * 8;
   const int d0 = 2 * pd - 1, y0 = 2 * py0 - 1, x0 = 2 * px0 - 1;
-  const float* xb = x + (int64_t)b * CI * T * H * W;
-  for (int i = tid; i < CI * PD * PH * PW; i += 256) {
-    const int xx = i % PW, yy = (i / PW) % PH, dd = (i / (PW * PH)) % PD, ci = i / (PW * PH * PD);
-    const int d = d0 + dd, y = y0 + yy, xw = x0 + xx;
-    float v = 0.f;
-    if (d >= 0 && d < T && y >= 0 && y < H && xw >= 0 && xw < W) {
-      if constexpr (WIN)
-        v = x[(((first + b * stride + d) * CI + ci) * H + y) * W + xw];
-      else
-        v = xb[(((int64_t)ci * T + d) * H + y) * W + xw];
+  if constexpr (WIN) {
+#pragma unroll
+    for (int dd = 0; dd < PD; ++dd) {
+      const int d = d0 + dd;
+      const bool in_t = d >= 0 && d < T;
+      const float* fr = in_t ? ws.frame(b, d) : nullptr;  // (block-uniform: one slot lookup per plane)
+      for (int i = tid; i < CI * PH * PW; i += 256) {
+        const int xx = i % PW, yy = (i / PW) % PH, ci = i / (PW * PH);
+        const int y = y0 + yy, xw = x0 + xx;
+        float v = 0.f;
+        if (in_t && y >= 0 && y < H && xw >= 0 && xw < W) v = fr[((int64_t)ci * H + y) * W + xw];
+        xs[ci][dd][yy][xx] = v;
+      }
     }
-    xs[ci][dd][yy][xx] = v;
+  } else {
+    const float* xb = x + (int64_t)b * CI * T * H * W;
+    for (int i = tid; i < CI * PD * PH * PW; i += 256) {
+      const int xx = i % PW, yy = (i / PW) % PH, dd = (i / (PW * PH)) % PD, ci = i / (PW * PH * PD);
+      const int d = d0 + dd, y = y0 + yy, xw = x0 + xx;
+      float v = 0.f;
+      if (d >= 0 && d < T && y >= 0 && y < H && xw >= 0 && xw < W) v = xb[(((int64_t)ci * T + d) * H + y) * W + xw];
+      xs[ci][dd][yy][xx] = v;
+    }
   }
   __syncthreads();
   const int pi = lane >> 3, pj = lane & 7;  // pooled voxel (py0 + pi, px0 + pj)
@@ -173,14 +186,16 @@ struct BbPlanImpl {
     w3 = w.take<float>(64 * 32 * 27);
   }
 
-  // x -> feature rows f (B, 1024); x: the B clips, or with win a video whose windows first + b * stride they are
-  int encoder(const float* x, float* f, hipStream_t st, bool win = false, int64_t first = 0, int64_t stride = 0) {
+  // x -> feature rows f (B, 1024); x: the B clips, or with win (x null) the windows of a video or ring that ws names
+  int encoder(const float* x, float* f, hipStream_t st, bool win = false, const WinSrc& ws = WinSrc{}) {
     DenseAct relu;
     relu.relu = 1;
     if (g_bbox_im2col) {  // (knob "bbox_im2col": the round-2 path -- im2col columns + f32 MFMA GEMMs)
+      VAD_CHECK(!win || ws.ring == 0, "vad_bbox_ring_forward: a ring needs the fused first layer (knob bbox_im2col = 0): "
+                                      "the im2col path reads windows as a strided view, which a ring is not");
       const int64_t hw = (int64_t)H * W;  // (a window is a strided view of the video: clip b, channel c, depth d)
-      const Strides5 sx = win ? Strides5{stride * 3 * hw, hw, 3 * hw, W, 1} : ncdhw_strides(g1.in);
-      VAD_TRY(im2col3d(x + (win ? first * 3 * hw : 0), sx, g1, nullptr, nullptr, 0, cols1, st));
+      const Strides5 sx = win ? Strides5{ws.stride * 3 * hw, hw, 3 * hw, W, 1} : ncdhw_strides(g1.in);
+      VAD_TRY(im2col3d(win ? ws.frames + ws.first * 3 * hw : x, sx, g1, nullptr, nullptr, 0, cols1, st));
       VAD_TRY(dense_fwd(cols1, (int)g1.rows(), g1.K(), P(0), P(1), 32, y1, relu, scratch, scratch_floats, st));
       VAD_TRY(maxpool3d_fwd(y1, nullptr, 0, g1.out(), 2, 2, 2, pooled, st));
       VAD_TRY(im2col3d(pooled, ndhwc_strides(pool_vol), g2, nullptr, nullptr, 0, cols2, st));
@@ -197,10 +212,10 @@ struct BbPlanImpl {
         const int tiles_w = (int)cdiv(pv.W, 8), tiles = (int)cdiv(pv.H, 8) * tiles_w;
         if (win)
           hipLaunchKernelGGL(bbox_conv1_pool_kernel<true>, dim3(pv.D * tiles, B), dim3(256), 0, st, x, T, H, W, wT1,
-                             P(1), pv.D, pv.H, pv.W, tiles_w, pooled, first, stride);
+                             P(1), pv.D, pv.H, pv.W, tiles_w, pooled, ws);
         else
           hipLaunchKernelGGL(bbox_conv1_pool_kernel<false>, dim3(pv.D * tiles, B), dim3(256), 0, st, x, T, H, W, wT1,
-                             P(1), pv.D, pv.H, pv.W, tiles_w, pooled, (int64_t)0, (int64_t)0);
+                             P(1), pv.D, pv.H, pv.W, tiles_w, pooled, WinSrc{});
         VAD_LAUNCH_CHECK();
       }
       VAD_TRY(conv3d_x3_fwd(B, pv.D, pv.H, pv.W, 32, 64, pooled, w3, P(3), y2, st));
@@ -227,10 +242,9 @@ struct BbPlanImpl {
     return head(f, scores, adj, st);
   }
 
-  int forward_windows(const float* frames, int64_t first, int64_t stride, float* scores, float* adj, float* features,
-                      hipStream_t st) {
+  int forward_windows(const WinSrc& ws, float* scores, float* adj, float* features, hipStream_t st) {
     float* f = features ? features : feats;
-    VAD_TRY(encoder(frames, f, st, true, first, stride));
+    VAD_TRY(encoder(nullptr, f, st, true, ws));
     return head(f, scores, adj, st);
   }
 };
@@ -290,7 +304,18 @@ int vad_bbox_windows_forward(vad_bbox_plan* plan, const float* frames, int64_t n
                 std::to_string(first) + " at stride " + std::to_string(stride) + " end past the video's " +
                 std::to_string(n_frames) + " frames");
   VAD_CHECK(plan->impl.params != nullptr, "vad_bbox_windows_forward: plan not bound");
-  return plan->impl.forward_windows(frames, first, stride, scores, adj, features, (hipStream_t)stream);
+  const WinSrc ws{frames, 3ll * plan->impl.H * plan->impl.W, first, stride, 0};
+  return plan->impl.forward_windows(ws, scores, adj, features, (hipStream_t)stream);
+}
+
+int vad_bbox_ring_forward(vad_bbox_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
+                          int64_t ring, float* scores, float* adj, float* features, void* stream) {
+  VAD_CHECK(plan && frames && scores && adj, "vad_bbox_ring_forward: null argument");
+  const int64_t B = plan->impl.B;
+  VAD_TRY(win_check("vad_bbox_ring_forward", n_frames, first, stride, ring, B, B, plan->impl.T));
+  VAD_CHECK(plan->impl.params != nullptr, "vad_bbox_ring_forward: plan not bound");
+  const WinSrc ws{frames, 3ll * plan->impl.H * plan->impl.W, first, stride, ring};
+  return plan->impl.forward_windows(ws, scores, adj, features, (hipStream_t)stream);
 }
 
 int vad_bbox_head_forward(vad_bbox_plan* plan, const float* features, float* scores, float* adj, void* stream) {

@@ -191,4 +191,46 @@ __device__ inline f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
+// ---------------------------------------------------------------- window source
+// Where the first layer of a clip model finds its input when the clips are windows of a video or of a ring of raw
+// frames: frames is frame-major, each frame planar (C, H, W), frame_floats = C * H * W apart; window b, time t is frame
+// first + b * stride + t, taken modulo ring when ring > 0 (a ring of that many slots).  Times t < 0 and t >= T are the
+// window's zero padding and are never looked up.  A loader resolves frame(b, t) once per staged halo plane -- the
+// 64-bit modulo stays out of its element and tap loops -- and indexes the plane with 64-bit pointer arithmetic.
+struct WinSrc {
+  const float* frames;
+  int64_t frame_floats, first, stride, ring;
+  __host__ __device__ int64_t slot(int64_t b, int t) const {
+    const int64_t f = first + b * stride + t;
+    return ring > 0 ? f % ring : f;
+  }
+  __device__ const float* frame(int64_t b, int t) const { return frames + slot(b, t) * frame_floats; }
+};
+
+// The argument checks every windows entry point makes before it queues anything (fn: its name, for the text): nw
+// windows of T frames on a plan of B clips, from a video of n_frames frames (ring = 0) or from a ring of ring <= n_frames
+// slots in which no window of the call may lap itself.  No product that could overflow.
+inline int win_check(const std::string& fn, int64_t n_frames, int64_t first, int64_t stride, int64_t ring, int64_t nw,
+                     int64_t B, int64_t T) {
+  VAD_CHECK(stride >= 1, fn + ": stride must be >= 1, got " + std::to_string(stride));
+  VAD_CHECK(first >= 0, fn + ": first must be >= 0, got " + std::to_string(first));
+  VAD_CHECK(nw >= 1 && nw <= B, fn + ": between 1 and the plan's " + std::to_string(B) + " windows per call, got " +
+                                    std::to_string(nw));
+  VAD_CHECK(ring >= 0, fn + ": ring must be >= 0 (0: a linear video), got " + std::to_string(ring));
+  const std::string what = std::to_string(nw) + " windows of " + std::to_string(T) + " frames from frame " +
+                           std::to_string(first) + " at stride " + std::to_string(stride);
+  if (ring == 0) {
+    VAD_CHECK(n_frames >= T && first <= n_frames - T && (nw == 1 || stride <= (n_frames - T - first) / (nw - 1)),
+              fn + ": " + what + " end past the video's " + std::to_string(n_frames) + " frames");
+    return 0;
+  }
+  VAD_CHECK(ring <= n_frames, fn + ": a ring of " + std::to_string(ring) + " slots in a buffer of " +
+                                  std::to_string(n_frames) + " frames");
+  VAD_CHECK(ring >= T, fn + ": a ring of " + std::to_string(ring) + " slots holds no window of " + std::to_string(T) +
+                           " frames");
+  VAD_CHECK(nw == 1 || stride <= (ring - T) / (nw - 1),
+            fn + ": " + what + " span more than the ring's " + std::to_string(ring) + " slots");
+  return 0;
+}
+
 }  // namespace vad

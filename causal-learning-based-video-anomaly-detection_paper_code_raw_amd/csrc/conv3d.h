@@ -77,6 +77,11 @@ int conv3d_direct_prep(const float* w, int Co, int Ci, float* wf, float* wd, hip
 // out (NDHWC, in's spatial dims, CO channels) = conv(src) + bias (nullable)
 int conv3d_direct_fwd(const float* src, const Strides5& s, const Vol5& in, const float* w, int CO, const float* bias,
                       float* out, hipStream_t st);
+// the same over the windows of a video or ring (common.h WinSrc): clip n of in = (nw, C, T, H, W) is
+// window n of ws, read in place -- only the staging address differs, the arithmetic and its order do not.  The frames
+// are addressed in 64 bit, so the video or ring may be of any size; `in` keeps conv3d_direct_fwd's limits.
+int conv3d_direct_fwd_windows(const WinSrc& ws, const Vol5& in, const float* w, int CO, const float* bias, float* out,
+                              hipStream_t st);
 // dW [Co][Ci][27] and db [Co] (nullable) written (not accumulated) from dY (NDHWC, CO channels) and the forward input
 int conv3d_direct_wgrad(const float* dy, int CO, const float* src, const Strides5& s, const Vol5& in, float* dW,
                         float* db, float* slab, int64_t slab_floats, hipStream_t st);

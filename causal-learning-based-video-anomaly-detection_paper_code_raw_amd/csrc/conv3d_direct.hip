@@ -63,8 +63,28 @@ __device__ __forceinline__ void stage_halo(float* xs, const float* src, const St
   }
 }
 
-template <int CO>
-__global__ __launch_bounds__(256) void conv3d_direct_kernel(const DirectArgs p) {
+// stage_halo for a window source (WIN form of conv3d_direct_kernel): clip n is window n of ws, whose frames are planar
+// (C, H, W); the frame of each of the halo's HD depth planes is resolved once (block-uniform), outside the element loop
+__device__ __forceinline__ void stage_halo_win(float* xs, const WinSrc& ws, const Vol5& in, int n, int d0, int h0,
+                                               int w0, int c0, int cn, int tid) {
+#pragma unroll
+  for (int hd = 0; hd < HD; ++hd) {
+    const int d = d0 - 1 + hd;
+    const bool in_t = d >= 0 && d < in.D;
+    const float* fr = in_t ? ws.frame(n, d) : nullptr;
+    for (int q = tid; q < cn * HH * HW; q += 256) {
+      const int ci = q / (HH * HW), hv = q % (HH * HW), hh = hv / HW, hw = hv % HW;
+      const int h = h0 - 1 + hh, w = w0 - 1 + hw;
+      float v = 0.f;
+      if (in_t && h >= 0 && h < in.H && w >= 0 && w < in.W) v = fr[((int64_t)(c0 + ci) * in.H + h) * in.W + w];
+      xs[ci * HALO + hd * (HH * HW) + hv] = v;
+    }
+  }
+}
+
+// WIN: the source is win (p.src and p.s are not read); everything behind the staged halo is the clip form's
+template <int CO, bool WIN = false>
+__global__ __launch_bounds__(256) void conv3d_direct_kernel(const DirectArgs p, const WinSrc win) {
   __shared__ float xs[CIB * HALO];
   __shared__ __attribute__((aligned(16))) float ws[CIB * 27 * CO];
   const int tid = threadIdx.x;
@@ -79,7 +99,10 @@ __global__ __launch_bounds__(256) void conv3d_direct_kernel(const DirectArgs p) 
     for (int c0 = 0; c0 < Ci; c0 += CIB) {
       const int cn = min(CIB, Ci - c0);
       __syncthreads();  // the previous chunk's (or tile's) LDS reads are done
-      stage_halo(xs, p.src, p.s, p.in, n, d0, h0, w0, c0, cn, tid);
+      if constexpr (WIN)
+        stage_halo_win(xs, win, p.in, n, d0, h0, w0, c0, cn, tid);
+      else
+        stage_halo(xs, p.src, p.s, p.in, n, d0, h0, w0, c0, cn, tid);
       for (int q = tid; q < cn * 27 * CO; q += 256)
         ws[q] = p.w[(int64_t)(c0 * 27 + q / CO) * p.CoT + co0 + q % CO];  // ([ci][tap] rows of CO)
       __syncthreads();
@@ -272,8 +295,9 @@ int conv3d_direct_prep(const float* w, int Co, int Ci, float* wf, float* wd, hip
   return 0;
 }
 
-int conv3d_direct_fwd(const float* src, const Strides5& s, const Vol5& in, const float* w, int CO, const float* bias,
-                      float* out, hipStream_t st) {
+template <bool WIN>
+static int direct_fwd_launch(const float* src, const Strides5& s, const WinSrc& ws, const Vol5& in, const float* w, int CO,
+                             const float* bias, float* out, hipStream_t st) {
   VAD_CHECK(CO == 8 || CO == 16 || CO == 32, "conv3d_direct_fwd: output channels 8, 16 or 32");
   VAD_CHECK(in.C >= 1 && in.numel() < (1ll << 31) && in.voxels() * CO < (1ll << 31),
             "conv3d_direct_fwd: volume too large for 32-bit voxel offsets");
@@ -290,11 +314,22 @@ int conv3d_direct_fwd(const float* src, const Strides5& s, const Vol5& in, const
   // few tiles (small volumes): the output channels split over block rows so the grid still covers the CUs
   const int split = (a.ntiles < 256 && CO >= 16) ? 2 : 1, cb = CO / split;
   const dim3 grid((unsigned)std::min(a.ntiles, 2048), (unsigned)split);
-  if (cb == 8) hipLaunchKernelGGL(conv3d_direct_kernel<8>, grid, dim3(256), 0, st, a);
-  else if (cb == 16) hipLaunchKernelGGL(conv3d_direct_kernel<16>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(conv3d_direct_kernel<32>, grid, dim3(256), 0, st, a);
+  if (cb == 8) hipLaunchKernelGGL((conv3d_direct_kernel<8, WIN>), grid, dim3(256), 0, st, a, ws);
+  else if (cb == 16) hipLaunchKernelGGL((conv3d_direct_kernel<16, WIN>), grid, dim3(256), 0, st, a, ws);
+  else hipLaunchKernelGGL((conv3d_direct_kernel<32, WIN>), grid, dim3(256), 0, st, a, ws);
   VAD_LAUNCH_CHECK();
   return 0;
+}
+
+int conv3d_direct_fwd(const float* src, const Strides5& s, const Vol5& in, const float* w, int CO, const float* bias,
+                      float* out, hipStream_t st) {
+  return direct_fwd_launch<false>(src, s, WinSrc{}, in, w, CO, bias, out, st);
+}
+
+int conv3d_direct_fwd_windows(const WinSrc& ws, const Vol5& in, const float* w, int CO, const float* bias, float* out,
+                              hipStream_t st) {
+  VAD_CHECK(ws.frame_floats == (int64_t)in.C * in.H * in.W, "conv3d_direct_fwd_windows: frames of C * H * W floats");
+  return direct_fwd_launch<true>(nullptr, Strides5{}, ws, in, w, CO, bias, out, st);
 }
 
 int64_t conv3d_direct_wgrad_slab_floats(const Vol5& in, int CO) {

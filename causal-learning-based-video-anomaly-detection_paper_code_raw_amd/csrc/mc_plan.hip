@@ -230,6 +230,7 @@ struct McPlanImpl {
   uint64_t seed = 0, step = 0;
   int64_t clip0 = 0;
   bool have_labels = false;
+  bool win_dirty = false;  // the activations are a windows call's: no backward until the next clip forward
 
   McPlanImpl(int B_, int C_, int T_, int H_, int W_) : B(B_), C(C_), T(T_), H(H_), W(W_), LY(C_) {
     Vol5 in{B, C, T, H, W};
@@ -318,6 +319,7 @@ struct McPlanImpl {
   int forward(const float* x, float* scores, hipStream_t st) {
     // direct convs (conv3d_direct.hip) keep the input for the weight gradient instead of the im2col columns
     direct_fwd = direct(0) && direct(1) && direct(2);
+    win_dirty = false;
     if (direct_fwd)
       VAD_HIP(hipMemcpyAsync(xin, x, g[0].in.numel() * sizeof(float), hipMemcpyDeviceToDevice, st));
     for (int s = 0; s < 3; ++s) {
@@ -349,6 +351,42 @@ struct McPlanImpl {
     return 0;
   }
 
+  // The first nw clips of the plan as windows of a video or ring (vad_mc_windows_forward), eval semantics: the forward
+  // above with training = 0 on nw clips, conv 1 reading the frames in place.  The running statistics, the counters,
+  // the plan's loss and status words and its per-call state are left alone (the classifier's three loss words go to
+  // the BatchNorm partials scratch, which nothing reads in eval mode); the activations are overwritten, so a backward
+  // is refused until the next clip forward (win_dirty).
+  int forward_windows(const WinSrc& src, int nw, float* scores, hipStream_t st) {
+    VAD_CHECK(direct(0) && direct(1) && direct(2),
+              "vad_mc_windows_forward: windows are read by the direct 3-D convs only (knob conv3d_direct = 1 and at most "
+              "16 input channels); the im2col path has no windows form");
+    win_dirty = true;
+    for (int s = 0; s < 3; ++s) {
+      const int Co = MC_CO[s];
+      Vol5 in = g[s].in, co = conv_out[s];
+      in.N = co.N = nw;
+      VAD_TRY(conv3d_direct_prep(P(LY.conv_w[s]), Co, in.C, wf[s], wd[s], st));
+      if (s == 0) VAD_TRY(conv3d_direct_fwd_windows(src, in, wf[s], Co, P(LY.conv_b[s]), y[s], st));
+      else VAD_TRY(conv3d_direct_fwd(pooled[s - 1], ndhwc_strides(in), in, wf[s], Co, P(LY.conv_b[s]), y[s], st));
+      VAD_TRY(bn_finalize(parts, 0, Co, (double)co.voxels(), P(LY.bn_w[s]), P(LY.bn_b[s]), RM(s), RV(s), 0.1f, 1e-5f, 0,
+                          stats[s], st));
+      VAD_TRY(maxpool3d_fwd(y[s], stats[s], 1, co, MC_POOL[s][0], MC_POOL[s][1], MC_POOL[s][2], pooled[s], st));
+    }
+    Vol5 pv = pooled_vol[2];
+    pv.N = nw;
+    VAD_TRY(adaptive_avgpool3d_fwd(pooled[2], nullptr, 0, pv, 1, 1, 1, feats, st));
+    McHeadArgs a = head_args();
+    a.B = nw;
+    a.training = 0;
+    a.labels = nullptr;
+    a.flags = nullptr;
+    a.losses = parts;
+    a.scores = scores;
+    hipLaunchKernelGGL(mc_head_fwd_kernel, dim3(1), dim3(256), 0, st, a);
+    VAD_LAUNCH_CHECK();
+    return 0;
+  }
+
   // everything behind the average pool, on the plan's feature rows: the classifier (Dropout x2 from the keyed RNG),
   // the BCE and the status words (vad_mc_head_forward runs this alone)
   int head(float* scores, hipStream_t st) {
@@ -361,6 +399,8 @@ struct McPlanImpl {
 
   int backward(const float* d_scores, hipStream_t st) {
     VAD_CHECK(d_scores || have_labels, "vad_mc_backward: no labels in the forward and no d_scores");
+    VAD_CHECK(!win_dirty, "vad_mc_backward: vad_mc_windows_forward has overwritten this plan's activations since its "
+                          "last forward");
     VAD_TRY(backward_head(d_scores, st));
     return backward_convs(st);
   }
@@ -489,6 +529,16 @@ int vad_mc_forward(vad_mc_plan* plan, const float* x, int training, uint64_t see
   plan->user_losses = losses;
   if (losses) VAD_HIP(hipMemcpyAsync(losses, c.losses, 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
   return 0;
+}
+
+int vad_mc_windows_forward(vad_mc_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
+                           int64_t ring, int nw, float* scores, void* stream) {
+  VAD_CHECK(plan && frames && scores, "vad_mc_windows_forward: null argument");
+  McPlanImpl& c = plan->impl;
+  VAD_TRY(win_check("vad_mc_windows_forward", n_frames, first, stride, ring, nw, c.B, c.T));
+  VAD_CHECK(c.params != nullptr, "vad_mc_windows_forward: plan not bound");
+  const WinSrc ws{frames, (int64_t)c.C * c.H * c.W, first, stride, ring};
+  return c.forward_windows(ws, nw, scores, (hipStream_t)stream);
 }
 
 int vad_mc_backward(vad_mc_plan* plan, const float* d_scores, void* stream) {

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
-from ._flat import FlatEngine
+from ._flat import FlatEngine, FlatPlan
 
 
 class SimpleVideoAnomalyDetector(nn.Module):
@@ -80,6 +80,34 @@ class SimpleVideoAnomalyDetector(nn.Module):
         params = [p for _, p in self.named_parameters()]  # slot order == named_parameters order
         return _McFunction.apply(x, e, self.training, seed, step, clip0, *params)
 
+    def scoring_engine(self, device) -> "McEngine":
+        """The engine on `device`, made if need be, without choosing a clip plan (score_video, open_stream)."""
+        e = self._engine
+        if e is None or e.device != device:
+            e = self._engine = McEngine(self, device)
+        return e
+
+    def score_video(self, frames, window=None, stride=4, batch=64) -> dict:
+        """Score every full window ``range(0, N - window + 1, stride)`` of a video: frames fp32 (N, C, H, W) on the
+        device (``data.ingest_u8(u8, (64, 64), 1)`` builds grey ones from camera bytes); window defaults to
+        temporal_frames.  Windows run ``batch`` at a time and are never copied into clips: the first conv reads window
+        b's frames in place (``vad_mc_windows_forward``).  Returns anomaly_scores (W,) -- for window w what
+        ``model(clip)`` returns in eval mode for frames[start:start + window] as a (C, T, H, W) clip -- and window_starts
+        (W,) int64 on the host.  Eval mode only: BatchNorm3d uses the running statistics and no buffer is written; runs
+        on plans of its own, so a pending backward is not disturbed."""
+        from .clip_stream import check_score_video, score_video
+        window = self.temporal_frames if window is None else window
+        x = check_score_video("mc", self, frames, window, stride, batch)
+        nat.require_hip(x)
+        return score_video(self.scoring_engine(x.device), x.float().contiguous(), int(window), int(stride), int(batch))
+
+    def open_stream(self, window=None, stride=1, *, max_push=1, frame_size=None):
+        """A clip_stream.ClipStream on this model: push frames (k, C, H, W) as they arrive, get score_video's keys for
+        the windows they complete, read from a ring of window + max_push - 1 raw frames."""
+        from .clip_stream import ClipStream
+        window = self.temporal_frames if window is None else window
+        return ClipStream(self, "mc", window, stride, max_push=max_push, frame_size=frame_size)
+
 
 class _McFunction(torch.autograd.Function):
     @staticmethod
@@ -95,9 +123,17 @@ class _McFunction(torch.autograd.Function):
         return (None, None, None, None, None, None, *e.grad_clones())
 
 
+class _McPlan(FlatPlan):
+    @staticmethod
+    def create_args(B, C, T, H, W, *tag):  # tag ("windows",): a scoring plan, apart from the clip plan of its shape
+        return B, C, T, H, W
+
+
 class McEngine(FlatEngine):
     """Flat device buffers (params / grads / BN buffers / Adam state, state_dict order) shared by per-shape plans
     (keyed by the input's (B, C, T, H, W))."""
+    PLAN = _McPlan
+    WINDOW_KEYS = ("anomaly_scores",)
 
     def __init__(self, model: SimpleVideoAnomalyDetector, device):
         super().__init__(model, device, "mc", replace_params=True, opt_state="eager", grad_tail=256,
@@ -118,6 +154,18 @@ class McEngine(FlatEngine):
                                            nat.ptr(labels) if labels is not None else None, nat.ptr(self.scores),
                                            nat.ptr(self.losses), nat.ptr(self.flags), self.stream()))
         return self.scores
+
+    def window_outputs(self, n):
+        return (torch.empty(n, dtype=torch.float32, device=self.device),)
+
+    def windows_forward(self, frames, first, stride, ring, nw, T, B, out):
+        """nw <= B windows of frames (n, C, H, W) -- a video (ring 0) or a ring of `ring` slots -- into out[0].  The
+        plan is a scoring plan: no clip forward runs on it, so no backward can be pending on the activations it
+        overwrites."""
+        n, C, H, W = frames.shape
+        p = self.plan(B, C, T, H, W, "windows")
+        nat.check(nat.lib().vad_mc_windows_forward(p.h, nat.ptr(frames), n, first, stride, ring, nw, nat.ptr(out[0]),
+                                                   self.stream()))
 
     def backward(self):
         """Backward of the BCE loss of the last forward (StableTrainer path)."""

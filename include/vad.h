@@ -356,6 +356,18 @@ int vad_mc_bind(vad_mc_plan* plan, void* workspace, float* params, float* grads,
  * the last three are filled by vad_mc_optimizer_step.  Dropout keys: (seed, step, clip0 + b). */
 int vad_mc_forward(vad_mc_plan* plan, const float* x, int training, uint64_t seed, uint64_t step, int64_t clip0,
                    const float* labels, float* scores, float* losses, int32_t* flags, void* stream);
+/* The first nw clips of the plan as windows of a video or of a ring of raw frames, eval semantics
+ * (training = 0: BatchNorm3d on the running statistics, no dropout): frames (n_frames, C, H, W) fp32 frame-major planar;
+ * window b, time t is frame first + b * stride + t, modulo ring when ring > 0 (a ring of ring <= n_frames slots); the
+ * first conv reads it in place, its temporal zero padding per window as for a clip.  scores (nw,).  running_mean,
+ * running_var, num_batches_tracked, labels, losses and status words are neither read nor written.  The plan's
+ * activations are overwritten: vad_mc_backward is refused until the next vad_mc_forward.  Refused before any launch:
+ * a null pointer, stride < 1, first < 0, nw outside 1..B, ring < 0; ring = 0: first + (nw - 1) * stride + T > n_frames;
+ * ring > 0: ring > n_frames, ring < T, (nw - 1) * stride + T > ring (a window of the call would lap another); an
+ * unbound plan; a plan whose convs run on the im2col path (knob conv3d_direct = 0 or C > 16), which has no windows
+ * form. */
+int vad_mc_windows_forward(vad_mc_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
+                           int64_t ring, int nw, float* scores, void* stream);
 /* d_scores (B,) nullable: NULL = backward of the forward's BCE (requires labels) */
 int vad_mc_backward(vad_mc_plan* plan, const float* d_scores, void* stream);
 /* grad norm (float64 sum of per-param norm^2); clip_grad_norm_(max_norm) only when norm > clip_above; Adam */
@@ -403,6 +415,16 @@ int vad_a2_forward(vad_a2_plan* plan, const float* x, int training, uint64_t see
 /* "borrow_input" 1: the next forwards read x in place and the backward reads it again (the caller keeps it unchanged
  * until then, as the fused train step does); 0 (default): the forward copies x for conv3d_1's weight gradient */
 int vad_a2_set_option(vad_a2_plan* plan, const char* key, int64_t value);
+/* The first nw clips of the plan as windows of a video or of a ring of raw frames, forward only, eval
+ * semantics (no dropout, no loss, nothing kept for a backward): frames (n_frames, 3, H, W) fp32 frame-major planar RGB;
+ * window b, time t is frame first + b * stride + t, modulo ring when ring > 0; conv3d_1 reads it in place (nothing is
+ * copied into the plan, borrow_input is ignored).  Outputs (nullable): scores (nw,), adj (nw,16,16), features (nw,16)
+ * -- what vad_a2_forward(training = 0) gives for the nw gathered clips; nw = 1 runs as two copies of the window, as a
+ * single clip must on the clip path, and returns the first.  The plan's activations are overwritten: vad_a2_backward
+ * is refused until the next vad_a2_forward.  Refused before any launch: as vad_mc_windows_forward; a plan created with
+ * knob a2_direct = 0. */
+int vad_a2_windows_forward(vad_a2_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
+                           int64_t ring, int nw, float* scores, float* adj, float* features, void* stream);
 /* compute_improved_loss alone, on the last forward's scores / adjacency (pseudo-labels keyed by seed/step/clip0);
  * vad_a2_loss_grads copies d total / d scores (B,) and d total / d adj (B,16,16) of that loss */
 int vad_a2_loss(vad_a2_plan* plan, uint64_t seed, uint64_t step, int64_t clip0, float* losses, void* stream);
@@ -454,6 +476,13 @@ int vad_bbox_forward(vad_bbox_plan* plan, const float* x, float* scores, float* 
  * first < 0, first + (B - 1) * stride + T > n_frames, an unbound plan. */
 int vad_bbox_windows_forward(vad_bbox_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
                              float* scores, float* adj, float* features, void* stream);
+/* vad_bbox_windows_forward on a ring of raw frames: frames holds n_frames >= ring frames, and window b,
+ * time t is frame (first + b * stride + t) mod ring.  Refused before any launch: a null pointer, stride < 1, first < 0,
+ * ring < T or > n_frames, (B - 1) * stride + T > ring (a window of the call would lap another), an unbound plan, and
+ * -- at the launch of the first layer -- knob bbox_im2col = 1, whose strided view cannot express a ring.  ring = 0 is
+ * vad_bbox_windows_forward. */
+int vad_bbox_ring_forward(vad_bbox_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
+                          int64_t ring, float* scores, float* adj, float* features, void* stream);
 /* Test seams.  vad_bbox_forward is encoder (x -> features) then head (features -> scores, adj);
  * vad_bbox_head_forward runs the head alone -- the causal_net and classifier GEMMs and the sigmoid tail -- on feature
  * rows (B, 1024) the caller chose.  vad_bbox_debug_buffer hands out the workspace arrays of the last forward:
