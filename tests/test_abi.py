@@ -1,5 +1,6 @@
-"""C ABI checks that need no GPU: the library loads, exports every function include/vad.h declares, its slot
-table matches the drop-in module's parameters, and errors come back as codes + text."""
+"""C ABI checks that need no GPU: the library loads, exports every function include/vad.h declares and is bound with
+the signatures the header declares, its slot table matches the drop-in module's parameters, and errors come back as
+codes + text."""
 import ctypes
 import os
 import re
@@ -27,6 +28,103 @@ def test_library_exports_every_declared_symbol():
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing
     assert L.vad_abi_version() == 1
+
+
+_P, _I, _I64, _U64, _U32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32
+_F, _D, _S = ctypes.c_float, ctypes.c_double, ctypes.c_char_p
+
+_HEADER_CASES = """
+/* a header in the small: every form include/vad.h holds */
+#ifndef X_H_
+#define X_H_
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define VAD_ABI_VERSION 1
+int vad_abi_version(void);
+const char* vad_last_error(void);
+typedef struct vad_x_plan vad_x_plan;
+int vad_x_create(int B, int T, vad_x_plan** out);
+void vad_x_destroy(vad_x_plan* plan);
+int64_t vad_x_workspace_bytes(const vad_x_plan* p);   /* bytes (not floats) */
+/* broken over three lines, a comment with ( brackets ) and a , between two parameters */
+int vad_x_forward(vad_x_plan* plan, const float* x, int training, uint64_t seed,
+                  uint32_t stream_id, /* keyed (seed, step) draws */ int64_t clip0, float scale, double drop_p,
+                  const int32_t* flags, const float* const* W, void* stream);
+typedef int (*vad_bn_sync_fn)(void* user, int bn_layer, int phase, int64_t n, void* stream);
+int vad_x_set_bn_sync(vad_x_plan* plan, vad_bn_sync_fn fn, void* user, int world);
+int vad_x_set_option(vad_x_plan* plan, const char* key, int64_t value);
+int vad_x_profile_read(vad_x_plan* plan, char* labels, double* total_ms, int* counts, int cap);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_parser_forms():
+    """_parse_header on literal text: every form of declaration and parameter vad.h holds, the lines it skips, and its
+    refusal to guess."""
+    from vad_amd import _native
+    parse = _native._parse_header
+    assert parse(_HEADER_CASES) == {
+        "vad_abi_version": (_I, []),
+        "vad_last_error": (_S, []),
+        "vad_x_create": (_I, [_I, _I, _P]),
+        "vad_x_destroy": (None, [_P]),
+        "vad_x_workspace_bytes": (_I64, [_P]),
+        "vad_x_forward": (_I, [_P, _P, _I, _U64, _U32, _I64, _F, _D, _P, _P, _P]),
+        "vad_x_set_bn_sync": (_I, [_P, _native.BN_SYNC_FN, _P, _I]),
+        "vad_x_set_option": (_I, [_P, _S, _I64]),
+        "vad_x_profile_read": (_I, [_P, _P, _P, _P, _I]),
+    }
+    assert _native.BN_SYNC_FN._restype_ is _I and _native.BN_SYNC_FN._argtypes_ == (_P, _I, _I, _I64, _P)
+    for text, words in [("int vad_x_f(int a, size_t n);", ("vad_x_f", "size_t")),          # a scalar not in the table
+                        ("int vad_x_g(vad_x_plan plan);", ("vad_x_g", "vad_x_plan")),      # a struct by value
+                        ("int vad_x_h(int32_t v, void* stream);", ("vad_x_h", "int32_t")),
+                        ("size_t vad_x_i(void);", ("vad_x_i", "size_t")),                  # an unknown return type
+                        ("int vad_x_j(int);", ("vad_x_j", "int")),                         # no parameter name
+                        ("int vad_x_k();", ("vad_x_k",)),
+                        ("int vad_x_l(void); int vad_x_l(int a);", ("vad_x_l",)),          # declared twice
+                        ("int vad_x_m(int a) { return a; }", ("vad_x_m",)),                # not a declaration
+                        ("struct vad_x_plan { int a; };", ("struct",))]:
+        with pytest.raises(ValueError) as e:
+            parse(text)
+        assert all(w in str(e.value) for w in words), (text, str(e.value))
+
+
+# typed from include/vad.h by hand, so that the parser cannot pass by agreeing with itself
+_PINNED = {
+    "vad_last_error": (_S, []),
+    "vad_cad_destroy": (None, [_P]),
+    "vad_cad_slot_offset": (_I64, [_I]),
+    "vad_cad_forward": (_I, [_P, _P, _I, _U64, _U64, _I64] + [_P] * 13),
+    "vad_cad_windows_forward_group": (_I, [_P, _P, _I64, _I, _I, _P, _I, _P, _U64, _U64] + [_P] * 8),
+    "vad_cad_optimizer_step": (_I, [_P] + [_F] * 7 + [_P, _P]),
+    "vad_cad_set_option": (_I, [_P, _S, _I64]),
+    "vad_cad_profile_read": (_I, [_P, _P, _P, _P, _I]),
+    "vad_dense_forward_ex": (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _D, _U64, _U32, _U64, _I64, _I, _P, _I64, _P]),
+    "vad_ae_bind": (_I, [_P] * 11),
+    "vad_ingest_u8_color": (_I, [_P, _I64, _I, _I, _I64, _I64, _I, _I, _I, _I, _I, _P, _P]),
+    "vad_head_backward": (_I, [_P, _I, _I, _P, _I, _U64, _U64, _I64] + [_P] * 16 + [_I64, _P]),
+}
+
+
+def test_signatures_come_from_the_header():
+    """Every function vad.h declares has its entry in _SIGS, the loaded library carries exactly those types, and the
+    entries pinned above are what the header says."""
+    from vad_amd import _native
+    L = _native.lib()
+    names = _declared()
+    assert sorted(_native._SIGS) == names
+    for name in names:
+        res, args = _native._SIGS[name]
+        fn = getattr(L, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    for name, sig in _PINNED.items():
+        assert _native._SIGS[name] == sig, name
+    assert _native._SIGS["vad_cad_set_bn_sync"] == (_I, [_P, _native.BN_SYNC_FN, _P, _I])
 
 
 # the tuning keys the test suite sets: retiring one of them would strand a test
