@@ -109,6 +109,12 @@ class CausalAnomalyDetector(nn.Module):
         from .clip_stream import ClipStream
         return ClipStream(self, "a2", window, stride, max_push=max_push, frame_size=frame_size)
 
+    def open_stream_group(self, num_streams, window=8, stride=1, *, max_push=1, frame_size=None):
+        """A clip_stream_group.ClipStreamGroup on this model: num_streams cameras of one frame size, one windows call
+        per push for the windows of all of them."""
+        from .clip_stream_group import ClipStreamGroup
+        return ClipStreamGroup(self, "a2", num_streams, window, stride, max_push=max_push, frame_size=frame_size)
+
 
 class _A2Function(torch.autograd.Function):
     @staticmethod
@@ -196,6 +202,15 @@ class A2Engine(FlatEngine):
         p = self.plan(max(B, 2), 3, T, H, W, "windows")
         nat.check(nat.lib().vad_a2_windows_forward(p.h, nat.ptr(frames), n, first, stride, ring, nw, *map(nat.ptr, out),
                                                    self.stream()))
+
+    def windows_forward_group(self, ring, cap, h_win, nw, dev_table, T, B, out):
+        """nw <= B windows of a group's rings (total_slots, 3, H, W), cap slots each, through the host rows h_win
+        (nw, 2) int64 and the caller's device table (vad_a2_windows_forward_group), into the tensors out; on
+        windows_forward's scoring plan."""
+        n, _, H, W = ring.shape
+        p = self.plan(max(B, 2), 3, T, H, W, "windows")
+        nat.check(nat.lib().vad_a2_windows_forward_group(p.h, nat.ptr(ring), n, cap, h_win.data_ptr(), nw,
+                                                         nat.ptr(dev_table), *map(nat.ptr, out), self.stream()))
 
     def set_host_losses(self, buf):
         """Let the current plan's forward also write its 10 loss words into `buf` (a pinned CPU tensor; None: stop)."""

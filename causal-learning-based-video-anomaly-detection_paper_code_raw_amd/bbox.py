@@ -81,6 +81,14 @@ class CausalAnomalyDetector(nn.Module):
         window = self.num_frames if window is None else window
         return ClipStream(self, "bbox", window, stride, max_push=max_push, frame_size=frame_size)
 
+    def open_stream_group(self, num_streams, window=None, stride=1, *, max_push=1, frame_size=None):
+        """A clip_stream_group.ClipStreamGroup on this model: num_streams cameras of one frame size, one windows call
+        per push for the windows of all of them (``vad_bbox_windows_forward_group``); window defaults to
+        num_frames."""
+        from .clip_stream_group import ClipStreamGroup
+        window = self.num_frames if window is None else window
+        return ClipStreamGroup(self, "bbox", num_streams, window, stride, max_push=max_push, frame_size=frame_size)
+
 
 def check_score_video(model, frames, window, stride, batch) -> torch.Tensor:
     """The ValueErrors of score_video, raised before any device work; returns the frames."""
@@ -145,6 +153,16 @@ class BboxEngine(FlatEngine):
         p = self.plan(nw, 3, T, H, W)
         nat.check(nat.lib().vad_bbox_ring_forward(p.h, nat.ptr(frames), n, first, stride, ring, *map(nat.ptr, out),
                                                   nat.stream_of(self.device)))
+
+    def windows_forward_group(self, ring, cap, h_win, nw, dev_table, T, B, out):
+        """nw windows of a group's rings (total_slots, 3, H, W), cap slots each, through the host rows h_win (nw, 2)
+        int64 and the caller's device table (vad_bbox_windows_forward_group), into the tensors out; on the plan of
+        exactly nw clips, as windows_forward."""
+        n, _, H, W = ring.shape
+        p = self.plan(nw, 3, T, H, W)
+        nat.check(nat.lib().vad_bbox_windows_forward_group(p.h, nat.ptr(ring), n, cap, h_win.data_ptr(), nw,
+                                                           nat.ptr(dev_table), *map(nat.ptr, out),
+                                                           nat.stream_of(self.device)))
 
     def score_video(self, x, window, stride, batch) -> dict:
         """x (N, 3, H, W) fp32 contiguous on the engine's device, checked."""

@@ -18,6 +18,7 @@
 #include "../../include/vad.h"
 #include "backbone.h"
 #include "conv3d.h"
+#include "group_table.h"
 #include "optim.h"
 #include "plan_util.h"
 
@@ -903,9 +904,14 @@ struct A2PlanImpl {
   // eval semantics on nw clips, conv3d_1 reading the frames in place -- no copy into xin, borrow_input ignored, no
   // dropout, no loss.  The plan's per-call state (training, seed, step, clip0, with_loss, xsrc) is left alone; its
   // activations are overwritten, so a backward is refused until the next clip forward (win_dirty).
-  int forward_windows(const WinSrc& src, int nw, hipStream_t st) {
+  int check_windows() const {
     VAD_CHECK(direct, "vad_a2_windows_forward: windows are read by the direct first conv only (knob a2_direct = 1 when "
                       "the plan was created); the im2col path has no windows form");
+    return 0;
+  }
+
+  int forward_windows(const WinSrc& src, int nw, hipStream_t st) {
+    VAD_TRY(check_windows());
     win_dirty = true;
     VAD_TRY(prep_images(st));
     const A2Tiles tl(nw, T, H, W);
@@ -1237,6 +1243,50 @@ int vad_a2_windows_forward(vad_a2_plan* plan, const float* frames, int64_t n_fra
   // least two clips, and the conv GEMMs choose their split of the reduction from the batch size -- and row 0 is kept.
   const WinSrc ws{frames, 3ll * c.H * c.W, first, nw == 1 ? 0 : stride, ring};
   VAD_TRY(c.forward_windows(ws, nw == 1 ? 2 : nw, st));
+  A2Copies cp{};
+  int k = 0;
+  auto add = [&](float* d, const float* s, int n) {
+    if (d) {
+      cp.dst[k] = d;
+      cp.src[k] = s;
+      cp.n[k++] = n;
+    }
+  };
+  add(scores, c.s, nw);
+  add(adj, c.adj, nw * 256);
+  add(features, c.f, nw * 16);
+  return a2_copies(cp, k, st);
+}
+
+// A group of streams.  The device table of the three clip models' group windows calls (group_table.h,
+// which also validates it): nw rows of 2 int64 each (base, first), no destination part; two rows at least, as a2 runs
+// a single window twice.
+int64_t vad_win_group_table_bytes(int64_t nw) {
+  if (nw < 1 || nw > (1ll << 31)) {
+    vad::set_error("vad_win_group_table_bytes: nw must be in 1..2^31, got " + std::to_string(nw));
+    return -1;
+  }
+  return std::max<int64_t>(nw, 2) * 16;
+}
+
+int vad_a2_windows_forward_group(vad_a2_plan* plan, const float* ring, int64_t total_slots, int cap,
+                                 const int64_t* host_windows, int nw, void* dev_table, float* scores, float* adj,
+                                 float* features, void* stream) {
+  const char* fn = "vad_a2_windows_forward_group";
+  VAD_CHECK(plan != nullptr, std::string(fn) + ": null plan");
+  A2PlanImpl& c = plan->impl;
+  VAD_TRY(win_group_check(fn, ring, total_slots, cap, host_windows, nw, dev_table, c.B, c.T));
+  VAD_CHECK(c.params != nullptr, std::string(fn) + ": plan not bound");
+  VAD_TRY(c.check_windows());
+  hipStream_t st = (hipStream_t)stream;
+  // A single window runs as two copies of itself, as in vad_a2_windows_forward: its row goes to the device twice (a
+  // pageable source: the copy has left it when hipMemcpyAsync returns), which is why the table holds two rows at least.
+  const int64_t twice[4] = {host_windows[0], host_windows[1], host_windows[0], host_windows[1]};
+  const int rows = nw == 1 ? 2 : nw;
+  WinSrc ws;
+  VAD_TRY(win_group_src(fn, ring, 3ll * c.H * c.W, total_slots, cap, nw == 1 ? twice : host_windows, rows, dev_table, st,
+                        ws));
+  VAD_TRY(c.forward_windows(ws, rows, st));
   A2Copies cp{};
   int k = 0;
   auto add = [&](float* d, const float* s, int n) {

@@ -11,6 +11,7 @@
 #include "../../include/vad.h"
 #include "backbone.h"
 #include "conv3d.h"
+#include "group_table.h"
 #include "plan_util.h"
 
 namespace vad {
@@ -187,12 +188,18 @@ struct BbPlanImpl {
   }
 
   // x -> feature rows f (B, 1024); x: the B clips, or with win (x null) the windows of a video or ring that ws names
+  // a ring, or the rings of a group, as the window source: refused on the im2col path
+  int check_ring() const {
+    VAD_CHECK(!g_bbox_im2col, "vad_bbox_ring_forward: a ring needs the fused first layer (knob bbox_im2col = 0): "
+                              "the im2col path reads windows as a strided view, which a ring is not");
+    return 0;
+  }
+
   int encoder(const float* x, float* f, hipStream_t st, bool win = false, const WinSrc& ws = WinSrc{}) {
     DenseAct relu;
     relu.relu = 1;
     if (g_bbox_im2col) {  // (knob "bbox_im2col": the round-2 path -- im2col columns + f32 MFMA GEMMs)
-      VAD_CHECK(!win || ws.ring == 0, "vad_bbox_ring_forward: a ring needs the fused first layer (knob bbox_im2col = 0): "
-                                      "the im2col path reads windows as a strided view, which a ring is not");
+      if (win && (ws.ring != 0 || ws.table)) VAD_TRY(check_ring());
       const int64_t hw = (int64_t)H * W;  // (a window is a strided view of the video: clip b, channel c, depth d)
       const Strides5 sx = win ? Strides5{ws.stride * 3 * hw, hw, 3 * hw, W, 1} : ncdhw_strides(g1.in);
       VAD_TRY(im2col3d(win ? ws.frames + ws.first * 3 * hw : x, sx, g1, nullptr, nullptr, 0, cols1, st));
@@ -316,6 +323,23 @@ int vad_bbox_ring_forward(vad_bbox_plan* plan, const float* frames, int64_t n_fr
   VAD_CHECK(plan->impl.params != nullptr, "vad_bbox_ring_forward: plan not bound");
   const WinSrc ws{frames, 3ll * plan->impl.H * plan->impl.W, first, stride, ring};
   return plan->impl.forward_windows(ws, scores, adj, features, (hipStream_t)stream);
+}
+
+int vad_bbox_windows_forward_group(vad_bbox_plan* plan, const float* ring, int64_t total_slots, int cap,
+                                   const int64_t* host_windows, int nw, void* dev_table, float* scores, float* adj,
+                                   float* features, void* stream) {
+  const char* fn = "vad_bbox_windows_forward_group";
+  VAD_CHECK(plan && scores && adj, std::string(fn) + ": null plan, scores or adj");
+  BbPlanImpl& c = plan->impl;
+  VAD_TRY(win_group_check(fn, ring, total_slots, cap, host_windows, nw, dev_table, c.B, c.T));
+  VAD_CHECK(nw == c.B, std::string(fn) + ": the whole plan runs: nw must be its " + std::to_string(c.B) +
+                           " windows, got " + std::to_string(nw));
+  VAD_CHECK(c.params != nullptr, std::string(fn) + ": plan not bound");
+  VAD_TRY(c.check_ring());
+  WinSrc ws;
+  VAD_TRY(win_group_src(fn, ring, 3ll * c.H * c.W, total_slots, cap, host_windows, nw, dev_table, (hipStream_t)stream,
+                        ws));
+  return c.forward_windows(ws, scores, adj, features, (hipStream_t)stream);
 }
 
 int vad_bbox_head_forward(vad_bbox_plan* plan, const float* features, float* scores, float* adj, void* stream) {

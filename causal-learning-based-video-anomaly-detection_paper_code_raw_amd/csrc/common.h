@@ -197,10 +197,28 @@ __device__ inline f32x16 mfma32(float a, float b, f32x16 c) {
 // first + b * stride + t, taken modulo ring when ring > 0 (a ring of that many slots).  Times t < 0 and t >= T are the
 // window's zero padding and are never looked up.  A loader resolves frame(b, t) once per staged halo plane -- the
 // 64-bit modulo stays out of its element and tap loops -- and indexes the plane with 64-bit pointer arithmetic.
+// The group form (table != null, and first, stride and ring are not read): frames is one allocation of
+// many rings of cap slots each, and table holds two int64 per window, (base, first) -- window b, time t is slot
+// base_b + (first_b + t) mod cap, where 0 <= first_b < cap and t < T <= cap make the modulo one wrap.  The rows are
+// validated on the host before the launch (group_table.h win_group_src); b is block-uniform in every loader, so the
+// two table words are one uniform load per plane.
 struct WinSrc {
   const float* frames;
   int64_t frame_floats, first, stride, ring;
+  const int64_t* table = nullptr;
+  int64_t cap = 0;
   __host__ __device__ int64_t slot(int64_t b, int t) const {
+    if (table) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      // (read through the constant address space: nothing writes the table while a kernel reads it, and a uniform
+      // load from there takes the scalar path even inside a persistent loop that stores between two reads)
+      const auto* row = (const __attribute__((address_space(4))) int64_t*)table + 2 * b;
+#else
+      const int64_t* row = table + 2 * b;
+#endif
+      const int64_t s = row[1] + t;
+      return row[0] + (s >= cap ? s - cap : s);
+    }
     const int64_t f = first + b * stride + t;
     return ring > 0 ? f % ring : f;
   }

@@ -59,4 +59,33 @@ static inline int check_and_copy_window_rows(const char* fn, const int64_t* host
   return 0;
 }
 
+// The clip models' group windows calls (vad_a2 / vad_mc / vad_bbox _windows_forward_group): their device
+// table has no destination part -- nw rows of (base, first) from byte 0.  win_group_check: the argument checks the
+// three share, apart from the rows; the entry point then makes its plan's own checks and calls win_group_src, which
+// validates the rows, queues their one copy and gives the window source the first conv reads (common.h WinSrc, group
+// form).  frames holds total_slots frames of frame_floats floats: total_slots / cap rings of cap slots; nw windows of
+// T frames on a plan of B clips.
+static inline int win_group_check(const char* fn, const float* frames, int64_t total_slots, int cap,
+                                  const int64_t* host_windows, int nw, void* dev_table, int64_t B, int64_t T) {
+  const std::string name(fn);
+  VAD_CHECK(frames != nullptr, name + ": null ring");
+  VAD_CHECK(host_windows && dev_table, name + ": null table (host_windows or dev_table)");
+  VAD_CHECK((reinterpret_cast<uintptr_t>(dev_table) & 15) == 0, name + ": dev_table must be 16-B aligned");
+  VAD_CHECK(cap >= 1 && total_slots >= cap && total_slots % cap == 0,
+            name + ": cap must be in 1..total_slots and divide it, got cap " + std::to_string(cap) + ", total_slots " +
+                std::to_string(total_slots));
+  VAD_CHECK(cap >= T, name + ": a ring of cap = " + std::to_string(cap) + " slots holds no window of " +
+                          std::to_string(T) + " frames");
+  VAD_CHECK(nw >= 1 && nw <= B, name + ": between 1 and the plan's " + std::to_string(B) + " windows per call, got " +
+                                    std::to_string(nw));
+  return 0;
+}
+
+static inline int win_group_src(const char* fn, const float* frames, int64_t frame_floats, int64_t total_slots, int cap,
+                                const int64_t* host_windows, int nw, void* dev_table, hipStream_t stream, WinSrc& ws) {
+  VAD_TRY(check_and_copy_window_rows(fn, host_windows, 2, nw, cap, total_slots, dev_table, 0, stream));
+  ws = WinSrc{frames, frame_floats, 0, 0, 0, static_cast<const int64_t*>(dev_table), cap};
+  return 0;
+}
+
 }  // namespace vad

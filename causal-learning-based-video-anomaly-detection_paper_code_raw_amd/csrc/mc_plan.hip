@@ -18,6 +18,7 @@
 #include "../../include/vad.h"
 #include "backbone.h"
 #include "conv3d.h"
+#include "group_table.h"
 #include "optim.h"
 #include "plan_util.h"
 
@@ -356,10 +357,15 @@ struct McPlanImpl {
   // the plan's loss and status words and its per-call state are left alone (the classifier's three loss words go to
   // the BatchNorm partials scratch, which nothing reads in eval mode); the activations are overwritten, so a backward
   // is refused until the next clip forward (win_dirty).
-  int forward_windows(const WinSrc& src, int nw, float* scores, hipStream_t st) {
+  int check_windows() const {
     VAD_CHECK(direct(0) && direct(1) && direct(2),
               "vad_mc_windows_forward: windows are read by the direct 3-D convs only (knob conv3d_direct = 1 and at most "
               "16 input channels); the im2col path has no windows form");
+    return 0;
+  }
+
+  int forward_windows(const WinSrc& src, int nw, float* scores, hipStream_t st) {
+    VAD_TRY(check_windows());
     win_dirty = true;
     for (int s = 0; s < 3; ++s) {
       const int Co = MC_CO[s];
@@ -538,6 +544,20 @@ int vad_mc_windows_forward(vad_mc_plan* plan, const float* frames, int64_t n_fra
   VAD_TRY(win_check("vad_mc_windows_forward", n_frames, first, stride, ring, nw, c.B, c.T));
   VAD_CHECK(c.params != nullptr, "vad_mc_windows_forward: plan not bound");
   const WinSrc ws{frames, (int64_t)c.C * c.H * c.W, first, stride, ring};
+  return c.forward_windows(ws, nw, scores, (hipStream_t)stream);
+}
+
+int vad_mc_windows_forward_group(vad_mc_plan* plan, const float* ring, int64_t total_slots, int cap,
+                                 const int64_t* host_windows, int nw, void* dev_table, float* scores, void* stream) {
+  const char* fn = "vad_mc_windows_forward_group";
+  VAD_CHECK(plan && scores, std::string(fn) + ": null plan or scores");
+  McPlanImpl& c = plan->impl;
+  VAD_TRY(win_group_check(fn, ring, total_slots, cap, host_windows, nw, dev_table, c.B, c.T));
+  VAD_CHECK(c.params != nullptr, std::string(fn) + ": plan not bound");
+  VAD_TRY(c.check_windows());
+  WinSrc ws;
+  VAD_TRY(win_group_src(fn, ring, (int64_t)c.C * c.H * c.W, total_slots, cap, host_windows, nw, dev_table,
+                        (hipStream_t)stream, ws));
   return c.forward_windows(ws, nw, scores, (hipStream_t)stream);
 }
 

@@ -108,6 +108,13 @@ class SimpleVideoAnomalyDetector(nn.Module):
         window = self.temporal_frames if window is None else window
         return ClipStream(self, "mc", window, stride, max_push=max_push, frame_size=frame_size)
 
+    def open_stream_group(self, num_streams, window=None, stride=1, *, max_push=1, frame_size=None):
+        """A clip_stream_group.ClipStreamGroup on this model: num_streams cameras of one frame size, one windows call
+        per push for the windows of all of them; window defaults to temporal_frames."""
+        from .clip_stream_group import ClipStreamGroup
+        window = self.temporal_frames if window is None else window
+        return ClipStreamGroup(self, "mc", num_streams, window, stride, max_push=max_push, frame_size=frame_size)
+
 
 class _McFunction(torch.autograd.Function):
     @staticmethod
@@ -166,6 +173,15 @@ class McEngine(FlatEngine):
         p = self.plan(B, C, T, H, W, "windows")
         nat.check(nat.lib().vad_mc_windows_forward(p.h, nat.ptr(frames), n, first, stride, ring, nw, nat.ptr(out[0]),
                                                    self.stream()))
+
+    def windows_forward_group(self, ring, cap, h_win, nw, dev_table, T, B, out):
+        """nw <= B windows of a group's rings (total_slots, C, H, W), cap slots each, through the host rows h_win
+        (nw, 2) int64 and the caller's device table (vad_mc_windows_forward_group), into out[0]; on windows_forward's
+        scoring plan."""
+        n, C, H, W = ring.shape
+        p = self.plan(B, C, T, H, W, "windows")
+        nat.check(nat.lib().vad_mc_windows_forward_group(p.h, nat.ptr(ring), n, cap, h_win.data_ptr(), nw,
+                                                         nat.ptr(dev_table), nat.ptr(out[0]), self.stream()))
 
     def backward(self):
         """Backward of the BCE loss of the last forward (StableTrainer path)."""

@@ -368,6 +368,23 @@ int vad_mc_forward(vad_mc_plan* plan, const float* x, int training, uint64_t see
  * form. */
 int vad_mc_windows_forward(vad_mc_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
                            int64_t ring, int nw, float* scores, void* stream);
+/* Windows of a group of streams, for the three clip models alike (vad_mc / vad_a2 / vad_bbox
+ * _windows_forward_group): ring is one allocation of total_slots frames of C * H * W floats holding total_slots / cap
+ * rings of cap slots, ring s in slots s*cap .. (s+1)*cap - 1.  host_windows, a HOST pointer, holds two int64 per
+ * window, (base, first): the window's frame t is slot base + (first + t) mod cap, read in place by the first conv, and
+ * row i of every output is window i.  The call validates its arguments and the table row by row on the host -- a
+ * violation returns non-zero, names the entry point and the numbers in vad_last_error and queues nothing, so a bad
+ * table cannot cause a load outside the allocation -- and then copies the rows with one hipMemcpyAsync on `stream`
+ * into dev_table, which the first conv reads.  Required: non-null pointers, dev_table 16-byte aligned, cap in
+ * 1..total_slots and dividing it, cap >= the plan's T, 1 <= nw <= the plan's B, every base a non-negative multiple of
+ * cap with base + cap <= total_slots, 0 <= first < cap; a bound plan and the conv path of the model's windows call.
+ * dev_table is caller-owned device memory of at least vad_win_group_table_bytes(nw) bytes (the rows from byte 0, two
+ * rows at least; -1 on a bad argument); the caller must not reuse it while an earlier call on ANOTHER stream may still
+ * read it.  A pageable host table may be changed as soon as the call returns; a pinned one only once `stream` has
+ * passed the copy.  Semantics, outputs and plan state are those of the model's windows call. */
+int64_t vad_win_group_table_bytes(int64_t nw);
+int vad_mc_windows_forward_group(vad_mc_plan* plan, const float* ring, int64_t total_slots, int cap,
+                                 const int64_t* host_windows, int nw, void* dev_table, float* scores, void* stream);
 /* d_scores (B,) nullable: NULL = backward of the forward's BCE (requires labels) */
 int vad_mc_backward(vad_mc_plan* plan, const float* d_scores, void* stream);
 /* grad norm (float64 sum of per-param norm^2); clip_grad_norm_(max_norm) only when norm > clip_above; Adam */
@@ -425,6 +442,11 @@ int vad_a2_set_option(vad_a2_plan* plan, const char* key, int64_t value);
  * knob a2_direct = 0. */
 int vad_a2_windows_forward(vad_a2_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
                            int64_t ring, int nw, float* scores, float* adj, float* features, void* stream);
+/* vad_a2_windows_forward for the windows of a group of streams (vad_mc_windows_forward_group: the arguments, the
+ * table and the refusals).  nw = 1 runs row 0 twice and returns the first, as vad_a2_windows_forward. */
+int vad_a2_windows_forward_group(vad_a2_plan* plan, const float* ring, int64_t total_slots, int cap,
+                                 const int64_t* host_windows, int nw, void* dev_table, float* scores, float* adj,
+                                 float* features, void* stream);
 /* compute_improved_loss alone, on the last forward's scores / adjacency (pseudo-labels keyed by seed/step/clip0);
  * vad_a2_loss_grads copies d total / d scores (B,) and d total / d adj (B,16,16) of that loss */
 int vad_a2_loss(vad_a2_plan* plan, uint64_t seed, uint64_t step, int64_t clip0, float* losses, void* stream);
@@ -483,6 +505,11 @@ int vad_bbox_windows_forward(vad_bbox_plan* plan, const float* frames, int64_t n
  * vad_bbox_windows_forward. */
 int vad_bbox_ring_forward(vad_bbox_plan* plan, const float* frames, int64_t n_frames, int64_t first, int64_t stride,
                           int64_t ring, float* scores, float* adj, float* features, void* stream);
+/* vad_bbox_ring_forward for the windows of a group of streams (vad_mc_windows_forward_group: the arguments, the table
+ * and the refusals).  The whole plan runs, so nw must be the plan's B; knob bbox_im2col = 1 is refused as for a ring. */
+int vad_bbox_windows_forward_group(vad_bbox_plan* plan, const float* ring, int64_t total_slots, int cap,
+                                   const int64_t* host_windows, int nw, void* dev_table, float* scores, float* adj,
+                                   float* features, void* stream);
 /* Test seams.  vad_bbox_forward is encoder (x -> features) then head (features -> scores, adj);
  * vad_bbox_head_forward runs the head alone -- the causal_net and classifier GEMMs and the sigmoid tail -- on feature
  * rows (B, 1024) the caller chose.  vad_bbox_debug_buffer hands out the workspace arrays of the last forward:
