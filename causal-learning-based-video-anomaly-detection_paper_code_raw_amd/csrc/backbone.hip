@@ -277,7 +277,7 @@ template <typename PT>
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const PT* __restrict__ partials, int P, int C,
                                                           double count, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float* running_mean,
-                                                          float* running_var, float momentum, float eps,
+                                                          float* running_var, float momentum, double eps,
                                                           int training, float* __restrict__ stats, int cm) {
   const int c = blockIdx.x;
   double a = 0.0, b = 0.0;
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const PT* __restrict__
       mean = running_mean[c];
       var = running_var[c];
     }
-    const double invstd = 1.0 / sqrt(var + (double)eps);
+    const double invstd = 1.0 / sqrt(var + eps);
     const double scale = (double)gamma[c] * invstd;
     stats[c] = (float)mean;
     stats[C + c] = (float)invstd;
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const PT* __restrict__
 }
 
 int bn_finalize(const float* partials, int P, int C, double count, const float* gamma, const float* beta,
-                float* running_mean, float* running_var, float momentum, float eps, int training, float* stats,
+                float* running_mean, float* running_var, float momentum, double eps, int training, float* stats,
                 hipStream_t st, int cm) {
   hipLaunchKernelGGL(bn_finalize_kernel<float>, dim3(C), dim3(256), 0, st, partials, P, C, count, gamma, beta,
                      running_mean, running_var, momentum, eps, training, stats, cm);
@@ -322,7 +322,7 @@ int bn_finalize(const float* partials, int P, int C, double count, const float* 
 }
 
 int bn_finalize_sums(const double* sums, int C, double count, const float* gamma, const float* beta,
-                     float* running_mean, float* running_var, float momentum, float eps, float* stats,
+                     float* running_mean, float* running_var, float momentum, double eps, float* stats,
                      hipStream_t st) {
   hipLaunchKernelGGL(bn_finalize_kernel<double>, dim3(C), dim3(256), 0, st, sums, 1, C, count, gamma, beta,
                      running_mean, running_var, momentum, eps, 1, stats, 0);

@@ -741,13 +741,13 @@ struct CadPlanImpl {
   int bn_fwd_stats(int i, int np, int C, double count, const float* gamma, const float* beta, hipStream_t st,
                    int cm = 0, const float* pparts = nullptr) {
     if (sync_fn == nullptr || !training) {
-      TIMED("bn_fin", bn_finalize(pparts ? pparts : parts, np, C, count, gamma, beta, RM(i), RV(i), 0.1f, 1e-5f, training, stats[i],
+      TIMED("bn_fin", bn_finalize(pparts ? pparts : parts, np, C, count, gamma, beta, RM(i), RV(i), 0.1f, 1e-5, training, stats[i],
                                   st, cm));
       return 0;
     }
     TIMED("bn_fin", bn_sum_partials(parts, np, C, bnsync, nullptr, nullptr, st, cm));
     VAD_CHECK(sync_fn(sync_user, i, 0, 2 * C, st) == 0, "BatchNorm sync callback failed (forward)");
-    TIMED("bn_fin", bn_finalize_sums(bnsync, C, count * sync_world, gamma, beta, RM(i), RV(i), 0.1f, 1e-5f, stats[i],
+    TIMED("bn_fin", bn_finalize_sums(bnsync, C, count * sync_world, gamma, beta, RM(i), RV(i), 0.1f, 1e-5, stats[i],
                                      st));
     return 0;
   }

@@ -50,6 +50,55 @@ def make_cad_model(case):
     return m
 
 
+EPS_REGIME_VAR = 1e-7  # running_var of the two channels per layer whose invstd is decided by eps = 1e-5
+CALIBRATION_FRAMES = 8
+
+
+def calibrated_bn_state(sd, case, seed):
+    """A copy of the cad state dict sd with the nine backbone BatchNorm layers in a trained-like state, on the CPU and
+    deterministic from seed (one torch.Generator, drawn layer by layer in oracle.cad_oracle.BN_LAYERS order: sign,
+    gamma, beta, mean noise, variance factor, eps-regime channels).  case: its "H", "W" size the calibration clip.
+      * gamma = s * U[0.5, 1.5], s = -1 on about a quarter of the channels (bn1 too: the frozen stem's min arm);
+        beta ~ N(0, 0.3);
+      * running_mean / running_var: the per-channel batch mean and unbiased variance of each layer's pre-BN map in one
+        float64 train-mode oracle forward of CALIBRATION_FRAMES synthetic frames of the case's size under the gamma and
+        beta above (every layer sees a network normalised below it), the mean times 1 + 0.1 n, n ~ N(0, 1), the
+        variance times U[0.5, 2];
+      * two channels per layer in the eps regime: running_var = EPS_REGIME_VAR, and gamma scaled by
+        sqrt((EPS_REGIME_VAR + eps) / (var + eps)) so that the channel's output is what it was with var;
+      * num_batches_tracked = 1000 + the layer's index.
+    Everything else (detector, heads: force_detector is applied before, as make_cad_model does) is untouched."""
+    from oracle import cad_oracle as co
+    g = torch.Generator().manual_seed(seed)
+    out = {k: v.detach().clone() for k, v in sd.items()}
+    draws = []
+    for bn, C in zip(co.BN_LAYERS, co.BN_CHANNELS):
+        sign = torch.where(torch.rand(C, generator=g) < 0.25, -1.0, 1.0)
+        out[bn + ".weight"] = sign * (0.5 + torch.rand(C, generator=g))
+        out[bn + ".bias"] = 0.3 * torch.randn(C, generator=g)
+        draws.append((torch.randn(C, generator=g, dtype=torch.float64),
+                      0.5 + 1.5 * torch.rand(C, generator=g, dtype=torch.float64),
+                      torch.randperm(C, generator=g)[:2]))
+    p = {k: v.double() for k, v in out.items() if "running" not in k and "num_batches" not in k}
+    bufs = {k: v.double().clone() for k, v in out.items() if "running" in k}
+    x = co.synth_clips(seed, 0, 0, 1, CALIBRATION_FRAMES, case["H"], case["W"]).double()
+    rec = {}
+    with torch.no_grad():
+        co.backbone_forward(p, bufs, x, training=True, record=rec)
+    for i, (bn, (n, u, epsc)) in enumerate(zip(co.BN_LAYERS, draws)):
+        y = rec["y_stem"] if i == 0 else rec[f"y{i - 1}"].detach()
+        mean = y.mean((0, 2, 3)) * (1 + 0.1 * n)
+        var = y.var((0, 2, 3), unbiased=True) * u
+        gamma = out[bn + ".weight"].double()
+        gamma[epsc] *= torch.sqrt((EPS_REGIME_VAR + 1e-5) / (var[epsc] + 1e-5))
+        var[epsc] = EPS_REGIME_VAR
+        out[bn + ".weight"] = gamma.float()
+        out[bn + ".running_mean"] = mean.float()
+        out[bn + ".running_var"] = var.float()
+        out[bn + ".num_batches_tracked"] = torch.tensor(1000 + i, dtype=torch.int64)
+    return out
+
+
 def ae_memory_init(case):
     """(normal_memory (500, 64), memory_ptr) of a cad1 AE case before training."""
     mem = torch.zeros(500, 64)

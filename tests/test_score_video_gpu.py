@@ -29,7 +29,10 @@ def _oracle_windows(case, frames, T, stride, seed, step, clip0):
         return co.cad_forward(params, bufs, X, co.CadDraws.make(seed, step, clip0, Wn, T), training=False)
 
 
-def _check_against_oracle(out, ref, N, T, stride):
+def _check_against_oracle(out, ref, N, T, stride, tol=None):
+    """tol: {output key: dict(rtol=, atol=)} replacing TOL for that key ("detections", "causal_factors" and the five
+    stacked outputs); the keys it leaves out keep TOL."""
+    tol = tol or {}
     Wn = (N - T) // stride + 1
     assert out["window_starts"].tolist() == [w * stride for w in range(Wn)]
     # counts first: a wrong count makes every later comparison meaningless
@@ -41,18 +44,22 @@ def _check_against_oracle(out, ref, N, T, stride):
     for f, d in ref_det.items():
         got = out["detections"][f].cpu().numpy()
         assert got.shape == tuple(d.shape), f"frame {f}: {got.shape[0]} boxes, oracle {d.shape[0]}"
-        np.testing.assert_allclose(got, d.numpy(), err_msg=f"boxes of frame {f}", **TOL)
+        np.testing.assert_allclose(got, d.numpy(), err_msg=f"boxes of frame {f}", **tol.get("detections", TOL))
     ref_nmax = [z.shape[0] for z in ref["causal_factors"]]
     assert [z.shape[0] for z in out["causal_factors"]] == ref_nmax
-    np.testing.assert_allclose(out["anomaly_scores"].cpu().numpy(), ref["anomaly_scores"].numpy(), **TOL)
-    np.testing.assert_allclose(out["direct_predictions"].cpu().numpy(), ref["direct_predictions"].numpy(), **TOL)
-    np.testing.assert_allclose(out["causal_anomaly_scores"].cpu().numpy(), ref["causal_anomaly_scores"].numpy(), **TOL)
-    np.testing.assert_allclose(out["kl_losses"].cpu().numpy(), torch.stack(ref["kl_losses"]).numpy(), **TOL)
+    np.testing.assert_allclose(out["anomaly_scores"].cpu().numpy(), ref["anomaly_scores"].numpy(),
+                               **tol.get("anomaly_scores", TOL))
+    np.testing.assert_allclose(out["direct_predictions"].cpu().numpy(), ref["direct_predictions"].numpy(),
+                               **tol.get("direct_predictions", TOL))
+    np.testing.assert_allclose(out["causal_anomaly_scores"].cpu().numpy(), ref["causal_anomaly_scores"].numpy(),
+                               **tol.get("causal_anomaly_scores", TOL))
+    np.testing.assert_allclose(out["kl_losses"].cpu().numpy(), torch.stack(ref["kl_losses"]).numpy(),
+                               **tol.get("kl_losses", TOL))
     np.testing.assert_allclose(out["adjacency_matrices"].cpu().numpy(), torch.stack(ref["adjacency_matrices"]).numpy(),
-                               **TOL)
+                               **tol.get("adjacency_matrices", TOL))
     for w in range(Wn):
         np.testing.assert_allclose(out["causal_factors"][w].cpu().numpy(), ref["causal_factors"][w].numpy(),
-                                   err_msg=f"z of window {w}", **TOL)
+                                   err_msg=f"z of window {w}", **tol.get("causal_factors", TOL))
     return ref_nmax
 
 
