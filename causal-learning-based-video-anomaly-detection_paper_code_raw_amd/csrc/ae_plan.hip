@@ -81,9 +81,6 @@ struct AeRing {
       : lat(0), gx(cap * AE_LAT), pix(cap * (AE_LAT + AE_GATES)), total(cap * (AE_LAT + AE_GATES + AE_PIX)) {}
 };
 constexpr int64_t AE_RING_MAX = 1ll << 24;  // slots: slot arithmetic in the kernels stays in int
-// How the per-window stage addresses its frames: rows of a frame cache, slots of one ring, or -- a group of streams --
-// slots of many rings of cap slots in one AeRing(total_slots), through a window table
-enum class AeWindows { Linear, Ring, Group };
 
 // model.named_parameters() and BN running-stat order (cad1:129-188)
 struct AeLayout : FlatLayout {
@@ -174,25 +171,18 @@ __global__ __launch_bounds__(256) void ae_frames_kernel(const float* __restrict_
 }
 
 // Ring store of a (B = k, T = 1) plan's per-frame results: block f copies row f of lat [k][64], gx [k][256] and xf
-// [k][4096] to slot s0 + f of the ring's arrays, less cap once if it passes the end (s0 = f0 mod cap, reduced on the
-// host; k <= cap), so a chunk may straddle the wrap.  float4 copies, no division.  TABLE (a group of streams: the three
-// arrays hold many rings): block f stores to the absolute slot table[f], or, where that is < 0 (a padding frame),
-// returns before any load; table[f] is block-uniform, so it is one scalar load.  The host validated the table
-// (below): the kernel checks nothing.
-template <bool TABLE = false>
+// [k][4096] to slot frame_slot<F>(f) of the ring's arrays (win_rows.h: Ring, where a chunk may straddle the wrap, or
+// Group, where a padding frame returns before any load).  float4 copies, no division.
+template <WinForm F>
 __global__ __launch_bounds__(256) void ae_ring_store_kernel(const float* __restrict__ lat,
                                                             const float* __restrict__ gx,
                                                             const float* __restrict__ xf, int s0, int cap,
                                                             float* __restrict__ rlat, float* __restrict__ rgx,
                                                             float* __restrict__ rpix, const int* __restrict__ table) {
+  static_assert(F != WinForm::Linear, "the linear cache is written by the encoder itself");
   const int f = blockIdx.x, t = threadIdx.x;
-  int slot = s0 + f;
-  if constexpr (TABLE) {
-    slot = table[f];
-    if (slot < 0) return;
-  } else {
-    if (slot >= cap) slot -= cap;
-  }
+  const int slot = frame_slot<F>(f, s0, cap, table);
+  if (F == WinForm::Group && slot < 0) return;
   if (t < AE_LAT / 4)
     reinterpret_cast<f32x4*>(rlat + (int64_t)slot * AE_LAT)[t] =
         reinterpret_cast<const f32x4*>(lat + (int64_t)f * AE_LAT)[t];
@@ -584,28 +574,19 @@ __global__ __launch_bounds__(256) void ae_add_kernel(float* __restrict__ a, cons
 // ------------------------------------------------------------------ LSTM(64, 64) (cad1:182-188, 236-240)
 // One block per clip: thread j owns gate row j of W_hh (64 registers), h is broadcast from LDS.  torch gate order
 // i, f, g, o; gx = x W_ih^T + b_ih for all frames (one GEMM).  The clip form (WIN = false) reads row t*B + b of the
-// plan's gx and keeps post-activation gates, c_t and h_{t-1} for BPTT.  The windowed form (WIN = true, eval scoring of
-// a video) reads the frame cache's gx row first + b*stride + t -- one coalesced 1 KB load per step, whose address
-// does not depend on h, so the rows of the next AE_PF steps are fetched into registers ahead of the dependent chain --
-// and stores nothing but the sequence feature.  The ring form (WIN and RING, a live stream) reads the gx array of a
-// ring of cap slots: the block reduces its first slot s0 = (first + b*stride) mod cap once (first: already mod cap),
-// and the row of step t -- the look-ahead row t + AE_PF of the prefetch too -- is s0 + t, less cap where it reaches
-// it (T <= cap: one block-uniform conditional subtract, no division in the recurrence).  The group form (GROUP, with
-// RING: many rings of cap slots in one gx array) reads its block's entry (base_b, s0_b) of the window table once,
-// before the recurrence -- its address depends on blockIdx alone, so both are scalar loads and stay in scalar
-// registers -- offsets gx by base_b rows and then is the ring form on a ring that starts there.  All forms run the
-// same floating-point instructions per step.
+// plan's gx and keeps post-activation gates, c_t and h_{t-1} for BPTT.  The windowed form (WIN = true, eval scoring)
+// reads the gx rows of window b of win (win_rows.h; the window is resolved once, before the recurrence) -- one
+// coalesced 1 KB load per step, whose address does not depend on h, so the rows of the next AE_PF steps (look-ahead
+// row t + AE_PF) are fetched into registers ahead of the dependent chain -- and stores nothing but the sequence
+// feature.  All forms run the same floating-point instructions per step.
 constexpr int AE_PF = 4;
 
-template <bool WIN, bool RING = false, bool GROUP = false>
+template <bool WIN, WinForm F = WinForm::Linear>
 __device__ __forceinline__ void ae_lstm_fwd_body(const float* __restrict__ gx, const float* __restrict__ whh,
-                                                 const float* __restrict__ bhh, int B, int T, int stride,
-                                                 int64_t first, int cap, float* __restrict__ gates,
-                                                 float* __restrict__ cs, float* __restrict__ hprev,
-                                                 float* __restrict__ seq, float* __restrict__ seq_out,
-                                                 const int64_t* __restrict__ tab = nullptr) {
-  static_assert(WIN || !RING, "the ring form is a windowed form");
-  static_assert(RING || !GROUP, "the group form addresses rings");
+                                                 const float* __restrict__ bhh, int B, int T, const WinRows& win,
+                                                 float* __restrict__ gates, float* __restrict__ cs,
+                                                 float* __restrict__ hprev, float* __restrict__ seq,
+                                                 float* __restrict__ seq_out) {
   __shared__ float h[AE_LAT], act[AE_GATES];
   const int b = blockIdx.x, j = threadIdx.x;
   float w[AE_LAT];
@@ -642,28 +623,9 @@ __device__ __forceinline__ void ae_lstm_fwd_body(const float* __restrict__ gx, c
     __syncthreads();
   };
   if constexpr (WIN) {
-    // the input projection of step t: frame (w0 + b) * stride + t of the cache, or its slot of the ring
-    const float* row;
-    int s0 = 0;
-    if constexpr (GROUP) {
-      const int64_t* e = tab + 2 * (int64_t)b;
-      row = gx + e[0] * AE_GATES + j;
-      s0 = (int)e[1];
-    } else if constexpr (RING) {
-      row = gx + j;
-      s0 = (int)(((unsigned)first + (unsigned)b * (unsigned)stride) % (unsigned)cap);
-    } else {
-      row = gx + (first + (int64_t)b * stride) * AE_GATES + j;
-    }
-    auto gx_at = [&](int t) -> float {
-      if constexpr (RING) {
-        int r = s0 + t;
-        if (r >= cap) r -= cap;  // (block-uniform)
-        return row[(int64_t)r * AE_GATES];
-      } else {
-        return row[(int64_t)t * AE_GATES];
-      }
-    };
+    const WinCursor<F> cur(win, b);
+    const float* row = gx + cur.base * AE_GATES + j;
+    auto gx_at = [&](int t) -> float { return row[(int64_t)cur.row(t) * AE_GATES]; };
     float pf[AE_PF];
 #pragma unroll
     for (int i = 0; i < AE_PF; ++i) pf[i] = i < T ? gx_at(i) : 0.f;
@@ -696,33 +658,16 @@ __global__ __launch_bounds__(256) void ae_lstm_fwd_kernel(const float* __restric
                                                           float* __restrict__ gates, float* __restrict__ cs,
                                                           float* __restrict__ hprev, float* __restrict__ seq,
                                                           float* __restrict__ seq_out) {
-  ae_lstm_fwd_body<false>(gx, whh, bhh, B, T, 0, 0, 0, gates, cs, hprev, seq, seq_out);
+  ae_lstm_fwd_body<false>(gx, whh, bhh, B, T, WinRows{}, gates, cs, hprev, seq, seq_out);
 }
 
-// window i of the launch = frames first + i*stride .. + T - 1 of the cache's gx; seq_out [gridDim.x][64]
+// window i of the launch = window i of win in gx (the frame cache's, the ring's or the rings' gx array); seq_out
+// [gridDim.x][64]
+template <WinForm F>
 __global__ __launch_bounds__(256) void ae_lstm_win_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
-                                                          const float* __restrict__ bhh, int T, int stride,
-                                                          int64_t first, float* __restrict__ seq_out) {
-  ae_lstm_fwd_body<true>(gx, whh, bhh, 0, T, stride, first, 0, nullptr, nullptr, nullptr, nullptr, seq_out);
-}
-
-// window i of the launch = frames first + i*stride .. + T - 1 of a ring of cap slots (gx: the ring's gx array; first
-// already reduced mod cap on the host; T <= cap)
-__global__ __launch_bounds__(256) void ae_lstm_ring_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
-                                                           const float* __restrict__ bhh, int T, int stride,
-                                                           int first, int cap, float* __restrict__ seq_out) {
-  ae_lstm_fwd_body<true, true>(gx, whh, bhh, 0, T, stride, first, cap, nullptr, nullptr, nullptr, nullptr, seq_out);
-}
-
-// window i of the launch = slots tab[2i] + (tab[2i + 1] + t, less cap where it reaches it), t < T, of an array of many
-// rings of cap slots (gx: that array; tab: the validated window table on the device; T <= cap)
-__global__ __launch_bounds__(256) void ae_lstm_group_kernel(const float* __restrict__ gx,
-                                                            const float* __restrict__ whh,
-                                                            const float* __restrict__ bhh, int T, int cap,
-                                                            const int64_t* __restrict__ tab,
-                                                            float* __restrict__ seq_out) {
-  ae_lstm_fwd_body<true, true, true>(gx, whh, bhh, 0, T, 1, 0, cap, nullptr, nullptr, nullptr, nullptr, seq_out,
-                                     tab);
+                                                          const float* __restrict__ bhh, int T, const WinRows win,
+                                                          float* __restrict__ seq_out) {
+  ae_lstm_fwd_body<true, F>(gx, whh, bhh, 0, T, win, nullptr, nullptr, nullptr, nullptr, seq_out);
 }
 
 // BPTT, one block per clip in reverse time: thread (q, k) holds column k of W_hh rows [64q, 64q + 64) for
@@ -831,49 +776,26 @@ __global__ __launch_bounds__(256) void ae_loss_finalize_kernel(const float* __re
   }
 }
 
-// The windowed form (eval scoring of a video): one block per (window i of the launch, 256-pixel chunk); the window's
-// one reconstruction r against its T frames first + i*stride + t of the caller's video, NaN -> 0 on both sides, in
+// The windowed form (eval scoring): one block per (window i of the launch, 256-pixel chunk); the window's one
+// reconstruction r against its T frames -- window i of win (win_rows.h) in frames -- NaN -> 0 on both sides, in
 // ae_loss_kernel's order (fmaf(d, d, sq) over t ascending, the same LDS tree).  recon (nullable) [windows][4096]: r
-// once per window.  RING (a live stream): frames is the ring's pix array of cap slots -- the plan's xf rows, NaN -> 0
-// already, so nan0 is the identity there and the sums are those of the linear form on the caller's frames -- first is
-// reduced mod cap on the host and the row of step t is s0 + t, less cap where it reaches it (T <= cap).  GROUP (with
-// RING: frames is the pix array of many rings of cap slots): the block reads its window's entry (base, s0) of the
-// window table once, ahead of the loop (block-uniform: scalar loads), offsets frames by base rows and then is the ring
-// form; the sum and the tree are the same.
-template <bool RING, bool GROUP = false>
+// once per window.  Linear: frames is the caller's video.  Ring, Group: frames is the pix array of the ring(s) -- the
+// plan's xf rows, NaN -> 0 already, so nan0 is the identity there and the sums are those of the linear form.
+template <WinForm F>
 __global__ __launch_bounds__(256) void ae_win_loss_kernel(const float* __restrict__ y3,
-                                                          const float* __restrict__ frames, int T, int stride,
-                                                          int64_t first, int cap, float* __restrict__ recon,
-                                                          float* __restrict__ part,
-                                                          const int64_t* __restrict__ tab) {
-  static_assert(RING || !GROUP, "the group form addresses rings");
+                                                          const float* __restrict__ frames, int T, const WinRows win,
+                                                          float* __restrict__ recon, float* __restrict__ part) {
   __shared__ float red[256];
   const int b = blockIdx.x / AE_CHUNKS, p = (blockIdx.x % AE_CHUNKS) * 256 + threadIdx.x;
   const float r0 = 1.f / (1.f + expf(-y3[(int64_t)b * AE_PIX + p]));
   const float r = r0 != r0 ? 0.f : r0;
-  const float* x;
-  int s0 = 0;
-  if constexpr (GROUP) {
-    const int64_t* e = tab + 2 * (int64_t)b;
-    x = frames + e[0] * AE_PIX + p;
-    s0 = (int)e[1];
-  } else if constexpr (RING) {
-    x = frames + p;
-    s0 = (int)(((unsigned)first + (unsigned)b * (unsigned)stride) % (unsigned)cap);
-  } else {
-    x = frames + (first + (int64_t)b * stride) * AE_PIX + p;
-  }
+  const WinCursor<F> cur(win, b);
+  const float* x = frames + cur.base * AE_PIX + p;
   float sq = 0.f;
   // (the loads of an unrolled group issue before its arithmetic; the adds stay in t order)
 #pragma unroll 4
   for (int t = 0; t < T; ++t) {
-    int64_t row = t;
-    if constexpr (RING) {
-      int q = s0 + t;
-      if (q >= cap) q -= cap;  // (block-uniform)
-      row = q;
-    }
-    const float d = r - nan0(x[row * AE_PIX]);
+    const float d = r - nan0(x[(int64_t)cur.row(t) * AE_PIX]);
     sq = fmaf(d, d, sq);
   }
   if (recon) recon[(int64_t)b * AE_PIX + p] = r;
@@ -1297,72 +1219,51 @@ struct AePlanImpl {
                   st);
   }
 
-  // The same on a live stream: the encoder writes the plan's own lat / gx rows, and those and the plan's NaN -> 0
-  // frames xf go to slots (f0 + f) mod cap of the ring
-  int frames_forward_ring(const float* frames_chunk, float* ring, int64_t cap, int64_t f0, hipStream_t st) {
-    const AeRing R(cap);
+  // The same on a live stream or a group of streams: the encoder writes the plan's own lat / gx rows, and those and the
+  // plan's NaN -> 0 frames xf go to the slots of AeRing(nslots) that frame_slot names (win_rows.h) -- Ring: slots
+  // (f0 + f) mod nslots; Group: slot dst[f], the validated destinations on the device, or nowhere
+  int frames_forward_ring(const float* frames_chunk, float* ring, int64_t nslots, WinForm form, int64_t f0,
+                          const int* dst, hipStream_t st) {
+    const AeRing R(nslots);
     training = 0;
     loss_mode = 0;
     have_fwd = 0;  // the encoder activations of an earlier forward are gone
     VAD_TRY(encode(frames_chunk, false, nullptr, lat, gx, nullptr, st));
-    hipLaunchKernelGGL(ae_ring_store_kernel<false>, dim3(NF), dim3(256), 0, st, lat, gx, xf, (int)(f0 % cap),
-                       (int)cap, ring + R.lat, ring + R.gx, ring + R.pix, (const int*)nullptr);
+    win_dispatch(form, [&](auto F) {
+      if constexpr (F() != WinForm::Linear)
+        hipLaunchKernelGGL(ae_ring_store_kernel<F()>, dim3(NF), dim3(256), 0, st, lat, gx, xf, (int)(f0 % nslots),
+                           (int)nslots, ring + R.lat, ring + R.gx, ring + R.pix, dst);
+    });
     VAD_LAUNCH_CHECK();
     return 0;
   }
 
-  // The same for a group of streams: ring is AeRing(total_slots) and frame f goes to slot dst[f] of it, or nowhere
-  // (dst: the validated destinations on the device)
-  int frames_forward_group(const float* frames_chunk, float* ring, int64_t total_slots, const int* dst,
-                           hipStream_t st) {
-    const AeRing R(total_slots);
-    training = 0;
-    loss_mode = 0;
-    have_fwd = 0;  // the encoder activations of an earlier forward are gone
-    VAD_TRY(encode(frames_chunk, false, nullptr, lat, gx, nullptr, st));
-    hipLaunchKernelGGL(ae_ring_store_kernel<true>, dim3(NF), dim3(256), 0, st, lat, gx, xf, 0, 0, ring + R.lat,
-                       ring + R.gx, ring + R.pix, dst);
-    VAD_LAUNCH_CHECK();
-    return 0;
-  }
-
-  // per-window stage for nw <= B windows, window i = frames first + i*stride + t: recurrence over the cached rows, ring
-  // score, one decoder call per window, its error against the window's T frames, the blend.  Ring: cache is a ring of
-  // nframes slots that holds the frames too (frames is not read).  Group: cache is AeRing(nframes) holding nframes /
-  // cap rings of cap slots, and window i is row i of tab (base, first slot; validated, on the device) -- stride and
-  // first are not read
-  int windows_forward(const float* cache, const float* frames, int64_t nframes, AeWindows mode, int T_, int stride,
-                      int64_t first, int nw, float* seq_out, float* recon_err, float* mem_score, float* score,
-                      float* recon, hipStream_t st, const int64_t* tab = nullptr, int cap = 0) {
+  // per-window stage for nw <= B windows, window i = window i of win (win_rows.h): recurrence over the cached rows,
+  // ring score, one decoder call per window, its error against the window's T frames, the blend.  Linear: cache is
+  // AeFrameCache(nframes) and the pixels are the caller's frames.  Ring, Group: cache is AeRing(nframes), which holds the
+  // frames too (frames is not read).
+  int windows_forward(const float* cache, const float* frames, int64_t nframes, WinForm form, const WinRows& win,
+                      int T_, int nw, float* seq_out, float* recon_err, float* mem_score, float* score, float* recon,
+                      hipStream_t st) {
     const AeLayout& L = ae_layout();
-    const int64_t* no_tab = nullptr;
+    const bool lin = form == WinForm::Linear;
+    const float* gx_rows = cache + (lin ? AeFrameCache(nframes).gx : AeRing(nframes).gx);
+    const float* pix_rows = lin ? frames : cache + AeRing(nframes).pix;
     training = 0;
     loss_mode = 0;
     have_fwd = 0;  // the decoder activations of an earlier forward are gone
-    if (mode == AeWindows::Group) {
-      hipLaunchKernelGGL(ae_lstm_group_kernel, dim3(nw), dim3(AE_GATES), 0, st, cache + AeRing(nframes).gx, P(L.whh),
-                         P(L.bhh), T_, cap, tab, seq_out);
-    } else if (mode == AeWindows::Ring) {
-      hipLaunchKernelGGL(ae_lstm_ring_kernel, dim3(nw), dim3(AE_GATES), 0, st, cache + AeRing(nframes).gx, P(L.whh),
-                         P(L.bhh), T_, stride, (int)(first % nframes), (int)nframes, seq_out);
-    } else {
-      hipLaunchKernelGGL(ae_lstm_win_kernel, dim3(nw), dim3(AE_GATES), 0, st, cache + AeFrameCache(nframes).gx,
-                         P(L.whh), P(L.bhh), T_, stride, first, seq_out);
-    }
+    win_dispatch(form, [&](auto F) {
+      hipLaunchKernelGGL(ae_lstm_win_kernel<F()>, dim3(nw), dim3(AE_GATES), 0, st, gx_rows, P(L.whh), P(L.bhh), T_, win,
+                         seq_out);
+    });
     VAD_LAUNCH_CHECK();
     hipLaunchKernelGGL(ae_memory_score_kernel, dim3(nw), dim3(256), 0, st, memory, mptr, seq_out, mem_score);
     VAD_LAUNCH_CHECK();
     VAD_TRY(decode(seq_out, nw, false, nullptr, st));
-    if (mode == AeWindows::Group) {
-      hipLaunchKernelGGL((ae_win_loss_kernel<true, true>), dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3],
-                         cache + AeRing(nframes).pix, T_, 1, (int64_t)0, cap, recon, lpart, tab);
-    } else if (mode == AeWindows::Ring) {
-      hipLaunchKernelGGL(ae_win_loss_kernel<true>, dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3],
-                         cache + AeRing(nframes).pix, T_, stride, first % nframes, (int)nframes, recon, lpart, no_tab);
-    } else {
-      hipLaunchKernelGGL(ae_win_loss_kernel<false>, dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3], frames, T_, stride,
-                         first, 0, recon, lpart, no_tab);
-    }
+    win_dispatch(form, [&](auto F) {
+      hipLaunchKernelGGL(ae_win_loss_kernel<F()>, dim3(nw * AE_CHUNKS), dim3(256), 0, st, dy[3], pix_rows, T_, win,
+                         recon, lpart);
+    });
     VAD_LAUNCH_CHECK();
     hipLaunchKernelGGL(ae_win_finalize_kernel, dim3((unsigned)cdiv(nw, 256)), dim3(256), 0, st, lpart, nw, T_,
                        mem_score, recon_err, score);
@@ -1642,8 +1543,8 @@ int vad_ae_windows_forward(vad_ae_plan* plan, const float* cache, const float* f
   VAD_CHECK(nw >= 1 && nw <= c.B, "vad_ae_windows_forward: nw must be in 1..B of the plan (its per-clip buffers)");
   VAD_CHECK(w0 >= 0 && w0 <= (nframes - T) / stride && nw - 1 <= (nframes - T) / stride - w0,
             "vad_ae_windows_forward: w0 .. w0 + nw - 1 reach outside the video");
-  return c.windows_forward(cache, frames, nframes, AeWindows::Linear, T, stride, w0 * stride, nw, seq, recon_err,
-                           mem_score, score, recon, (hipStream_t)stream);
+  return c.windows_forward(cache, frames, nframes, WinForm::Linear, WinRows::linear(w0 * stride, stride), T, nw, seq,
+                           recon_err, mem_score, score, recon, (hipStream_t)stream);
 }
 
 int64_t vad_ae_ring_floats(int64_t cap) {
@@ -1676,7 +1577,7 @@ int vad_ae_frames_forward_ring(vad_ae_plan* plan, const float* frames_chunk, int
   VAD_CHECK(cap >= 1 && cap <= AE_RING_MAX, "vad_ae_frames_forward_ring: cap must be in 1..2^24");
   VAD_CHECK(c.B <= cap, "vad_ae_frames_forward_ring: cap must hold the plan's B frames");
   VAD_CHECK(f0 >= 0, "vad_ae_frames_forward_ring: f0 must be >= 0");
-  return c.frames_forward_ring(frames_chunk, ring, cap, f0, (hipStream_t)stream);
+  return c.frames_forward_ring(frames_chunk, ring, cap, WinForm::Ring, f0, nullptr, (hipStream_t)stream);
 }
 
 int vad_ae_windows_forward_ring(vad_ae_plan* plan, const float* ring, int64_t cap, int T, int stride,
@@ -1698,8 +1599,8 @@ int vad_ae_windows_forward_ring(vad_ae_plan* plan, const float* ring, int64_t ca
             "vad_ae_windows_forward_ring: nw must be in 1..B of the plan (its per-clip buffers)");
   VAD_CHECK((int64_t)(nw - 1) * stride + T <= cap,
             "vad_ae_windows_forward_ring: the span (nw - 1) * stride + T of the batch exceeds cap");
-  return c.windows_forward(ring, nullptr, cap, AeWindows::Ring, T, stride, first_frame, nw, seq, recon_err, mem_score,
-                           score, recon, (hipStream_t)stream);
+  return c.windows_forward(ring, nullptr, cap, WinForm::Ring, WinRows::ring(first_frame, stride, cap), T, nw, seq,
+                           recon_err, mem_score, score, recon, (hipStream_t)stream);
 }
 
 // A group of streams.  The device table of one push (group_table.h, which also validates it): the plan's B destination
@@ -1725,8 +1626,8 @@ int vad_ae_frames_forward_group(vad_ae_plan* plan, const float* frames_chunk, in
             "vad_ae_frames_forward_group: total_slots must be in 1..2^24");
   VAD_TRY(check_and_copy_dst_table("vad_ae_frames_forward_group", host_dst, c.NF, total_slots, dev_table,
                                    (hipStream_t)stream));
-  return c.frames_forward_group(frames_chunk, ring, total_slots, static_cast<const int*>(dev_table),
-                                (hipStream_t)stream);
+  return c.frames_forward_ring(frames_chunk, ring, total_slots, WinForm::Group, 0,
+                               static_cast<const int*>(dev_table), (hipStream_t)stream);
 }
 
 int vad_ae_windows_forward_group(vad_ae_plan* plan, const float* ring, int64_t total_slots, int cap, int T,
@@ -1752,8 +1653,9 @@ int vad_ae_windows_forward_group(vad_ae_plan* plan, const float* ring, int64_t t
             "vad_ae_windows_forward_group: nw must be in 1..B of the plan (its per-clip buffers)");
   VAD_TRY(check_and_copy_window_rows("vad_ae_windows_forward_group", host_windows, 2, nw, cap, total_slots, dev_table,
                                      c.NF, (hipStream_t)stream));
-  return c.windows_forward(ring, nullptr, total_slots, AeWindows::Group, T, 1, 0, nw, seq, recon_err, mem_score, score,
-                           recon, (hipStream_t)stream, group_window_rows(dev_table, c.NF), cap);
+  return c.windows_forward(ring, nullptr, total_slots, WinForm::Group,
+                           WinRows::group(group_window_rows(dev_table, c.NF), 2, cap), T, nw, seq, recon_err, mem_score,
+                           score, recon, (hipStream_t)stream);
 }
 
 int vad_ae_debug_buffer(vad_ae_plan* plan, const char* name, int idx, void** ptr, int64_t* nfloats) {

@@ -944,29 +944,26 @@ struct CadPlanImpl {
     return 0;
   }
 
-  // The per-frame stage of the eval forward on this plan's NF frames, into frames frame0.. of a frame cache (ring:
-  // into slots (frame0 + f) mod nframes of a ring of nframes slots).
-  // dst (a group of streams): a device table of NF slots; frame f goes to slot dst[f] of the nframes slots, or nowhere.
-  int frames_forward(const float* x, int64_t nframes, float* cache, int64_t frame0, bool ring, hipStream_t st,
-                     const int* dst = nullptr) {
+  // The per-frame stage of the eval forward on this plan's NF frames, into a frame cache of nframes slots: frames
+  // frame0.. of a video, slots (frame0 + f) mod nframes of a ring, or slot dst[f] (a device table of NF slots; nowhere
+  // where negative) of a group's rings -- head.h frame_cache_store.
+  int frames_forward(const float* x, int64_t nframes, float* cache, WinForm form, int64_t frame0, const int* dst,
+                     hipStream_t st) {
     training = 0;
     labels = nullptr;
     have_labels = false;
     VAD_TRY(forward(x, st, true));
-    if (dst) TIMED("frame_cache", frame_cache_store_group(head_args(), head_out(), feats, cache, nframes, dst, st));
-    else TIMED("frame_cache", frame_cache_store(head_args(), head_out(), feats, cache, nframes, frame0, st, ring));
+    TIMED("frame_cache", frame_cache_store(head_args(), head_out(), feats, cache, nframes, form, frame0, dst, st));
     return 0;
   }
 
-  // The per-window stage for nw <= B windows of a frame cache, window i = frames first + i * stride + t at window
-  // index widx0 + i: the per-clip buffers of this plan (pooled, the direct classifier's activations, clip_flags) take
-  // one row per window.  The outputs go straight to the caller's arrays; the plan's own result arrays, flags and
-  // detector gate stay as the last forward left them.  ring: the cache is a ring of nframes slots.  tab (a group of
-  // streams): the cache holds nframes / cap rings of cap slots and window i is row i of the device window table
-  // (head.h); ring, stride, first, widx0 and clip0 are not used then.
-  int windows_forward(const float* cache, int64_t nframes, bool ring, int Tw, int stride, int64_t first, int64_t widx0,
+  // The per-window stage for nw <= B windows of a frame cache of nframes slots, window i = window i of win
+  // (win_rows.h) with the RNG key of clip clip0 + widx0 + i or of its table row: the per-clip buffers of this plan
+  // (pooled, the direct classifier's activations, clip_flags) take one row per window.  The outputs go straight to the
+  // caller's arrays; the plan's own result arrays, flags and detector gate stay as the last forward left them.
+  int windows_forward(const float* cache, int64_t nframes, WinForm form, const WinRows& win, int64_t widx0, int Tw,
                       int nw, float* o_final, float* o_probs, float* o_causal, float* o_kl, float* o_z, float* o_adj,
-                      int* o_nmax, hipStream_t st, const int64_t* tab = nullptr, int cap = 0) {
+                      int* o_nmax, hipStream_t st) {
     const CadLayout& LY = layout();
     VAD_TRY(join_open_stage2(st));
     training = 0;
@@ -975,8 +972,7 @@ struct CadPlanImpl {
     bwd_state = 0;
     dir_pre = tail_pre = 0;
     const FrameCache C(nframes);
-    if (tab) TIMED("window_mean", window_mean_group(cache, nframes, cap, Tw, tab, nw, pooled, st));
-    else TIMED("window_mean", window_mean(cache, nframes, Tw, stride, first, nw, pooled, st, ring));
+    TIMED("window_mean", window_mean(cache, nframes, Tw, form, win, nw, pooled, st));
     // direct_classifier on the window means (cad:525-538, 568-570), eval activations, through the forward's launchers
     const int gd[6] = {6144, 512, 256, 128, 64, 2};
     const float* in = pooled;
@@ -989,21 +985,15 @@ struct CadPlanImpl {
     HeadArgs a = head_args();
     a.B = nw;
     a.T = Tw;
+    a.clip0 += widx0;
     a.ws = nullptr;
     a.iws = nullptr;
     a.rows = nullptr;
     a.grad = nullptr;
-    SeqWindows win{};
-    win.gi = cache + C.gi;
-    win.counts = reinterpret_cast<const int*>(cache) + C.counts;
-    win.slot = reinterpret_cast<const int*>(cache) + C.slot;
-    win.stride = stride;
-    win.first = first;
-    win.widx0 = widx0;
-    win.cap = tab ? cap : ring ? (int)nframes : 0;
+    const int* ci = reinterpret_cast<const int*>(cache);
+    const SeqWindows sw{cache + C.gi, ci + C.counts, ci + C.slot, win};
     const HeadOut ho{o_causal, o_kl, o_z, o_adj, nullptr, nullptr, o_nmax, clip_flags};
-    if (tab) TIMED("head_seq_win", head_seq_group_fwd(a, win, tab, nw, ho, st));
-    else TIMED("head_seq_win", head_seq_windows_fwd(a, win, nw, ho, st));
+    TIMED("head_seq_win", head_seq_windows_fwd(a, form, sw, nw, ho, st));
     TailArgs t{};
     t.B = nw;
     t.direct_logits = glog;
@@ -1475,7 +1465,7 @@ int vad_cad_frames_forward(vad_cad_plan* plan, const float* x, int64_t nframes, 
             "vad_cad_frames_forward: frame0 .. frame0 + B*T outside the nframes of the cache");
   VAD_CHECK((int64_t)c.NF * c.H * c.W * 4 < (1ll << 31), "vad_cad_frames_forward: x is 2 GB or more");
   VAD_CHECK(FrameCache(nframes).total * 4 < (1ll << 31), "vad_cad_frames_forward: cache is 2 GB or more");
-  return c.frames_forward(x, nframes, cache, frame0, false, (hipStream_t)stream);
+  return c.frames_forward(x, nframes, cache, WinForm::Linear, frame0, nullptr, (hipStream_t)stream);
 }
 
 int vad_cad_frames_forward_ring(vad_cad_plan* plan, const float* x, int64_t cap, float* cache, int64_t frame0,
@@ -1487,7 +1477,7 @@ int vad_cad_frames_forward_ring(vad_cad_plan* plan, const float* x, int64_t cap,
   VAD_CHECK(frame0 >= 0, "vad_cad_frames_forward_ring: frame0 must be >= 0");
   VAD_CHECK((int64_t)c.NF * c.H * c.W * 4 < (1ll << 31), "vad_cad_frames_forward_ring: x is 2 GB or more");
   VAD_CHECK(FrameCache(cap).total * 4 < (1ll << 31), "vad_cad_frames_forward_ring: cache is 2 GB or more");
-  return c.frames_forward(x, cap, cache, frame0, true, (hipStream_t)stream);
+  return c.frames_forward(x, cap, cache, WinForm::Ring, frame0, nullptr, (hipStream_t)stream);
 }
 
 int vad_cad_windows_forward(vad_cad_plan* plan, const float* cache, int64_t nframes, int T, int stride, int64_t w0,
@@ -1508,8 +1498,8 @@ int vad_cad_windows_forward(vad_cad_plan* plan, const float* cache, int64_t nfra
   c.seed = seed;
   c.step = step;
   c.clip0 = clip0;
-  return c.windows_forward(cache, nframes, false, T, stride, w0 * stride, w0, nw, final_scores, probs, causal, kl, z,
-                           adj, nmax, (hipStream_t)stream);
+  return c.windows_forward(cache, nframes, WinForm::Linear, WinRows::linear(w0 * stride, stride), w0, T, nw,
+                           final_scores, probs, causal, kl, z, adj, nmax, (hipStream_t)stream);
 }
 
 int vad_cad_windows_forward_ring(vad_cad_plan* plan, const float* cache, int64_t cap, int T, int stride,
@@ -1533,8 +1523,8 @@ int vad_cad_windows_forward_ring(vad_cad_plan* plan, const float* cache, int64_t
   c.seed = seed;
   c.step = step;
   c.clip0 = clip0;
-  return c.windows_forward(cache, cap, true, T, stride, first_frame, widx0, nw, final_scores, probs, causal, kl, z,
-                           adj, nmax, (hipStream_t)stream);
+  return c.windows_forward(cache, cap, WinForm::Ring, WinRows::ring(first_frame, stride, cap), widx0, T, nw,
+                           final_scores, probs, causal, kl, z, adj, nmax, (hipStream_t)stream);
 }
 
 // A group of streams.  The device table of one push (group_table.h, which also validates it): the plan's B*T
@@ -1556,7 +1546,8 @@ int vad_cad_frames_forward_group(vad_cad_plan* plan, const float* x, int64_t tot
   VAD_CHECK(FrameCache(total_slots).total * 4 < (1ll << 31), "vad_cad_frames_forward_group: cache is 2 GB or more");
   VAD_TRY(check_and_copy_dst_table("vad_cad_frames_forward_group", host_dst, c.NF, total_slots, dev_table,
                                    (hipStream_t)stream));
-  return c.frames_forward(x, total_slots, cache, 0, false, (hipStream_t)stream, static_cast<const int*>(dev_table));
+  return c.frames_forward(x, total_slots, cache, WinForm::Group, 0, static_cast<const int*>(dev_table),
+                          (hipStream_t)stream);
 }
 
 int vad_cad_windows_forward_group(vad_cad_plan* plan, const float* cache, int64_t total_slots, int cap, int T,
@@ -1581,8 +1572,9 @@ int vad_cad_windows_forward_group(vad_cad_plan* plan, const float* cache, int64_
   c.seed = seed;
   c.step = step;
   c.clip0 = 0;
-  return c.windows_forward(cache, total_slots, true, T, 1, 0, 0, nw, final_scores, probs, causal, kl, z, adj, nmax,
-                           (hipStream_t)stream, group_window_rows(dev_table, c.NF), cap);
+  return c.windows_forward(cache, total_slots, WinForm::Group,
+                           WinRows::group(group_window_rows(dev_table, c.NF), 3, cap), 0, T, nw, final_scores, probs,
+                           causal, kl, z, adj, nmax, (hipStream_t)stream);
 }
 
 int vad_cad_backward(vad_cad_plan* plan, int use_loss, const float* d_final, const float* d_probs,

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <string>
 
+#include "win_rows.h"
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -199,7 +201,7 @@ __device__ inline f32x16 mfma32(float a, float b, f32x16 c) {
 // 64-bit modulo stays out of its element and tap loops -- and indexes the plane with 64-bit pointer arithmetic.
 // The group form (table != null, and first, stride and ring are not read): frames is one allocation of
 // many rings of cap slots each, and table holds two int64 per window, (base, first) -- window b, time t is slot
-// base_b + (first_b + t) mod cap, where 0 <= first_b < cap and t < T <= cap make the modulo one wrap.  The rows are
+// base_b + (first_b + t) mod cap, where 0 <= first_b < cap and t < T <= cap make the modulo wrap_once.  The rows are
 // validated on the host before the launch (group_table.h win_group_src); b is block-uniform in every loader, so the
 // two table words are one uniform load per plane.
 struct WinSrc {
@@ -216,8 +218,7 @@ struct WinSrc {
 #else
       const int64_t* row = table + 2 * b;
 #endif
-      const int64_t s = row[1] + t;
-      return row[0] + (s >= cap ? s - cap : s);
+      return row[0] + wrap_once(row[1] + t, cap);
     }
     const int64_t f = first + b * stride + t;
     return ring > 0 ? f % ring : f;

@@ -87,44 +87,32 @@ struct FrameCache {
     total = o;
   }
 };
-// The same layout serves as a ring of N slots for a stream of frames (ring = true below): frame g, counted from the
-// start of the stream, lives in slot g mod N.  Which frames are resident is the caller's bookkeeping.
-// copies the B*T frames head_rows_fwd just processed (a.rows / a.iws, o.boxes / o.counts) and their pooled features
-// to frames frame0.. of the cache (ring: to slots (frame0 + f) mod nframes; the chunk may straddle the wrap)
+// The same layout serves a live stream as a ring of N slots, and a group of streams as total_slots = (number of
+// rings) * cap slots, ring s in slots s * cap .. (s + 1) * cap - 1.  The three functions below take the form as a
+// WinForm; how each form finds frame t of window b, and where it stores frame f of a chunk, is win_rows.h.  The group
+// form's device tables were validated by the caller on the host (vad_cad_*_group in cad_plan.hip); nothing here looks
+// at a table's contents.  Which frames are resident is the caller's bookkeeping.
+// copies the B*T frames head_rows_fwd just processed (a.rows / a.iws, o.boxes / o.counts) and their pooled features to
+// the cache: frame f to slot frame_slot(f) of its nframes slots (Linear, Ring: from frame0, and a ring's chunk may
+// straddle the wrap; Group: to dst[f], a device table, or nowhere where dst[f] < 0)
 int frame_cache_store(const HeadArgs& a, const HeadOut& o, const float* feats, float* cache, int64_t nframes,
-                      int64_t frame0, hipStream_t st, bool ring = false);
-// pooled[i][k] = (sum_{t < T} feats[first + i * stride + t][k]) / T for i < nw, summed in ascending t from 0 as
-// avgpool_fwd forms a clip's mean (ring: row t is slot (first + i * stride + t) mod nframes, the same sum)
-int window_mean(const float* cache, int64_t nframes, int T, int stride, int64_t first, int nw, float* pooled,
-                hipStream_t st, bool ring = false);
-// head_seq_fwd on windows of the cache, forward only: block i runs the window of frames first + i * stride + t with
-// the RNG key of clip a.clip0 + widx0 + i and writes row i of o.causal / kl / z / adj / nmax / clip_flags; a.T is the
-// window length; a.rows / a.ws / a.iws are not used (no backward state is kept).  cap = 0: the cache is linear;
-// cap > 0: a ring of cap >= a.T slots, frame g in slot g mod cap.
+                      WinForm form, int64_t frame0, const int* dst, hipStream_t st);
+// pooled[i][k] = (sum_{t < T} feats[frame t of window i of win][k]) / T for i < nw, summed in ascending t from 0 as
+// avgpool_fwd forms a clip's mean, in every form
+int window_mean(const float* cache, int64_t nframes, int T, WinForm form, const WinRows& win, int nw, float* pooled,
+                hipStream_t st);
+// head_seq_fwd on windows of the cache, forward only: block i runs window i of win.rows with the RNG key of clip
+// a.clip0 + i (Group: the key of its table row, three words per row; a.clip0 is not read) and writes row i of
+// o.causal / kl / z / adj / nmax / clip_flags; a.T is the window length; a.rows / a.ws / a.iws are not used (no
+// backward state is kept).
 struct SeqWindows {
   const float* gi;    // FrameCache::gi
   const int* counts;  // FrameCache::counts
   const int* slot;    // FrameCache::slot
-  int stride;
-  int64_t first;      // the first frame of window 0
-  int64_t widx0;      // the index of window 0 (RNG key)
-  int cap;
+  WinRows rows;
 };
-int head_seq_windows_fwd(const HeadArgs& a, const SeqWindows& win, int nw, const HeadOut& o, hipStream_t st);
-
-// A group of streams: one cache of total_slots = (number of rings) * cap slots, ring s in slots s * cap .. (s + 1) *
-// cap - 1.  The three kernels take their addresses from device tables that the caller has validated on the host
-// (vad_cad_*_group in cad_plan.hip); nothing here looks at a table's contents.
-// frame_cache_store with frame f going to slot dst[f] of the cache, or nowhere where dst[f] < 0
-int frame_cache_store_group(const HeadArgs& a, const HeadOut& o, const float* feats, float* cache, int64_t total_slots,
-                            const int* dst, hipStream_t st);
-// Window table: int64 (base, s0, key) per window -- the window's T frames are slots base + ((s0 + t) wrapped once at
-// cap) and key is its RNG clip key.  window_mean / head_seq_windows_fwd on the nw windows of such a table; win.gi /
-// counts / slot / cap are read, win.stride / first / widx0 and a.clip0 are not.
-int window_mean_group(const float* cache, int64_t total_slots, int cap, int T, const int64_t* tab, int nw,
-                      float* pooled, hipStream_t st);
-int head_seq_group_fwd(const HeadArgs& a, const SeqWindows& win, const int64_t* tab, int nw, const HeadOut& o,
-                       hipStream_t st);
+int head_seq_windows_fwd(const HeadArgs& a, WinForm form, const SeqWindows& win, int nw, const HeadOut& o,
+                         hipStream_t st);
 
 // backward: upstream grads -> grad slabs [B][slab] and d(det logits) [B*T][20]
 struct HeadUp {

@@ -385,23 +385,14 @@ __global__ __launch_bounds__(256) void head_rows_fwd_kernel(HeadArgs a, const fl
 
 // The per-clip sequence forward, for two callers.  WIN = false (head_seq_fwd_kernel): block b runs clip b of the batch
 // -- frames b*T + t of a.rows / a.iws -- and keeps the recurrence's state (r, z, n, W_hn h, h_prev rows) and its
-// small activations for the backward.  WIN = true (head_seq_win_kernel, sliding-window scoring): block b runs window
-// b of a batch of windows of a frame cache -- frames win.first + b * win.stride + t -- with the RNG key of clip
-// a.clip0 + win.widx0 + b, forward only: none of the backward state is stored (most of the clip kernel's memory
-// traffic).  RING (head_seq_ring_kernel, with WIN): the cache is a ring of win.cap >= T slots and frame g lives in slot
-// g mod cap; the window's first slot is reduced once per block, step t then reads slot s0 + t less cap where it passes
-// the end (s0 + t < 2 cap) -- an add, a compare and a select on wave-uniform values, no division in the recurrence.
-// GROUP (head_seq_group_kernel, with RING): the cache holds many rings of win.cap slots and block b reads its entry
-// (base_b, s0_b, key_b) of the window table once, before the recurrence: cnt / slot / gi_win start at slot base_b,
-// s0_b is the window's first slot within that ring and key_b its RNG clip key.  The entry's address depends on
-// blockIdx alone, so the three values are scalar loads and stay in scalar registers; the recurrence is the ring form's.
-// Every difference is an `if constexpr`, so the clip kernel's and the linear window kernel's arithmetic and its order
-// are those of the untemplated kernel.
-template <bool WIN, bool RING = false, bool GROUP = false>
-__device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWindows win,
-                                                  const int64_t* __restrict__ tab = nullptr) {
-  static_assert(WIN || !RING, "the ring form addresses a frame cache");
-  static_assert(RING || !GROUP, "the group form addresses rings");
+// small activations for the backward.  WIN = true (head_seq_win_kernel<F>, sliding-window scoring): block b runs window
+// b of win.rows (win_rows.h), reading the frame cache's rows, with the RNG key of clip a.clip0 + b or, in the group
+// form, of its table row; forward only: none of the backward state is stored (most of the clip kernel's memory
+// traffic).  The window is resolved once per block, before the recurrence, and the row of a step is block-uniform
+// integer work.  Every difference is an `if constexpr`, so the clip kernel's and the linear window kernel's arithmetic
+// and its order are those of the untemplated kernel.
+template <bool WIN, WinForm F = WinForm::Linear>
+__device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, const SeqWindows& win) {
   const int b = blockIdx.x, T = a.T, tid = threadIdx.x;
   const HL L;
   const RowLayout RL((int64_t)a.B * T * NMAX);
@@ -410,35 +401,14 @@ __device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWind
   const int* iw = a.iws + (int64_t)b * a.iws_stride;
   const int* cnt = iw;
   const int* slot = iw + T;
-  const float* gi_win = nullptr;  // WIN: the projections of the window's first frame (RING: of slot 0)
-  int s0 = 0;                     // RING: the slot of the window's first frame
-  // frame t of the window: row t of cnt / slot / gi_win, or with RING row fr(t)
-  auto fr = [&](int t) {
-    if constexpr (RING) {
-      const int s = s0 + t;
-      return s >= win.cap ? s - win.cap : s;
-    } else {
-      return t;
-    }
-  };
-  if constexpr (GROUP) {
-    const int64_t* e = tab + 3 * (int64_t)b;
-    const int64_t f0 = e[0];
-    s0 = (int)e[1];
-    cnt = win.counts + f0;
-    slot = win.slot + f0 * NMAX;
-    gi_win = win.gi + f0 * NMAX * G3;
-    a.clip0 = e[2] - b;  // the RNG key of block b, a.clip0 + b below, is the table's
-  } else if constexpr (WIN) {
-    int64_t f0 = win.first + (int64_t)b * win.stride;
-    if constexpr (RING) {
-      s0 = (int)(f0 % win.cap);
-      f0 = 0;
-    }
-    cnt = win.counts + f0;
-    slot = win.slot + f0 * NMAX;
-    gi_win = win.gi + f0 * NMAX * G3;
-    a.clip0 += win.widx0;  // the RNG key of block b: clip a.clip0 + b
+  const float* gi_win = nullptr;  // WIN: the projections of row 0 of the window's cursor
+  const WinCursor<F> cur(win.rows, WIN ? b : 0);
+  // frame t of the window is row cur.row(t) of cnt / slot / gi_win
+  if constexpr (WIN) {
+    cnt = win.counts + cur.base;
+    slot = win.slot + cur.base * NMAX;
+    gi_win = win.gi + cur.base * NMAX * G3;
+    if constexpr (F == WinForm::Group) a.clip0 = cur.key() - b;  // the RNG key of block b is a.clip0 + b below
   }
   __shared__ __attribute__((aligned(16))) float big[HF_BIG];  // W_hh during the recurrence, then the MLP weights
   __shared__ __attribute__((aligned(16))) float sw[HL_TOTAL];
@@ -455,8 +425,8 @@ __device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWind
   if (tid == 0) {
     int N = 1, any = 0;
     for (int t = 0; t < T; ++t) {
-      N = max(N, cnt[fr(t)]);
-      if (slot[fr(t) * NMAX] >= 0) any = 1;
+      N = max(N, cnt[cur.row(t)]);
+      if (slot[cur.row(t) * NMAX] >= 0) any = 1;
     }
     s_N = N;
     s_any = any;
@@ -500,7 +470,7 @@ __device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWind
           g[k][0] = g[k][1] = g[k][2] = 0.f;
           if (t0 + k < T) {
             const float* gi;
-            if constexpr (WIN) gi = gi_win + ((int64_t)fr(t0 + k) * NMAX + nn) * G3;
+            if constexpr (WIN) gi = gi_win + ((int64_t)cur.row(t0 + k) * NMAX + nn) * G3;
             else gi = rows + RL.gi + (((int64_t)b * T + t0 + k) * NMAX + nn) * G3;
             g[k][0] = gi[u]; g[k][1] = gi[GH + u]; g[k][2] = gi[2 * GH + u];
           }
@@ -697,15 +667,9 @@ __device__ __forceinline__ void head_seq_fwd_body(HeadArgs a, HeadOut o, SeqWind
 __global__ __launch_bounds__(HT) void head_seq_fwd_kernel(HeadArgs a, HeadOut o) {
   head_seq_fwd_body<false>(a, o, SeqWindows{});
 }
+template <WinForm F>
 __global__ __launch_bounds__(HT) void head_seq_win_kernel(HeadArgs a, HeadOut o, SeqWindows win) {
-  head_seq_fwd_body<true>(a, o, win);
-}
-__global__ __launch_bounds__(HT) void head_seq_ring_kernel(HeadArgs a, HeadOut o, SeqWindows win) {
-  head_seq_fwd_body<true, true>(a, o, win);
-}
-__global__ __launch_bounds__(HT) void head_seq_group_kernel(HeadArgs a, HeadOut o, SeqWindows win,
-                                                            const int64_t* __restrict__ tab) {
-  head_seq_fwd_body<true, true, true>(a, o, win, tab);
+  head_seq_fwd_body<true, F>(a, o, win);
 }
 
 int head_rows_fwd(const HeadArgs& a, const float* det_logits, const HeadOut& o, hipStream_t st) {
@@ -719,21 +683,19 @@ int head_seq_fwd(const HeadArgs& a, const HeadOut& o, hipStream_t st) {
   VAD_LAUNCH_CHECK();
   return 0;
 }
-int head_seq_windows_fwd(const HeadArgs& a, const SeqWindows& win, int nw, const HeadOut& o, hipStream_t st) {
-  VAD_CHECK(a.T >= 1 && a.T <= 4096 && win.stride >= 1 && win.first >= 0 && nw >= 1, "head: bad window arguments");
-  // (a ring holds the batch's whole span, so no slot stands for two frames of it)
-  VAD_CHECK(win.cap == 0 || (win.cap >= a.T && (int64_t)(nw - 1) * win.stride + a.T <= win.cap),
-            "head: the windows do not fit the ring");
-  if (win.cap > 0) VAD_KLAUNCH(head_seq_ring_kernel, dim3(nw), dim3(HT), 0, st, a, o, win);
-  else VAD_KLAUNCH(head_seq_win_kernel, dim3(nw), dim3(HT), 0, st, a, o, win);
-  VAD_LAUNCH_CHECK();
-  return 0;
-}
-int head_seq_group_fwd(const HeadArgs& a, const SeqWindows& win, const int64_t* tab, int nw, const HeadOut& o,
-                       hipStream_t st) {
-  VAD_CHECK(tab != nullptr && nw >= 1 && a.T >= 1 && a.T <= 4096 && win.cap >= a.T,
-            "head: bad window-table arguments");
-  VAD_KLAUNCH(head_seq_group_kernel, dim3(nw), dim3(HT), 0, st, a, o, win, tab);
+int head_seq_windows_fwd(const HeadArgs& a, WinForm form, const SeqWindows& win, int nw, const HeadOut& o,
+                         hipStream_t st) {
+  const WinRows& r = win.rows;
+  if (form == WinForm::Group) {
+    VAD_CHECK(r.tab != nullptr && r.words == 3 && nw >= 1 && a.T >= 1 && a.T <= 4096 && r.cap >= a.T,
+              "head: bad window-table arguments");
+  } else {
+    VAD_CHECK(a.T >= 1 && a.T <= 4096 && r.stride >= 1 && r.first >= 0 && nw >= 1, "head: bad window arguments");
+    // (a ring holds the batch's whole span, so no slot stands for two frames of it)
+    VAD_CHECK(form == WinForm::Linear || (r.cap >= a.T && (int64_t)(nw - 1) * r.stride + a.T <= r.cap),
+              "head: the windows do not fit the ring");
+  }
+  win_dispatch(form, [&](auto F) { VAD_KLAUNCH(head_seq_win_kernel<F()>, dim3(nw), dim3(HT), 0, st, a, o, win); });
   VAD_LAUNCH_CHECK();
   return 0;
 }
