@@ -45,6 +45,54 @@ struct X3Args {
   const __bf16* w3;  // stride-2 input gradient: pre-split Wd planes [N][9][C / 16][3][16] (nullable)
 };
 
+// Buffer-resource addressing of the staging loads and the epilogue stores: a resource over the whole tensor (the host
+// keeps every tensor of these launch paths below 2 GB) and a 32-bit byte offset per lane.  A lane with nothing to load
+// or store takes S2_OOB, a byte offset past every buffer's end: the load returns zeros and the store is dropped, so
+// neither needs a branch, a dummy address or a select on the values.  Offsets are unsigned to the hardware: S2_OOB plus
+// any in-range offset (< 2^31 - 16) is still past the end, so a tile or chunk base may be added to it unselected.
+constexpr int S2_OOB = 0x7ffffff0;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t s2_rsrc(const void* p, int64_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0,
+                                           (int)(bytes < (int64_t)S2_OOB ? bytes : (int64_t)S2_OOB), 0x00020000);
+}
+__device__ __forceinline__ int s2_add(int off, int add) { return off == S2_OOB ? S2_OOB : off + add; }
+__device__ __forceinline__ int s2_uadd(int off, int add) { return (int)((unsigned)off + (unsigned)add); }
+
+// 8 consecutive elements (32 B of fp32, 16 B of bf16) at byte offset o, raw; piece_f converts them at stash time
+template <bool AB>
+struct Piece8 {
+  u32x4 q[AB ? 1 : 2];
+  __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t rs, int o) {
+    q[0] = __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 0);
+    if constexpr (!AB) q[1] = __builtin_amdgcn_raw_buffer_load_b128(rs, s2_uadd(o, 16), 0, 0);
+  }
+  __device__ __forceinline__ void get(float* v) const {
+    if constexpr (AB) {
+      typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+      const bf16x8_t b = __builtin_bit_cast(bf16x8_t, q[0]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (float)b[e];
+    } else {
+      const f32x4 v0 = __builtin_bit_cast(f32x4, q[0]), v1 = __builtin_bit_cast(f32x4, q[1]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[e] = v0[e];
+        v[4 + e] = v1[e];
+      }
+    }
+  }
+};
+template <bool AB>
+__device__ __forceinline__ void buf_st(__amdgpu_buffer_rsrc_t rs, int o, float v) {
+  if constexpr (AB) __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)v), rs, o, 0, 0);
+  else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, o, 0, 0);
+}
+template <bool AB>
+__device__ __forceinline__ float buf_ld(__amdgpu_buffer_rsrc_t rs, int o) {
+  if constexpr (AB) return (float)__builtin_bit_cast(__bf16, __builtin_amdgcn_raw_buffer_load_b16(rs, o, 0, 0));
+  else return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0));
+}
+
 // epilogue half of the fused BN-backward reduce (bn_bwd_reduce_kernel's arithmetic on the value just computed; with
 // bf16 storage on the value as stored)
 struct BnBwdLane {
@@ -54,10 +102,6 @@ struct BnBwdLane {
     inv = st[C + c];
     sc = st[2 * C + c];
     sh = st[3 * C + c];
-  }
-  template <bool AB>
-  __device__ __forceinline__ static float ld(const void* bny, int64_t idx) {
-    return act_ld(reinterpret_cast<const act_t<AB>*>(bny) + idx);
   }
   // (the y values are loaded for the whole epilogue first: one wait instead of a round trip per pixel)
   template <bool AB>
@@ -145,8 +189,6 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv3x3_x3_kernel(const X3Arg
   static_assert(NP == 3 || NP == 1, "three split planes (fp32 numerics) or one (bf16 operands)");
   static_assert(!AB || NP == 1, "bf16 storage with bf16 operands only");
   using TA = act_t<AB>;
-  const TA* src = reinterpret_cast<const TA*>(p.src);
-  TA* out = reinterpret_cast<TA*>(p.out);
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   static_assert(NI * TH * TW == 32 * NW, "a wave owns 32 output pixels");
   constexpr int NTHR = 64 * NW;
@@ -183,14 +225,25 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv3x3_x3_kernel(const X3Arg
   // q % G8 put 8 rows x 2 groups in a phase: two lanes on one quad in every phase)
   const int g8p = G8 == 2 ? (tid >> 4) & 1 : g8;
   auto prow = [](int q) { return G8 == 2 ? ((q >> 5) << 4) + (q & 15) : q / G8; };
-  act_raw4<AB> pv[PIT][2];
-  f32x4 wv[WIT][2];
-  // prefetch loads are unconditional (out-of-range lanes read a valid dummy address) and the zero padding is applied
-  // at stash time from these bits, so no masked-load branch makes the compiler wait for the loads before the MFMAs
-  bool pok[PIT], wok[WIT];
-  // loop-invariant piece geometry, 32-bit offsets (the host keeps every tensor below 2^31 elements): patch piece it =
+  Piece8<AB> pv[PIT];
+  Piece8<false> wv[WIT];
+  f32x4 sc[2], sh[2];  // BN scale / shift of the prefetched item's 8 channels (forward)
+  // prefetch loads are unconditional buffer loads (see S2_OOB: a piece outside the frame, past the patch or in an image
+  // >= NF reads zeros from an offset past the end), so no masked-load branch makes the compiler wait for the loads
+  // before the MFMAs and the zero padding costs no select on the values.  A piece left or right of the frame is not
+  // out of range in the linear buffer -- it lies on a neighbouring row -- so the offset, not the address range,
+  // carries the mask: one select per piece.  pok is kept for BN on load alone (a padded tap must stay 0, not relu(shift))
+  bool pok[PIT];
+  const bool bn = FWD && p.scale;
+  constexpr int TB = (int)sizeof(TA);
+  const __amdgpu_buffer_rsrc_t src_rs = s2_rsrc(p.src, (int64_t)p.NF * p.IH * p.IW * p.C * TB);
+  const __amdgpu_buffer_rsrc_t w_rs = s2_rsrc(p.w, (int64_t)KD * p.N * 9 * p.C * 4);
+  // (no BN: zero-length ranges, scale and shift read as 0 and are not used)
+  const __amdgpu_buffer_rsrc_t sc_rs = s2_rsrc(bn ? p.scale : p.w, bn ? (int64_t)p.C * 4 : 0);
+  const __amdgpu_buffer_rsrc_t sh_rs = s2_rsrc(bn ? p.shift : p.w, bn ? (int64_t)p.C * 4 : 0);
+  // loop-invariant piece geometry, 32-bit byte offsets (the host keeps every tensor below 2 GB): patch piece it =
   // (image, patch row, input column) packed (-1: past the patch), its NHWC offset from the tile's patch origin and its
-  // LDS offset; weight piece it = its offset from row n0 of chunk 0 (-1: past the slice or the last channel)
+  // LDS offset; weight piece it = its offset from row n0 of chunk 0 (S2_OOB: past the slice or the last channel)
   int pgeo[PIT], pgo[PIT], plo[PIT], wgo[WIT], wlo[WIT];
 #pragma unroll
   for (int it = 0; it < PIT; ++it) {
@@ -200,14 +253,14 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv3x3_x3_kernel(const X3Arg
     // (stride 2: staging items run in the stored, parity-split column order, see stash)
     const int rx = S == 1 ? scol : (scol < PWE ? 2 * scol : 2 * (scol - PWE) + 1);
     pgeo[it] = row < PROWS ? (im << 16) | (ry << 8) | rx : -1;
-    pgo[it] = ((im * p.IH + ry) * p.IW + rx) * p.C + g8p * 8;
+    pgo[it] = (((im * p.IH + ry) * p.IW + rx) * p.C + g8p * 8) * TB;
     plo[it] = ((im * PH + ry) * PW + scol) * RP + g8p * 8;
   }
 #pragma unroll
   for (int it = 0; it < WIT; ++it) {
     const int q = min(tid + it * NTHR, WQ - 1);
     const int n = q / (9 * G8), t = (q / G8) % 9;
-    wgo[it] = (tid + it * NTHR < WQ && n0 + n < p.N) ? (n * 9 + (FWD ? t : 8 - t)) * p.C + g8 * 8 : -1;
+    wgo[it] = (tid + it * NTHR < WQ && n0 + n < p.N) ? ((n * 9 + (FWD ? t : 8 - t)) * p.C + g8 * 8) * 4 : S2_OOB;
     wlo[it] = tid + it * NTHR < WQ ? n * WP + t * NP * PC + g8 * 8 : -1;
   }
   auto origin = [&](int tile, int& img0, int& oy0, int& ox0) {
@@ -216,82 +269,59 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv3x3_x3_kernel(const X3Arg
     oy0 = (tr / p.tiles_w) * TH;
     ox0 = (tr % p.tiles_w) * TW;
   };
-  auto fetch = [&](int tile, int ch, bool weights) {
+  auto fetch = [&](int tile, int ch, bool weights, bool bnc) {
     int img0, oy0, ox0;
     origin(tile, img0, oy0, ox0);
     const int kd = ch / nchc, c0 = (ch - kd * nchc) * PC;
     const int iy0 = oy0 * S - 1, ix0 = ox0 * S - 1;
-    if constexpr (KD == 1) {
-      // (block-uniform) the whole patch inside the frames: only the pieces past the patch are masked
-      const bool inner = iy0 >= 0 && ix0 >= 0 && iy0 + PH <= p.IH && ix0 + PW <= p.IW && img0 + NI <= p.NF;
-      const int base = ((img0 * p.IH + iy0) * p.IW + ix0) * p.C + c0;
+    // (block-uniform) the whole patch inside the frames: only the pieces past the patch are masked
+    const bool inner =
+        KD == 1 && iy0 >= 0 && ix0 >= 0 && iy0 + PH <= p.IH && ix0 + PW <= p.IW && img0 + NI <= p.NF;
+    // byte offset of the tile's patch origin (KD = 3: in depth slice d + kd - 1); it may lie before the tensor, a
+    // piece inside the frames never does
+    const int base = ((((img0 + (KD == 3 ? kd - 1 : 0)) * p.IH + iy0) * p.IW + ix0) * p.C + c0) * TB;
 #pragma unroll
-      for (int it = 0; it < PIT; ++it) {
-        const int g = pgeo[it], im = (g >> 16) & 255, ry = (g >> 8) & 255, rx = g & 255;
-        pok[it] = g >= 0 && (inner || (img0 + im < p.NF && (unsigned)(iy0 + ry) < (unsigned)p.IH &&
-                                       (unsigned)(ix0 + rx) < (unsigned)p.IW));
-        const TA* s = src + (pok[it] ? base + pgo[it] : 0);
-        pv[it][0] = act_ld4(s);
-        pv[it][1] = act_ld4(s + 4);
+    for (int it = 0; it < PIT; ++it) {
+      const int g = pgeo[it], im = (g >> 16) & 255, ry = (g >> 8) & 255, rx = g & 255;
+      bool ok = g >= 0 && (inner || (img0 + im < p.NF && (unsigned)(iy0 + ry) < (unsigned)p.IH &&
+                                     (unsigned)(ix0 + rx) < (unsigned)p.IW));
+      if constexpr (KD == 3) {  // depth slice d + kd - 1 of the same clip
+        const int d = (img0 + im) % p.D + kd - 1;
+        ok = ok && d >= 0 && d < p.D;
       }
-    } else {
-#pragma unroll
-      for (int it = 0; it < PIT; ++it) {
-        const int g = pgeo[it], im = (g >> 16) & 255, ry = (g >> 8) & 255, rx = g & 255;
-        const int iy = iy0 + ry, ix = ix0 + rx;
-        // depth slice d + kd - 1 of the same clip
-        const int img = img0 + im + kd - 1, d = (img0 + im) % p.D + kd - 1;
-        pok[it] = g >= 0 && d >= 0 && d < p.D && img0 + im < p.NF && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
-        const TA* s = src + c0 + g8p * 8 + (pok[it] ? (((int64_t)img * p.IH + iy) * p.IW + ix) * p.C : (int64_t)0);
-        pv[it][0] = act_ld4(s);
-        pv[it][1] = act_ld4(s + 4);
-      }
+      pok[it] = ok;
+      pv[it].load(src_rs, ok ? base + pgo[it] : S2_OOB);
+    }
+    if (FWD && bnc) {
+      // the chunk's BN constants travel with its patch (they were loaded, and waited for, at the top of every stash);
+      // bnc: only where the channel base changes between items
+      const int o = (c0 + g8p * 8) * 4;
+      sc[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sc_rs, o, 0, 0));
+      sc[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sc_rs, o + 16, 0, 0));
+      sh[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sh_rs, o, 0, 0));
+      sh[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sh_rs, o + 16, 0, 0));
     }
     if (weights) {
-      const float* wsrc = p.w + ((int64_t)kd * p.N + n0) * 9 * p.C + c0;
+      const int wbase = ((kd * p.N + n0) * 9 * p.C + c0) * 4;
 #pragma unroll
-      for (int it = 0; it < WIT; ++it) {
-        wok[it] = wgo[it] >= 0;
-        const float* s = wok[it] ? wsrc + wgo[it] : p.w;
-        wv[it][0] = *reinterpret_cast<const f32x4*>(s);
-        wv[it][1] = *reinterpret_cast<const f32x4*>(s + 4);
-      }
+      for (int it = 0; it < WIT; ++it) wv[it].load(w_rs, s2_uadd(wgo[it], wbase));
     }
   };
   auto stash = [&](int tile, int ch, bool weights) {
     const int c0 = (ch % nchc) * PC;
-    // (BN constants loaded and used unconditionally -- from a dummy address when there is no BN -- so no load is
-    // left pending on a branch the waitcnt analysis would have to assume, which made it drain the prefetch loads
-    // before the first MFMA)
-    const bool bn = FWD && p.scale;
-    f32x4 sc[2], sh[2];
-    if constexpr (FWD) {
-      const float* scp = bn ? p.scale : p.w;
-      const float* shp = bn ? p.shift : p.w;
-      sc[0] = *reinterpret_cast<const f32x4*>(scp + c0 + g8p * 8);
-      sc[1] = *reinterpret_cast<const f32x4*>(scp + c0 + g8p * 8 + 4);
-      sh[0] = *reinterpret_cast<const f32x4*>(shp + c0 + g8p * 8);
-      sh[1] = *reinterpret_cast<const f32x4*>(shp + c0 + g8p * 8 + 4);
-    }
 #pragma unroll
     for (int it = 0; it < PIT; ++it) {
       if (pgeo[it] >= 0) {
         float v[8];
-        const f32x4 v0 = act_f4(pv[it][0]), v1 = act_f4(pv[it][1]);
-        const bool ok = pok[it];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[e] = ok ? v0[e] : 0.f;
-          v[4 + e] = ok ? v1[e] : 0.f;
-        }
+        pv[it].get(v);  // (a masked piece was loaded as zeros)
         if constexpr (FWD) {
           if (bn) {  // zero padding stays zero (padded taps read 0 in the reference's zero-padded relu(bn(y)));
                      // selects, no branches; NaN propagates like torch's relu
+            const bool ok = pok[it];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float a0 = fmaf(v0[e], sc[0][e], sh[0][e]), a1 = fmaf(v1[e], sc[1][e], sh[1][e]);
-              v[e] = (a0 <= 0.f || !ok) ? 0.f : a0;
-              v[4 + e] = (a1 <= 0.f || !ok) ? 0.f : a1;
+            for (int e = 0; e < 8; ++e) {
+              const float a = fmaf(v[e], sc[e >> 2][e & 3], sh[e >> 2][e & 3]);
+              v[e] = (a <= 0.f || !ok) ? 0.f : a;
             }
           }
         }
@@ -306,11 +336,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv3x3_x3_kernel(const X3Arg
       for (int it = 0; it < WIT; ++it) {
         if (wlo[it] >= 0) {
           float v[8];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v[e] = wok[it] ? wv[it][0][e] : 0.f;
-            v[4 + e] = wok[it] ? wv[it][1][e] : 0.f;
-          }
+          wv[it].get(v);
           put_planes<NP>(wl + wlo[it] + (WCH > 1 ? (c0 / PC) * WCS : 0), PC, v, false);
         }
       }
@@ -324,6 +350,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv3x3_x3_kernel(const X3Arg
   float bj[NT], s1[NT], s2[NT];
   BnBwdLane bl[NT];
   const bool bnb = !FWD && p.bny;
+  const int64_t obytes = (int64_t)p.NF * p.OH * p.OW * p.N * TB;
+  const __amdgpu_buffer_rsrc_t out_rs = s2_rsrc(p.out, obytes);
+  const __amdgpu_buffer_rsrc_t y_rs = s2_rsrc(bnb ? p.bny : p.out, bnb ? obytes : 0);
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int col = n0 + nt * 32 + j;
@@ -333,7 +362,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv3x3_x3_kernel(const X3Arg
   }
   f32x16 acc[NT];
   const int nitems = (t1 - t0) * nch;
-  if (nitems > 0) fetch(t0, 0, true);
+  if (nitems > 0) fetch(t0, 0, true, true);
   for (int item = 0; item < nitems; ++item) {
     const int tile = t0 + item / nch, ch = item % nch;
     const bool wnow = WCH > 1 ? item < nch : (nch > 1 || item == 0);
@@ -343,7 +372,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv3x3_x3_kernel(const X3Arg
     __syncthreads();
     if (item + 1 < nitems) {
       const int nx = item + 1;
-      fetch(t0 + nx / nch, nx % nch, WCH > 1 ? nx < nch : nch > 1);
+      fetch(t0 + nx / nch, nx % nch, WCH > 1 ? nx < nch : nch > 1, nchc > 1);
     }
     if (ch == 0) {
 #pragma unroll
@@ -391,38 +420,40 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv3x3_x3_kernel(const X3Arg
       // row = pixel (r&3) + 8(r>>2) + 4h of the wave's 32, column = channel n0 + 32 nt + j
       int img0, oy0, ox0;
       origin(tile, img0, oy0, ox0);
-      float yb[16][NT];
-      if (bnb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          int qi, qy, qx;
-          tile_pixel<S, NI, TH, TW, NW>(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, qi, qy, qx);
-          const int oy = oy0 + qy, ox = ox0 + qx, img = img0 + qi;
-          const bool ok = img < p.NF && oy < p.OH && ox < p.OW;
-          const int64_t base = ok ? (((int64_t)img * p.OH + oy) * p.OW + ox) * p.N : 0;
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) yb[r][nt] = BnBwdLane::ld<AB>(p.bny, base + min(n0 + nt * 32 + j, p.N - 1));
-        }
-      }
+      // branch-free: stores and y loads go through buffer resources at 32-bit offsets from the tile origin, a pixel
+      // outside the frame (or a channel >= N) at S2_OOB -- the store is dropped, the load reads 0 and the sums add
+      // exact zeros for it
+      const int obase = (((img0 * p.OH + oy0) * p.OW + ox0) * p.N + n0 + j) * TB;
+      int off[16][NT];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int qi, qy, qx;
         tile_pixel<S, NI, TH, TW, NW>(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, qi, qy, qx);
-        const int oy = oy0 + qy, ox = ox0 + qx, img = img0 + qi;
-        if (img < p.NF && oy < p.OH && ox < p.OW) {
-          TA* o = out + (((int64_t)img * p.OH + oy) * p.OW + ox) * p.N + n0 + j;
+        const bool ok = img0 + qi < p.NF && oy0 + qy < p.OH && ox0 + qx < p.OW;
+        const int o = obase + (((qi * p.OH + qy) * p.OW + qx) * p.N) * TB;
 #pragma unroll
-          for (int nt = 0; nt < NT; ++nt) {
-            if (n0 + nt * 32 + j < p.N) {
-              const float v = acc[nt][r] + bj[nt];
-              act_st(o + nt * 32, v);
-              if (FWD) {
-                s1[nt] += v;
-                s2[nt] = fmaf(v, v, s2[nt]);
-              } else if (bnb) {
-                bl[nt].template add<AB>(yb[r][nt], v, s1[nt], s2[nt]);
-              }
-            }
+        for (int nt = 0; nt < NT; ++nt) off[r][nt] = (ok && n0 + nt * 32 + j < p.N) ? o + nt * 32 * TB : S2_OOB;
+      }
+      float yb[16][NT];
+      if (bnb) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+          for (int nt = 0; nt < NT; ++nt) yb[r][nt] = buf_ld<AB>(y_rs, off[r][nt]);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          const bool in = off[r][nt] != S2_OOB;
+          const float v = acc[nt][r] + bj[nt];
+          buf_st<AB>(out_rs, off[r][nt], v);
+          if (FWD) {
+            const float vm = in ? v : 0.f;
+            s1[nt] += vm;
+            s2[nt] = fmaf(vm, vm, s2[nt]);
+          } else if (bnb) {
+            bl[nt].template add<AB>(yb[r][nt], v, s1[nt], s2[nt], in);
           }
         }
       }
@@ -467,8 +498,6 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
   static_assert(NP == 3 || NP == 1, "three split planes (fp32 numerics) or one (bf16 operands)");
   static_assert(!AB || NP == 1, "bf16 storage with bf16 operands only");
   using TA = act_t<AB>;
-  const TA* src = reinterpret_cast<const TA*>(p.src);
-  TA* out = reinterpret_cast<TA*>(p.out);
   static_assert(NI * TH * TW == 32 * NW, "a wave owns 32 output pixels");
   constexpr int S = 1, NTHR = 64 * NW, NC = 32, G8 = PC / 8;
   constexpr int PH = TH + 2, PW = TW + 2, PROWS = NI * PH * PW;
@@ -499,13 +528,26 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
   // patch staging: 16 consecutive rows of one channel group per 16-lane write phase (see conv3x3_x3_kernel)
   const int g8p = G8 == 2 ? (tid >> 4) & 1 : g8;
   auto prow = [](int q) { return G8 == 2 ? ((q >> 5) << 4) + (q & 15) : q / G8; };
+  // (staging loads and epilogue stores through buffer resources, masked lanes at S2_OOB: see conv3x3_x3_kernel; pok
+  // is kept for BN on load alone)
   struct Regs {
-    act_raw4<AB> pv[PIT][2];
+    Piece8<AB> pv[PIT];
     bool pok[PIT];
-    f32x4 wv[WIT][2];
-    bool wok[WIT];
+    Piece8<false> wv[WIT];
   };
   Regs R0, R1;
+  constexpr int TB = (int)sizeof(TA);
+  const __amdgpu_buffer_rsrc_t src_rs = s2_rsrc(p.src, (int64_t)p.NF * p.IH * p.IW * p.C * TB);
+  const __amdgpu_buffer_rsrc_t w_rs = s2_rsrc(p.w, (int64_t)p.N * 9 * p.C * 4);
+  // weight piece it: byte offset of its 8 channels in chunk 0 (S2_OOB: past the last output channel)
+  int wgo[WIT];
+#pragma unroll
+  for (int it = 0; it < WIT; ++it) {
+    // (threads past the slice redo its last item: same loads, same LDS bytes -- no divergent branch in the stash)
+    const int q = min(tid + it * NTHR, WQ - 1);
+    const int n = q / (9 * G8), t = (q / G8) % 9;
+    wgo[it] = n0 + n < p.N ? (((n0 + n) * 9 + (FWD ? t : 8 - t)) * p.C + g8 * 8) * 4 : S2_OOB;
+  }
   auto origin = [&](int tile, int& img0, int& oy0, int& ox0) {
     img0 = (tile / tiles_per_img) * NI;
     const int tr = tile % tiles_per_img;
@@ -514,25 +556,17 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
   };
   auto fetch_w = [&](Regs& R, int ch) {
 #pragma unroll
-    for (int it = 0; it < WIT; ++it) {
-      // (threads past the slice redo its last item: same loads, same LDS bytes -- no divergent branch in the stash)
-      const int q = min(tid + it * NTHR, WQ - 1);
-      const int n = q / (9 * G8), t = (q / G8) % 9;
-      R.wok[it] = n0 + n < p.N;
-      const float* s = p.w + ch * PC + g8 * 8 + (R.wok[it] ? ((int64_t)(n0 + n) * 9 + (FWD ? t : 8 - t)) * p.C : (int64_t)0);
-      R.wv[it][0] = *reinterpret_cast<const f32x4*>(s);
-      R.wv[it][1] = *reinterpret_cast<const f32x4*>(s + 4);
-    }
+    for (int it = 0; it < WIT; ++it) R.wv[it].load(w_rs, s2_uadd(wgo[it], ch * PC * 4));
   };
-  // loop-invariant piece geometry, 32-bit offsets from the tile's patch origin (the host keeps the input below 2^31
-  // elements): patch piece it = (image, patch row, patch column) packed
+  // loop-invariant piece geometry, 32-bit byte offsets from the tile's patch origin (the host keeps the input below
+  // 2 GB): patch piece it = (image, patch row, patch column) packed
   int pgeo[PIT], pgo[PIT];
 #pragma unroll
   for (int it = 0; it < PIT; ++it) {
     const int row = min(prow(tid + it * NTHR), PROWS - 1);  // (past the patch: the last row again, see fetch_w)
     const int im = row / (PH * PW), rr = row % (PH * PW), ry = rr / PW, rx = rr % PW;
     pgeo[it] = (im << 16) | (ry << 8) | rx;
-    pgo[it] = ((im * p.IH + ry) * p.IW + rx) * p.C + g8p * 8;
+    pgo[it] = (((im * p.IH + ry) * p.IW + rx) * p.C + g8p * 8) * TB;
   }
   auto fetch = [&](Regs& R, int item) {
     const int tile = t0 + item / nch, ch = item % nch;
@@ -541,15 +575,13 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
     const int iy0 = oy0 - 1, ix0 = ox0 - 1;
     // (block-uniform) the whole patch inside the frames
     const bool inner = iy0 >= 0 && ix0 >= 0 && iy0 + PH <= p.IH && ix0 + PW <= p.IW && img0 + NI <= p.NF;
-    const int base = ((img0 * p.IH + iy0) * p.IW + ix0) * p.C + ch * PC;
+    const int base = (((img0 * p.IH + iy0) * p.IW + ix0) * p.C + ch * PC) * TB;
 #pragma unroll
     for (int it = 0; it < PIT; ++it) {
       const int g = pgeo[it], im = g >> 16, ry = (g >> 8) & 255, rx = g & 255;
       R.pok[it] = inner || (img0 + im < p.NF && (unsigned)(iy0 + ry) < (unsigned)p.IH &&
                             (unsigned)(ix0 + rx) < (unsigned)p.IW);
-      const TA* s = src + (R.pok[it] ? base + pgo[it] : 0);
-      R.pv[it][0] = act_ld4(s);
-      R.pv[it][1] = act_ld4(s + 4);
+      R.pv[it].load(src_rs, R.pok[it] ? base + pgo[it] : S2_OOB);
     }
     if (wper) fetch_w(R, ch);
   };
@@ -559,12 +591,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
       const int row = min(prow(tid + it * NTHR), PROWS - 1);
       const int c0 = (item % nch) * PC + g8p * 8;
       float v[8];
-      const f32x4 v0 = act_f4(R.pv[it][0]), v1 = act_f4(R.pv[it][1]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[e] = R.pok[it] ? v0[e] : 0.f;
-        v[4 + e] = R.pok[it] ? v1[e] : 0.f;
-      }
+      R.pv[it].get(v);  // (a masked piece was loaded as zeros)
       if constexpr (FWD) {
         // zero padding stays zero: padded taps read 0 in the reference's zero-padded relu(bn(y)) (selects, no branch;
         // NaN propagates like torch's relu)
@@ -572,7 +599,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
           const bool ok = R.pok[it];
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            const float a = fmaf(e < 4 ? v0[e] : v1[e - 4], bnl[c0 + e], bnl[CMAX + c0 + e]);
+            const float a = fmaf(v[e], bnl[c0 + e], bnl[CMAX + c0 + e]);
             v[e] = (a <= 0.f || !ok) ? 0.f : a;
           }
         }
@@ -585,11 +612,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
     {
       const int n = q / (9 * G8), t = (q / G8) % 9;
       float v[8];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[e] = R.wok[it] ? R.wv[it][0][e] : 0.f;
-        v[4 + e] = R.wok[it] ? R.wv[it][1][e] : 0.f;
-      }
+      R.wv[it].get(v);
       put_planes<NP>(wimg + n * WP + seg * WCS + t * NP * PC + g8 * 8, PC, v, false);
     }
   };
@@ -627,6 +650,9 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
   BnBwdLane bl;
   const bool bnb = !FWD && p.bny;
   if (bnb) bl.load(p.bnst, p.N, min(n0 + j, p.N - 1));
+  const int64_t obytes = (int64_t)p.NF * p.OH * p.OW * p.N * TB;
+  const __amdgpu_buffer_rsrc_t out_rs = s2_rsrc(p.out, obytes);
+  const __amdgpu_buffer_rsrc_t y_rs = s2_rsrc(bnb ? p.bny : p.out, bnb ? obytes : 0);
   f32x16 acc;
 
   auto step = [&](auto curc, int k) {
@@ -683,32 +709,32 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
     if (ch == nch - 1) {
       int img0, oy0, ox0;
       origin(t0 + k / nch, img0, oy0, ox0);
-      float yb[16];
-      if (bnb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          int qi, qy, qx;
-          tile_pixel<S, NI, TH, TW, NW>(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, qi, qy, qx);
-          const int oy = oy0 + qy, ox = ox0 + qx, img = img0 + qi;
-          const bool ok = img < p.NF && oy < p.OH && ox < p.OW;
-          yb[r] = BnBwdLane::ld<AB>(p.bny, (ok ? (((int64_t)img * p.OH + oy) * p.OW + ox) * p.N : 0) + min(n0 + j, p.N - 1));
-        }
-      }
+      // branch-free, as conv3x3_x3_kernel's epilogue
+      const int obase = (((img0 * p.OH + oy0) * p.OW + ox0) * p.N + n0 + j) * TB;
+      int off[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int qi, qy, qx;
         tile_pixel<S, NI, TH, TW, NW>(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, qi, qy, qx);
-        const int oy = oy0 + qy, ox = ox0 + qx, img = img0 + qi;
-        if (img < p.NF && oy < p.OH && ox < p.OW && n0 + j < p.N) {
-          const float v = acc[r] + bj;
-          const int64_t oi = (((int64_t)img * p.OH + oy) * p.OW + ox) * p.N + n0 + j;
-          act_st(out + oi, v);
-          if (FWD) {
-            s1 += v;
-            s2 = fmaf(v, v, s2);
-          } else if (bnb) {
-            bl.template add<AB>(yb[r], v, s1, s2);
-          }
+        const bool ok = img0 + qi < p.NF && oy0 + qy < p.OH && ox0 + qx < p.OW && n0 + j < p.N;
+        off[r] = ok ? obase + (((qi * p.OH + qy) * p.OW + qx) * p.N) * TB : S2_OOB;
+      }
+      float yb[16];
+      if (bnb) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) yb[r] = buf_ld<AB>(y_rs, off[r]);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bool in = off[r] != S2_OOB;
+        const float v = acc[r] + bj;
+        buf_st<AB>(out_rs, off[r], v);
+        if (FWD) {
+          const float vm = in ? v : 0.f;
+          s1 += vm;
+          s2 = fmaf(vm, vm, s2);
+        } else if (bnb) {
+          bl.template add<AB>(yb[r], v, s1, s2, in);
         }
       }
     }
@@ -739,14 +765,22 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_x3p_kernel(const X3Args p)
   }
 }
 
+// every tensor the kernels address through a buffer resource (input, output = the fused BN-backward's y, weight image
+// of kd depth taps) ends below S2_OOB bytes
+static bool x3_fits_2gb(const X3Args& a, int act_bytes, int kd) {
+  return (int64_t)a.NF * a.IH * a.IW * a.C * act_bytes < (int64_t)S2_OOB &&
+         (int64_t)a.NF * a.OH * a.OW * a.N * act_bytes < (int64_t)S2_OOB &&
+         (int64_t)kd * a.N * 9 * a.C * 4 < (int64_t)S2_OOB;
+}
+
 constexpr int X3_DGRAD_BLOCKS = 512;  // target grid of the input gradients (as the forwards': 2 blocks per CU)
 
 template <int S, int NI, int TH, int TW, int NT, int PC, bool FWD, int NP, int WCH = 1, int NW = 4>
 static int launch_np(X3Args a, int max_blocks, hipStream_t st, int* nparts) {
   VAD_CHECK(!g_act_bf16 || NP == 1, "conv3x3_x3: bf16 activations need the bf16-operand kernels (conv_bf16)");
   VAD_CHECK(WCH == 1 || a.C == WCH * PC, "conv3x3_x3: resident weights need C == WCH * PC");
-  VAD_CHECK((int64_t)a.NF * a.IH * a.IW * a.C < ((int64_t)1 << 31) && (int64_t)a.N * 9 * a.C < ((int64_t)1 << 31),
-            "conv3x3_x3: 32-bit staging offsets (input and weight images below 2^31 elements)");
+  VAD_CHECK(x3_fits_2gb(a, g_act_bf16 ? 2 : 4, 1),
+            "conv3x3_x3: 32-bit buffer offsets (input, output and weight images below 2 GB each)");
   a.tiles_h = (int)cdiv(a.OH, TH);
   a.tiles_w = (int)cdiv(a.OW, TW);
   a.ntiles = (int)(cdiv(a.NF, NI) * a.tiles_h * a.tiles_w);
@@ -790,7 +824,8 @@ static int launch_pipe(X3Args a, int max_blocks, hipStream_t st, int* nparts) {
   constexpr int PC = 16, NW = 8, NP = 3;
   VAD_CHECK(!g_act_bf16 && !g_conv_bf16, "conv3x3_x3p: fp32 operands and activations only");
   VAD_CHECK(a.C % PC == 0 && a.C <= 256 && (WCH == 1 ? a.C > PC : a.C == WCH * PC), "conv3x3_x3p: channel count");
-  VAD_CHECK((int64_t)a.NF * a.IH * a.IW * a.C < ((int64_t)1 << 31), "conv3x3_x3p: 32-bit staging offsets");
+  VAD_CHECK(x3_fits_2gb(a, 4, 1),
+            "conv3x3_x3p: 32-bit buffer offsets (input, output and weight images below 2 GB each)");
   a.tiles_h = (int)cdiv(a.OH, TH);
   a.tiles_w = (int)cdiv(a.OW, TW);
   a.ntiles = (int)(cdiv(a.NF, NI) * a.tiles_h * a.tiles_w);
@@ -887,6 +922,8 @@ int conv3_x3_fwd(const Conv3Layer& L, const float* src, const float* src_stats, 
 // conv3x3_x3_kernel on 256-pixel tiles of 8 waves (three split planes: fp32-class numerics)
 template <int NI, int TH, int TW, int NT>
 static int launch_x3_3d(X3Args a, hipStream_t st) {
+  VAD_CHECK(x3_fits_2gb(a, 4, 3),
+            "conv3d_x3_fwd: 32-bit buffer offsets (input, output and weight images below 2 GB each)");
   a.tiles_h = (int)cdiv(a.OH, TH);
   a.tiles_w = (int)cdiv(a.OW, TW);
   a.ntiles = (int)(cdiv(a.NF, NI) * a.tiles_h * a.tiles_w);
@@ -988,13 +1025,6 @@ __device__ __forceinline__ void dgrad_s2x3_class(f32x16 (&acc)[NT], const __bf16
     }
   }
 }
-
-constexpr int S2_OOB = 0x7ffffff0;  // a byte offset past every buffer's end: the load returns zeros
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t s2_rsrc(const void* p, int64_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0,
-                                           (int)(bytes < (int64_t)S2_OOB ? bytes : (int64_t)S2_OOB), 0x00020000);
-}
-__device__ __forceinline__ int s2_add(int off, int add) { return off == S2_OOB ? S2_OOB : off + add; }
 
 // W3: the weight slices come pre-split (p.w3, PC == 16, NP == 3): plain 16-B copies instead of the fp32 load + split
 template <int NT, int PC, int NP, bool AB = false, bool W3 = false>

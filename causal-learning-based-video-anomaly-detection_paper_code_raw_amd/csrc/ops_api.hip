@@ -35,6 +35,23 @@ int vad_conv3x3_dgrad(const float* dy_nhwc, int NF, int Ci, int IH, int IW, cons
   return conv3_dgrad(L, dy_nhwc, wd_scratch, dx_nhwc, (hipStream_t)stream);
 }
 
+int vad_conv3x3_forward_bn(const float* x_nhwc, const float* src_stats, int NF, int Ci, int IH, int IW, const float* w,
+                           const float* bias, int Co, int stride, float* y_nhwc, float* wf_scratch, float* wd_scratch,
+                           float* partials, int* nparts, int* parts_cm, void* stream) {
+  Conv3Layer L{NF, Ci, Co, IH, IW, (IH - 1) / stride + 1, (IW - 1) / stride + 1, stride};
+  if (w) VAD_TRY(conv3_prep_weights(w, L, wf_scratch, wd_scratch, (hipStream_t)stream));  // w == NULL: prepared
+  return conv3_fwd(L, x_nhwc, src_stats, wf_scratch, bias, y_nhwc, partials, nparts, (hipStream_t)stream, parts_cm);
+}
+
+int vad_conv3x3_dgrad_bnfuse(const float* dy_nhwc, int NF, int Ci, int IH, int IW, const float* w, int Co, int stride,
+                             float* dx_nhwc, float* wf_scratch, float* wd_scratch, const float* y_nhwc,
+                             const float* stats, float* parts, int64_t parts_floats, int* nparts, void* stream) {
+  Conv3Layer L{NF, Ci, Co, IH, IW, (IH - 1) / stride + 1, (IW - 1) / stride + 1, stride};
+  if (w) VAD_TRY(conv3_prep_weights(w, L, wf_scratch, wd_scratch, (hipStream_t)stream));  // w == NULL: prepared
+  const BnBwdFuse f{y_nhwc, stats, parts, parts_floats, nparts};
+  return conv3_dgrad(L, dy_nhwc, wd_scratch, dx_nhwc, (hipStream_t)stream, &f);
+}
+
 }  // extern "C"
 
 extern "C" int vad_conv3x3_wgrad(const float* x_nhwc, const float* dy_nhwc, int NF, int Ci, int IH, int IW, int Co,

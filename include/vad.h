@@ -215,6 +215,18 @@ int vad_conv3x3_forward(const float* x_nhwc, int NF, int Ci, int IH, int IW, con
 /* input gradient of the same conv (transposed conv; stride-2 split into four parity classes) */
 int vad_conv3x3_dgrad(const float* dy_nhwc, int NF, int Ci, int IH, int IW, const float* w, int Co, int stride,
                       float* dx_nhwc, float* wf_scratch, float* wd_scratch, void* stream);
+/* vad_conv3x3_forward with the fused-step extras: src_stats (nullable) = the BatchNorm state of the layer that made x,
+ * [mean | invstd | scale | shift] (4 Ci floats): the conv reads relu(scale x + shift), zero-padded; *nparts = rows of
+ * BN partial sums written to partials ([nparts][2 Co], or [2 Co][nparts] when *parts_cm comes back 1) */
+int vad_conv3x3_forward_bn(const float* x_nhwc, const float* src_stats, int NF, int Ci, int IH, int IW, const float* w,
+                           const float* bias, int Co, int stride, float* y_nhwc, float* wf_scratch, float* wd_scratch,
+                           float* partials, int* nparts, int* parts_cm, void* stream);
+/* vad_conv3x3_dgrad with the BN-backward reduce of the layer that made the conv's input fused into its epilogue:
+ * y = that layer's raw output (dx's dims), stats = its BN state (4 Ci floats); the per-block sums of dZ and dZ xhat land
+ * column-major [2 Ci][*nparts] in parts (parts_floats floats); *nparts = 0 when the dispatched kernel does not fuse */
+int vad_conv3x3_dgrad_bnfuse(const float* dy_nhwc, int NF, int Ci, int IH, int IW, const float* w, int Co, int stride,
+                             float* dx_nhwc, float* wf_scratch, float* wd_scratch, const float* y_nhwc,
+                             const float* stats, float* parts, int64_t parts_floats, int* nparts, void* stream);
 /* kernel tuning knobs (sweeps, A/B of kernel variants): the keys, their defaults and meanings are the list in
  * csrc/tuning.h.  Process-global, except "conv_bf16" and "act_bf16" (the calling thread's).  An unknown key fails with
  * the error "unknown tuning key <key>". */
